@@ -2,10 +2,16 @@
 global batch 2048) on N MI355X GPUs — one full optimisation step per "step": all microbatches fwd+bwd, gradient
 exchange (N > 1), clip, AdamW.  Prints ONE JSON line (contract in the task description).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: spawns its own N ranks, one per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   (N > 1: spawns its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
-Extra keys of the line (the headline fields are unchanged by them):
+A plain run sets up, warms up, times the K steps and prints the headline fields; at N > 1 also
+  dp             ranks verified by an all-reduce of ones over RCCL, exchange format, buckets, and the time the compute
+                 stream waited for the gradient exchange after the last backward kernel of the timed steps (`exposed_comm_ms`).
+--dump-outputs DIR then writes what the last timed step returned to its caller as float32 .npy files (see dump_outputs); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+Extra keys of the line with --full, each measured after the headline (the headline fields are unchanged by them):
   other_stages   the same full step on the reference's other stage configs (BASELINE.json configs[3], [4]):
                  res_256_finetune (mask 0: 256 backbone tokens) and res_512_pretrain (64x64 latents, pos_interp_scale 2),
                  1 warm-up + 5 timed steps each at microbatch 256 (their YAMLs say 64 / 32: stated per stage), N = 1 only
@@ -21,8 +27,6 @@ Extra keys of the line (the headline fields are unchanged by them):
   roofline_hbm   the bandwidth-bound kernel classes (attention, LayerNorm, QK-LayerNorm, SwiGLU, gate backward, split-K reduce):
                  algorithmic bytes / per-launch HIP-event time against the 8 TB/s HBM3E peak AND against the streaming envelope
                  measured on this chip for the class's read : write mix (scripts/hbm_envelope.hip), from the same profiling step;
-  dp             (N > 1) ranks verified by an all-reduce of ones over RCCL, exchange format, buckets, and the time the
-                 compute stream waited for the gradient exchange after the last backward kernel (`exposed_comm_ms`);
   cpu_baseline   the CPU restatement of the reference step on the host cores (kind "port": the reference is pure Python and
                  /root/reference does not travel to the GPU box), >= 3 timed steps, threads used and host cores stated.
 """
@@ -271,6 +275,32 @@ def gemm_traffic():
     return (None if info["stale"] else t.get("bytes_per_launch")), info
 
 
+DUMP_PER_TENSOR = 4096              # sampled elements per parameter tensor (XL/2: 476 tensors -> 1.58 M elements, 6.3 MB per array)
+DUMP_SEED = 0
+
+
+def dump_outputs(head, loss, out_dir):
+    """--dump-outputs: what the caller of the timed step holds after the last one -- its loss and the updated training state
+    (fp32 master weights, AdamW first and second moments) -- as float32 DIR/<name>.npy.  The state is 1.17 G elements per array,
+    so every parameter tensor contributes the same seeded sample of min(numel, DUMP_PER_TENSOR) elements, in named_parameters()
+    order (independent of the flat buffer's layout)."""
+    import numpy as np
+    dit, opt = head.model.dit, head.trainer.opt
+    offs = dit.flat_buffers()["offs"]
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = []
+    for name, p in dit.named_parameters():
+        n = p.numel()
+        pick = np.arange(n) if n <= DUMP_PER_TENSOR else np.sort(rng.choice(n, DUMP_PER_TENSOR, replace=False))
+        idx.append(offs[name] + pick)
+    idx = torch.from_numpy(np.concatenate(idx)).to(opt.m.device)
+    arrays = {"loss": torch.tensor([loss], dtype=torch.float32), "params": dit.flat_buffers()["p"][idx],
+              "adamw_exp_avg": opt.m[idx], "adamw_exp_avg_sq": opt.v[idx]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -297,14 +327,22 @@ def main():
                          "memory setting (Composer also accepts 'auto'); the accumulated gradient of the rank batch is the same "
                          "for any split, and 288 GB of HBM3E holds 1024 (205 GB peak at N=1)")
     ap.add_argument("--arch", default="MicroDiT_XL_2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-other-stages", action="store_true", help="skip the res_256_finetune / res_512_pretrain / microbatch-256 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the roofline profiling step, the microbatch-256 / 248-CU / rank-of-8 legs, "
+                         "the other stages and the CPU baseline (each can be left out by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and a fixed sample of the training state after the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the roofline profiling step")
+    ap.add_argument("--no-other-stages", action="store_true", help="with --full: skip the res_256_finetune / res_512_pretrain / microbatch-256 legs")
     ap.add_argument("--attn-bwd", default="auto", choices=["auto", "pair", "fused1", "fused2", "fused2s", "stream"],
                     help="A/B runs: force one attention-backward kernel wherever it covers the shape (default: the library's rule)")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rank-probe", action="store_true", help=argparse.SUPPRESS)   # tests: every rank reports itself and exits (no GPU needed)
     args = ap.parse_args()
+    profile = args.full and not args.no_profile
+    other_stages = args.full and not args.no_other_stages
+    with_cpu_baseline = args.full and not args.no_cpu_baseline
     if args.cpu_baseline_worker:
         _cpu_baseline_worker()
         return
@@ -367,6 +405,10 @@ def main():
         head.model.dit.engine.attn_bwd_prefer = {"pair": 1, "fused1": 2, "fused2": 3, "fused2s": 4, "stream": 5}[args.attn_bwd]
     elapsed, loss = head.timed(args.steps, args.warmup, world)
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs:
+        head.trainer.consolidate()          # sharded optimiser (N > 1): every rank gathers the whole state; a no-op otherwise
+        if rank == 0:
+            dump_outputs(head, loss, args.dump_outputs)
     value = args.global_batch * args.steps / elapsed
     gf = FWD_BWD_GFLOP_PER_IMG[("res256", 0.75)]
     out = {
@@ -398,7 +440,7 @@ def main():
 
     if args.attn_bwd != "auto":
         out["config"]["attn_bwd_forced"] = args.attn_bwd
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and profile:
         # ---- roofline leg: per-launch HIP events around every launch of the dominant kernel (the MFMA GEMM) in one
         # extra, untimed step (events are recorded on the stream the kernels are launched on).
         eng = head.model.dit.engine
@@ -444,7 +486,7 @@ def main():
                                "streaming_envelope_tbs": HBM_ENVELOPE_TBS,
                                "streaming_envelope_source": "scripts/hbm_envelope.hip on MI355X, profiles/r4_hbm_envelope.txt (no-arithmetic kernels of the same access shapes)",
                                "kernels": dict(sorted(hb.items(), key=lambda kv: -kv[1]["total_ms"]))}
-    if world == 1 and not args.no_other_stages:
+    if world == 1 and other_stages:
         # ---- the YAML microbatch (the per-rank shape of an 8-GPU run) on the same model
         head.trainer.microbatch_size = 256
         e256, _ = head.timed(2, 1, 1)
@@ -480,7 +522,7 @@ def main():
         eng = None
         head.trainer.microbatch_size = args.microbatch
     head.close()
-    if world == 1 and not args.no_other_stages:
+    if world == 1 and other_stages:
         other = {}
         for name in ("res_256_finetune", "res_512_pretrain"):
             st = Stage(name, args.arch, args.global_batch, STAGES[name]["microbatch"], 1, 0)
@@ -493,10 +535,10 @@ def main():
                            "step_mfma_frac": v * FWD_BWD_GFLOP_PER_IMG[STAGES[name]["key"]] / 1e3 / MFMA_BF16_DENSE_PEAK_TFLOPS}
             st.close()
         out["other_stages"] = other
-    if rank == 0 and world > 1 and not args.no_cpu_baseline:
+    if rank == 0 and world > 1 and with_cpu_baseline:
         out["cpu_baseline"] = {"value": None, "unit": "images/sec", "cores": None, "kind": "port",
                                "sample": "measured at N=1 only (the other ranks would idle behind it)"}
-    elif rank == 0 and not args.no_cpu_baseline:
+    elif rank == 0 and with_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline()
         except Exception as e:  # host too small for the XL/2 oracle: report, do not fail the GPU number

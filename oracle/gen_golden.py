@@ -336,7 +336,29 @@ def gen_forward_return():
     print("tiny_forward_return.npz", {k: (v.tolist() if hasattr(v, "tolist") else v) for k, v in out.items()})
 
 
+def gen_configs():
+    """The reference's stage configs (configs/*.yaml) as yaml.safe_load returns them, `${}` interpolations unresolved, minus the
+    image monitor's prompt list: tests/test_config_cli.py checks the repo's configs and the config loader against these values."""
+    import json
+    import yaml
+    cdir = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(ref_model.__file__))), "configs")   # <reference>/configs
+    out = {}
+    for fn in sorted(os.listdir(cdir)):
+        if fn.endswith(".yaml"):
+            with open(os.path.join(cdir, fn)) as fh:
+                cfg = yaml.safe_load(fh)
+            cfg["callbacks"]["image_monitor"].pop("prompts")
+            out[fn[:-len(".yaml")]] = cfg
+    with open(os.path.join(OUT, "reference_configs.json"), "w") as fh:
+        json.dump(out, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("reference_configs.json", sorted(out))
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "configs":
+        gen_configs()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "forward_return":
         gen_forward_return()
         sys.exit(0)

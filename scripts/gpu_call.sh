@@ -89,7 +89,7 @@ PY
       # bench.py --gpus 2 with BOTH ranks on this one GPU over gloo (host-bounced collectives): a functional run of the N > 1
       # bench path (dp block of the JSON line, sharded optimiser step), not a measurement
       MD_DIST_BACKEND=gloo MD_DP_MODE=${MD_DP_MODE:-sharded} MD_DP_EXCHANGE=bf16 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --microbatch 256 --no-cpu-baseline --no-other-stages $arg > "$log" 2>&1
+        --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --microbatch 256 --full --no-cpu-baseline --no-other-stages $arg > "$log" 2>&1
       grep "^{" "$log" | tail -n 1 > gpurun_out/${tag}_bench_dp2_gloo.json; cut -c1-600 gpurun_out/${tag}_bench_dp2_gloo.json; tail -n 5 "$log" | cut -c1-300 ;;
     *) echo "unknown step $name" ;;
   esac

@@ -1,7 +1,7 @@
 """Host-side surface: the reference's YAML configs parse unchanged (no hydra / omegaconf), overrides and ${}
 interpolation behave like the reference CLI (README.md:34-50), every `_target_` maps to a native implementation, and
 the repo's own stage configs carry the reference's values."""
-import glob
+import json
 import os
 
 import pytest
@@ -11,7 +11,9 @@ from micro_diffusion_amd import config as mdcfg
 from micro_diffusion_amd.trainer import LRSchedule, parse_batches
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/configs"
+# The reference's configs/*.yaml as yaml.safe_load returns them (written by `python oracle/gen_golden.py configs`)
+with open(os.path.join(ROOT, "tests", "golden", "reference_configs.json")) as _fh:
+    REF = json.load(_fh)
 
 
 def _flat(d, p=""):
@@ -34,19 +36,20 @@ def test_stage_configs(name):
     for k, v in _flat(cfg).items():
         if k.endswith("_target_"):
             assert v in mdcfg.TARGETS, f"unmapped _target_ {v}"
-    if os.path.isdir(REF):            # build container only: same values as the reference's YAML
-        ref = mdcfg.coerce_numbers(yaml.safe_load(open(os.path.join(REF, name + ".yaml"))))
-        mine = mdcfg.coerce_numbers(yaml.safe_load(open(os.path.join(ROOT, "configs", name + ".yaml"))))
-        fr, fm = _flat(ref), _flat(mine)
-        diff = {k: (fr.get(k), fm.get(k)) for k in set(fr) | set(fm)
-                if fr.get(k) != fm.get(k) and "image_monitor" not in k and "wandb" not in k}
-        assert not diff, diff
+    # same values as the reference's YAML
+    ref = mdcfg.coerce_numbers(REF[name])
+    mine = mdcfg.coerce_numbers(yaml.safe_load(open(os.path.join(ROOT, "configs", name + ".yaml"))))
+    fr, fm = _flat(ref), _flat(mine)
+    diff = {k: (fr.get(k), fm.get(k)) for k in set(fr) | set(fm)
+            if fr.get(k) != fm.get(k) and "image_monitor" not in k and "wandb" not in k}
+    assert not diff, diff
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference configs only exist in the build container")
-def test_reference_yaml_parses_unchanged():
-    for fn in glob.glob(os.path.join(REF, "*.yaml")):
-        cfg = mdcfg.load_config(REF, os.path.basename(fn), ["trainer.device_train_microbatch_size=128"])
+def test_reference_yaml_parses_unchanged(tmp_path):
+    assert sorted(REF) == ["res_256_finetune", "res_256_pretrain", "res_512_finetune", "res_512_pretrain"]
+    for name, raw in REF.items():
+        (tmp_path / (name + ".yaml")).write_text(yaml.safe_dump(raw))
+        cfg = mdcfg.load_config(str(tmp_path), name + ".yaml", ["trainer.device_train_microbatch_size=128"])
         assert cfg["trainer"]["device_train_microbatch_size"] == 128
         assert cfg["callbacks"]["image_monitor"]["seed"] == cfg["seed"]
         assert mdcfg.locate(cfg["model"]["_target_"]).__name__ == "create_latent_diffusion"
