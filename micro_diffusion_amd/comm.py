@@ -7,17 +7,15 @@ Reference being replaced: Composer's FSDP gradient reduction (configs/res_256_pr
 from __future__ import annotations
 
 import ctypes
-import hashlib
 import os
-import subprocess
 from ctypes import POINTER, byref, c_char_p, c_int32, c_int64, c_void_p
+
+from . import native
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "csrc", "comm", "md_comm.cpp")
-_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-_HEADER = os.path.join(_INCLUDE, "microdit_comm.h")
+_HASHED = [_SRC, os.path.join(native.INCLUDE, "microdit_comm.h")]
 LIB_PATH = os.path.join(_HERE, "libmicrodit_comm.so")
-_HASH_PATH = os.path.join(_HERE, ".libmicrodit_comm.hash")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-D__HIP_PLATFORM_AMD__"]
 
@@ -26,54 +24,13 @@ UNIQUE_ID_BYTES = 128
 ABI_VERSION = 2
 
 
-def _source_hash() -> str:
-    h = hashlib.sha256()
-    for f in (_SRC, _HEADER):
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    h.update(" ".join(CXX_FLAGS).encode())
-    return h.hexdigest()
-
-
 def build(force: bool = False) -> str:
     """Compile csrc/comm/md_comm.cpp into libmicrodit_comm.so in-tree (idempotent; host code only: g++ + the HIP runtime).
-    With MD_COMM=native all N ranks of a node reach this together: an exclusive file lock serialises them (as hip.build does) and
-    the library is linked to a temporary name and renamed into place, so no rank can dlopen a half-written file."""
-    import fcntl
-    if not force and _up_to_date():          # nothing to do: no lock file is touched (a read-only install works)
-        return LIB_PATH
-    with open(os.path.join(_HERE, ".libmicrodit_comm.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            return _build_locked(force)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-
-
-def _up_to_date() -> bool:
-    if not (os.path.exists(LIB_PATH) and os.path.exists(_HASH_PATH)):
-        return False
-    with open(_HASH_PATH) as fh:
-        return fh.read().strip() == _source_hash()
-
-
-def _build_locked(force: bool) -> str:
-    want = _source_hash()
-    if not force and _up_to_date():
-        return LIB_PATH
-    cxx = os.environ.get("CXX", "g++")
-    tmp = f"{LIB_PATH}.{os.getpid()}.tmp"
-    cmd = [cxx, *CXX_FLAGS, "-I", _INCLUDE, "-I", os.path.join(ROCM, "include"), _SRC, "-o", tmp,
-           "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-ldl", f"-Wl,-rpath,{os.path.join(ROCM, 'lib')}"]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    if r.returncode != 0:
-        if os.path.exists(tmp):
-            os.unlink(tmp)
-        raise RuntimeError(f"{cxx} failed on md_comm.cpp:\n{r.stdout.decode(errors='replace')}")
-    os.replace(tmp, LIB_PATH)
-    with open(_HASH_PATH, "w") as fh:
-        fh.write(want)
-    return LIB_PATH
+    With MD_COMM=native all N ranks of a node reach this together (native.build serialises them)."""
+    rocm_lib = os.path.join(ROCM, "lib")
+    return native.build(LIB_PATH, native.source_hash(_HASHED, CXX_FLAGS), lambda tmp: native.run(
+        [os.environ.get("CXX", "g++"), *CXX_FLAGS, "-I", native.INCLUDE, "-I", os.path.join(ROCM, "include"), _SRC, "-o", tmp,
+         "-L", rocm_lib, "-lamdhip64", "-ldl", f"-Wl,-rpath,{rocm_lib}"]), force)
 
 
 _SIGS = {
@@ -103,19 +60,7 @@ _lib = None
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        stale = True
-        if os.path.exists(LIB_PATH) and os.path.exists(_HASH_PATH):
-            with open(_HASH_PATH) as fh:
-                stale = fh.read().strip() != _source_hash()
-        if stale:
-            build()
-        L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        if L.md_comm_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"libmicrodit_comm.so reports ABI version {L.md_comm_abi_version()}, this binding is written for {ABI_VERSION}")
-        _lib = L
+        _lib = native.load(build(), _SIGS, "md_comm_abi_version", ABI_VERSION)
     return _lib
 
 

@@ -7,17 +7,14 @@ CPU oracle or through PyTorch ops).
 from __future__ import annotations
 
 import ctypes
-import hashlib
 import os
-import subprocess
-import sys
 from ctypes import c_float, c_int, c_int32, c_int64, c_void_p, POINTER, Structure, byref
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(_HERE, "csrc")
-_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-LIB_PATH = os.path.join(_HERE, "libmicrodit_hip.so")
-_HASH_PATH = os.path.join(_HERE, ".libmicrodit_hip.hash")
+from . import native
+
+_CSRC = native.CSRC
+_HEADER = os.path.join(native.INCLUDE, "microdit_hip.h")
+LIB_PATH = os.path.join(os.path.dirname(_CSRC), "libmicrodit_hip.so")
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
                "-Wno-unused-result", "-Wno-inline-asm"]   # (inline-asm: gemm_w4's literal v[128:255] clobbers are "reserved" by design)
@@ -31,82 +28,36 @@ GEMM_VARIANT_NAMES = {"auto": 0, "reg128": 1, "dma128": 2, "paced256": 3, "pp256
 ATTN_BWD_AUTO, ATTN_BWD_FUSED_1PHASE, ATTN_BWD_FUSED_2PHASE, ATTN_BWD_FUSED_2PHASE_SPLIT, ATTN_BWD_STREAM_PAIR = 0, 2, 3, 4, 5   # (1: removed)
 
 
-def _sources():
-    return sorted(f for f in os.listdir(_CSRC) if f.endswith(".hip"))
+def _hashed_files():
+    """What the build reads: every file directly under csrc/ (headers and generated includes too), and the public header."""
+    return [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if os.path.isfile(os.path.join(_CSRC, f))] + [_HEADER]
 
 
 def _gemm_source_hash() -> str:
     """Hash of what determines the GEMM kernels alone (gemm*.hip, their headers and generated includes, md_common.h, the public header,
     the compiler flags): the key of profiles/*_gemm_traffic.json, so that an edit of attention.hip does not void a GEMM measurement."""
-    h = hashlib.sha256()
     files = [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC))
              if f.endswith((".hip", ".h", ".inc")) and (f.startswith("gemm") or f == "md_common.h")]
-    files.append(os.path.join(_INCLUDE, "microdit_hip.h"))
-    for f in files:
-        h.update(os.path.basename(f).encode())
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    h.update(" ".join(HIPCC_FLAGS).encode())
-    return h.hexdigest()
+    return native.source_hash(files + [_HEADER], HIPCC_FLAGS)
 
 
 def _source_hash() -> str:
-    h = hashlib.sha256()
-    files = [os.path.join(_CSRC, f) for f in sorted(os.listdir(_CSRC)) if f.endswith((".hip", ".h"))]
-    files.append(os.path.join(_INCLUDE, "microdit_hip.h"))
-    for f in files:
-        h.update(os.path.basename(f).encode())
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    h.update(" ".join(HIPCC_FLAGS).encode())
-    return h.hexdigest()
+    return native.source_hash(_hashed_files(), HIPCC_FLAGS)
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
-    """Compile every .hip under csrc/ for gfx950 and link libmicrodit_hip.so in-tree (idempotent).  Serialised across
-    processes by a file lock: with one process per GPU every rank may find the library stale at the same moment."""
-    import fcntl
-    os.makedirs(os.path.join(_CSRC, "build"), exist_ok=True)
-    with open(os.path.join(_CSRC, "build", ".lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            return _build_locked(force, verbose)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-
-
-def _build_locked(force: bool, verbose: bool) -> str:
-    want = _source_hash()
-    if not force and os.path.exists(LIB_PATH) and os.path.exists(_HASH_PATH):
-        with open(_HASH_PATH) as fh:
-            if fh.read().strip() == want:
-                return LIB_PATH
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        hipcc = "hipcc"
-    objdir = os.path.join(_CSRC, "build")
-    os.makedirs(objdir, exist_ok=True)
-    procs = []
-    objs = []
-    for src in _sources():
-        obj = os.path.join(objdir, src[:-4] + ".o")
-        objs.append(obj)
-        cmd = [hipcc, *HIPCC_FLAGS, "-I", _INCLUDE, "-c", os.path.join(_CSRC, src), "-o", obj]
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-    for src, p in procs:
-        out, _ = p.communicate()
-        if p.returncode != 0:
-            raise RuntimeError(f"hipcc failed on {src}:\n{out.decode(errors='replace')}")
-        if verbose and out.strip():
-            sys.stderr.write(out.decode(errors="replace"))
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB_PATH + ".tmp"]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    if r.returncode != 0:
-        raise RuntimeError(f"link failed:\n{r.stdout.decode(errors='replace')}")
-    os.replace(LIB_PATH + ".tmp", LIB_PATH)
-    with open(_HASH_PATH, "w") as fh:
-        fh.write(want)
-    return LIB_PATH
+    """Compile every .hip under csrc/ for gfx950 in parallel into csrc/build/<name>.o (scripts/build_*_variant.sh link against
+    those objects) and link libmicrodit_hip.so in-tree (idempotent)."""
+    def make(tmp):
+        hipcc = native.hipcc()
+        objdir = os.path.join(_CSRC, "build")
+        os.makedirs(objdir, exist_ok=True)
+        srcs = sorted(f for f in os.listdir(_CSRC) if f.endswith(".hip"))
+        objs = [os.path.join(objdir, f[:-4] + ".o") for f in srcs]
+        native.run(*([hipcc, *HIPCC_FLAGS, "-I", native.INCLUDE, "-c", os.path.join(_CSRC, f), "-o", o] for f, o in zip(srcs, objs)),
+                   verbose=verbose)
+        native.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", tmp])
+    return native.build(LIB_PATH, _source_hash(), make, force)
 
 
 class GemmProblem(Structure):
@@ -143,27 +94,19 @@ ABI_VERSION = 6        # MD_ABI_VERSION of include/microdit_hip.h this binding w
 def lib() -> ctypes.CDLL:
     """Load (once) the in-tree shared library; raise loudly when it is absent."""
     global _lib
-    if _lib is None and os.environ.get("MICRODIT_LIB"):       # experiments only: load an explicitly named build
-        _lib = ctypes.CDLL(os.environ["MICRODIT_LIB"])
-        _declare(_lib)
-        return _lib
     if _lib is None:
-        stale = True
-        if os.path.exists(LIB_PATH) and os.path.exists(_HASH_PATH):
-            with open(_HASH_PATH) as fh:
-                stale = fh.read().strip() != _source_hash()
-        if stale and (os.path.exists("/opt/rocm/bin/hipcc") or os.environ.get("HIPCC")):
-            build()                      # sources changed since the last build: never run a stale library
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} is missing: the MicroDiT HIP extension has not been built. "
-                "Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). "
-                "There is no CPU / PyTorch fallback for the training path.")
-        _lib = ctypes.CDLL(LIB_PATH)
-        _declare(_lib)
-        if _lib.md_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"libmicrodit_hip.so reports ABI version {_lib.md_abi_version()}, this binding is written for "
-                               f"{ABI_VERSION}; rebuild")
+        path = os.environ.get("MICRODIT_LIB")       # experiments only: load an explicitly named build
+        if not path:
+            stale = not native.up_to_date(LIB_PATH, _source_hash())
+            if stale and (os.path.exists("/opt/rocm/bin/hipcc") or os.environ.get("HIPCC")):
+                build()                      # sources changed since the last build: never run a stale library
+            if not os.path.exists(LIB_PATH):
+                raise RuntimeError(
+                    f"{LIB_PATH} is missing: the MicroDiT HIP extension has not been built. "
+                    "Run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). "
+                    "There is no CPU / PyTorch fallback for the training path.")
+            path = LIB_PATH
+        _lib = native.load(path, _SIGS, "md_abi_version", ABI_VERSION)
     return _lib
 
 
@@ -176,12 +119,12 @@ def check(code: int, what: str) -> None:
         raise RuntimeError(f"{what} failed with code {code} ({why})")
 
 
-# name -> argtypes; every function returns int and takes the stream last.
-_SIGS = {}
+# name -> (restype, argtypes); every launch function returns int and takes the stream last.
+_SIGS = {"md_abi_version": (c_int, [])}
 
 
 def _sig(name, *argtypes):
-    _SIGS[name] = list(argtypes)
+    _SIGS[name] = (c_int, list(argtypes))
 
 
 P, I64, I32, F32 = c_void_p, c_int64, c_int32, c_float
@@ -270,18 +213,9 @@ _sig("md_adamw_step", POINTER(AdamWArgs), P)
 _sig("md_adamw_step_ranges", POINTER(AdamWArgs), P, P, I32, P)
 
 
-def _declare(l: ctypes.CDLL) -> None:
-    l.md_abi_version.restype = c_int
-    l.md_abi_version.argtypes = []
-    for name, argtypes in _SIGS.items():
-        fn = getattr(l, name)  # AttributeError here = header/library mismatch, fail loudly
-        fn.restype = c_int
-        fn.argtypes = argtypes
-
-
 def exported_symbols():
     """Names the header declares (used by the CPU-side ABI test)."""
-    return ["md_abi_version", *_SIGS.keys()]
+    return list(_SIGS)
 
 
 def stream_ptr():

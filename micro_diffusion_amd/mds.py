@@ -5,20 +5,19 @@ a missing library raises."""
 from __future__ import annotations
 
 import ctypes
-import hashlib
 import os
-import subprocess
 from ctypes import POINTER, c_char_p, c_int, c_int32, c_int64, c_void_p, byref
 
 import numpy as np
 
+from . import native
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "csrc", "io", "mds_reader.cpp")
-_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-_HEADER = os.path.join(_INCLUDE, "microdit_io.h")
+_HASHED = [_SRC, os.path.join(native.INCLUDE, "microdit_io.h")]
 LIB_PATH = os.path.join(_HERE, "libmicrodit_io.so")
-_HASH_PATH = os.path.join(_HERE, ".libmicrodit_io.hash")
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall"]
+ABI_VERSION = 1
 
 OK, BAD_ARG, NOT_FOUND, BAD_FORMAT, UNSUPPORTED, SIZE_MISMATCH = 0, -1, -2, -3, -4, -5
 
@@ -29,29 +28,10 @@ class MDSError(RuntimeError):
         self.code = code
 
 
-def _source_hash() -> str:
-    h = hashlib.sha256()
-    for f in (_SRC, _HEADER):
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    h.update(" ".join(CXX_FLAGS).encode())
-    return h.hexdigest()
-
-
 def build(force: bool = False) -> str:
-    """Compile csrc/io/mds_reader.cpp into libmicrodit_io.so in-tree (idempotent)."""
-    want = _source_hash()
-    if not force and os.path.exists(LIB_PATH) and os.path.exists(_HASH_PATH):
-        with open(_HASH_PATH) as fh:
-            if fh.read().strip() == want:
-                return LIB_PATH
-    cxx = os.environ.get("CXX", "g++")
-    r = subprocess.run([cxx, *CXX_FLAGS, "-I", _INCLUDE, _SRC, "-o", LIB_PATH], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    if r.returncode != 0:
-        raise RuntimeError(f"{cxx} failed on mds_reader.cpp:\n{r.stdout.decode(errors='replace')}")
-    with open(_HASH_PATH, "w") as fh:
-        fh.write(want)
-    return LIB_PATH
+    """Compile csrc/io/mds_reader.cpp into libmicrodit_io.so in-tree (idempotent; every loader rank may reach this at once)."""
+    return native.build(LIB_PATH, native.source_hash(_HASHED, CXX_FLAGS), lambda tmp: native.run(
+        [os.environ.get("CXX", "g++"), *CXX_FLAGS, "-I", native.INCLUDE, _SRC, "-o", tmp]), force)
 
 
 _SIGS = {
@@ -81,20 +61,7 @@ _lib = None
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        stale = True
-        if os.path.exists(LIB_PATH) and os.path.exists(_HASH_PATH):
-            with open(_HASH_PATH) as fh:
-                stale = fh.read().strip() != _source_hash()
-        if stale:
-            build()
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        _lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(_lib, name)
-            fn.restype, fn.argtypes = res, args
-        if _lib.md_io_abi_version() != 1:
-            raise RuntimeError("libmicrodit_io.so ABI version mismatch; rebuild")
+        _lib = native.load(build(), _SIGS, "md_io_abi_version", ABI_VERSION)
     return _lib
 
 

@@ -8,7 +8,8 @@ src=gemm_pp.hip
 if [ "$1" == "--src" ]; then src=$2; shift 2; fi
 base=${src%.hip}
 mkdir -p scratch_libs/obj
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result "$@" -I include -c micro_diffusion_amd/csrc/$src -o scratch_libs/obj/${base}_$name.o
+hipcc_flags=$(python -c "from micro_diffusion_amd import hip; print(' '.join(hip.HIPCC_FLAGS))")
+/opt/rocm/bin/hipcc $hipcc_flags "$@" -I include -c micro_diffusion_amd/csrc/$src -o scratch_libs/obj/${base}_$name.o
 objs=$(ls micro_diffusion_amd/csrc/build/*.o | grep -v "/${base}.o")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs scratch_libs/obj/${base}_$name.o -o scratch_libs/lib_$name.so
 echo built scratch_libs/lib_$name.so

@@ -7,16 +7,16 @@ Usage: python scripts/check_pp_asm.py   (exit code 0 = ok)
 import collections
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "micro_diffusion_amd", "csrc", "gemm_pp.hip")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from micro_diffusion_amd import hip, native  # noqa: E402
+
+src = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else "gemm_pp.hip"
 with tempfile.TemporaryDirectory() as td:
     out = os.path.join(td, "gemm_pp.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
-                    "-Wno-unused-command-line-argument", "-I", os.path.join(ROOT, "include"), "-S", "--cuda-device-only", src, "-o", out], check=True)
+    native.compile_csrc(src, hip.HIPCC_FLAGS, out, "-S", "--cuda-device-only")
     lines = open(out).read().split("\n")
 
 kern, inasm, inloop = None, False, False

@@ -4,11 +4,11 @@ accumulator register (they belong to the k-loop: scripts/gen_w4_acc.py), and not
     python scripts/check_w4_asm.py [<gemm_w4 .s file>]     (without an argument: compiles gemm_w4.hip to assembly first; exit code 0 = ok)"""
 import os
 import re
-import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from micro_diffusion_amd import hip, native  # noqa: E402
 
 
 def audit(text):
@@ -42,9 +42,7 @@ if __name__ == "__main__":
     else:
         with tempfile.TemporaryDirectory() as td:
             out = os.path.join(td, "gemm_w4.s")
-            subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-inline-asm",
-                            "-Wno-unused-command-line-argument", "-I", os.path.join(ROOT, "include"), "-S", "--cuda-device-only",
-                            os.path.join(ROOT, "micro_diffusion_amd", "csrc", "gemm_w4.hip"), "-o", out], check=True)
+            native.compile_csrc("gemm_w4.hip", hip.HIPCC_FLAGS, out, "-S", "--cuda-device-only")
             text = open(out).read()
     names, problems = audit(text)
     print(f"{len(names)} w4 kernels, {len(problems)} problem lines")

@@ -4,7 +4,10 @@ gradient buffer exactly once — world_size 2, gloo backend, 127.0.0.1."""
 import ctypes
 import os
 import re
+import shutil
 import socket
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -321,6 +324,56 @@ def test_comm_library_exports_every_declared_symbol():
     assert L.md_comm_wait(None, 1, None) == -1 and L.md_comm_destroy(None) == -1
     t = ctypes.c_int64(0)
     assert L.md_comm_allreduce_bucket(None, None, 8, 0, None, ctypes.byref(t)) == -1
+
+
+# one process of the build-protocol tests: bring libanswer.so up to date with answer.cpp through native.build (g++, the compile held
+# for a moment so that a second process arrives while the first one builds), load it, print "built" if this process compiled
+_BUILD_CHILD = """
+import ctypes, sys, time
+sys.path.insert(0, sys.argv[1])
+from micro_diffusion_amd import native
+src, lib = sys.argv[2], sys.argv[3]
+def make(tmp):
+    print("built")
+    time.sleep(0.5)
+    native.run(["g++", "-shared", "-fPIC", src, "-o", tmp])
+native.build(lib, native.source_hash([src], ["-shared", "-fPIC"]), make)
+print("answer", native.load(lib, {"answer": (ctypes.c_int, [])}).answer())
+"""
+
+
+def _start_build(tmp_path):
+    return subprocess.Popen([sys.executable, "-c", _BUILD_CHILD, ROOT, str(tmp_path / "answer.cpp"), str(tmp_path / "libanswer.so")],
+                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+
+
+def _finish(p):
+    out = p.communicate(timeout=120)[0]
+    assert p.returncode == 0, out
+    return out.split()
+
+
+@pytest.mark.skipif(not shutil.which("g++"), reason="needs g++")
+def test_native_build_runs_the_compiler_only_when_sources_change(tmp_path):
+    """native.build (every native library of the project): an up-to-date library is loaded without a compiler run and without
+    creating a lock file (a read-only install works); an edit of a hashed source rebuilds it."""
+    (tmp_path / "answer.cpp").write_text('extern "C" int answer() { return 1; }\n')
+    assert _finish(_start_build(tmp_path)) == ["built", "answer", "1"]
+    os.unlink(tmp_path / ".libanswer.lock")
+    assert _finish(_start_build(tmp_path)) == ["answer", "1"]
+    assert not (tmp_path / ".libanswer.lock").exists()
+    (tmp_path / "answer.cpp").write_text('extern "C" int answer() { return 2; }\n')
+    assert _finish(_start_build(tmp_path)) == ["built", "answer", "2"]
+    assert sorted(os.listdir(tmp_path)) == [".libanswer.hash", ".libanswer.lock", "answer.cpp", "libanswer.so"]
+
+
+@pytest.mark.skipif(not shutil.which("g++"), reason="needs g++")
+def test_native_build_two_processes_at_once(tmp_path):
+    """Two processes that find the library missing at the same moment (every rank of a node does): one compiles while the other
+    waits on the lock, and both load the complete library."""
+    (tmp_path / "answer.cpp").write_text('extern "C" int answer() { return 3; }\n')
+    outs = [_finish(p) for p in [_start_build(tmp_path), _start_build(tmp_path)]]
+    assert sorted(outs) == [["answer", "3"], ["built", "answer", "3"]], outs
 
 
 def test_grouped_wgrad_host_logic():

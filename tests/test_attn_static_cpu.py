@@ -10,32 +10,12 @@
     reach past the image.
 """
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from micro_diffusion_amd import hip, native
+
 HIPCC = "/opt/rocm/bin/hipcc"
-
-
-def _kernel_resources(tmp_path):
-    src = os.path.join(ROOT, "micro_diffusion_amd", "csrc", "attention.hip")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result",
-                        "-I", os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage", "-c", src,
-                        "-o", str(tmp_path / "attn.o")], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = {}
-    for b in re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]:
-        name = b.split()[0]
-
-        def field(label):
-            m = re.search(label + r": (\d+)", b)
-            assert m, (label, name)
-            return int(m.group(1))
-        out[name] = dict(vgprs=field(r"VGPRs"), spill=field(r"VGPRs Spill"), scratch=field(r"ScratchSize \[bytes/lane\]"),
-                         lds=field(r"LDS Size \[bytes/block\]"), occ=field(r"Occupancy \[waves/SIMD\]"))
-    return out
 
 
 def _lds_1phase(hd, sqp, skp):
@@ -48,7 +28,7 @@ def _lds_2phase(hd, sqp, skp):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_attention_kernel_resources(tmp_path):
-    res = _kernel_resources(tmp_path)
+    res = native.resource_usage("attention.hip", hip.HIPCC_FLAGS, tmp_path / "attn.o")
 
     def find(kernel, *targs):
         tag = f"{kernel}ILi" + "ELi".join(str(t) for t in targs) + "EE"

@@ -7,12 +7,11 @@ backward sat at 134 VGPRs = 3 waves / SIMD until it stopped keeping an fp32 copy
 hipcc cross-compiles gfx950 without a GPU; -Rpass-analysis=kernel-resource-usage prints what the code object will ask for.
 """
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from micro_diffusion_amd import hip, native
+
 HIPCC = "/opt/rocm/bin/hipcc"
 FILES = ["norm.hip", "elementwise.hip", "routing.hip", "edm.hip", "optim.hip"]
 
@@ -35,30 +34,11 @@ OCCUPANCY = [
 ]
 
 
-def _resources(src, tmp_path):
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result",
-                        "-I", os.path.join(ROOT, "include"), "-Rpass-analysis=kernel-resource-usage", "-c",
-                        os.path.join(ROOT, "micro_diffusion_amd", "csrc", src), "-o", str(tmp_path / (src + ".o"))],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = {}
-    for b in re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]:
-        name = b.split()[0]
-
-        def field(label):
-            m = re.search(label + r": (\d+)", b)
-            assert m, (label, name)
-            return int(m.group(1))
-        out[name] = dict(vgprs=field(r"VGPRs"), spill=field(r"VGPRs Spill"), scratch=field(r"ScratchSize \[bytes/lane\]"),
-                         occ=field(r"Occupancy \[waves/SIMD\]"))
-    return out
-
-
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_no_spills_no_scratch_and_hot_kernel_occupancy(tmp_path):
     res = {}
     for f in FILES:
-        res.update(_resources(f, tmp_path))
+        res.update(native.resource_usage(f, hip.HIPCC_FLAGS, tmp_path / (f + ".o")))
     assert len(res) >= 50, f"expected the kernels of {FILES}, parsed {len(res)}"
     for name, v in res.items():
         assert v["spill"] == 0, f"{name} spills {v['spill']} VGPRs"
