@@ -1,0 +1,90 @@
+"""The shapes of tests/test_kernel_geometry_gpu.py and the launch geometry each one is meant to reach.
+
+Each case names the heuristic branch it exists for.  The GPU tests run the shapes; tests/test_kernel_geometry_cpu.py reads the
+heuristic constants out of the kernel sources and checks, through the functions below, that every shape still lands in the branch
+it claims.  A retune of a heuristic then fails on a CPU instead of quietly moving a GPU test off the production path.
+
+The functions restate the launch code of csrc/ with its constants as parameters (K: the dict the CPU test parses)."""
+from collections import namedtuple
+
+# ---------------------------------------------------------------------------------------------------------------- heuristics
+
+
+def nch(C):
+    """Chunks of 512 columns per lane: the template instance the LN / qkln / gate_bwd launchers pick (1, 2 or 4)."""
+    return 1 if C <= 512 else 2 if C <= 1024 else 4
+
+
+def ln_fwd_rpw(rows, K):
+    """md_ln_fwd: consecutive rows per wave."""
+    return max(1, min(K["ln_rpw_max"], -(-rows // K["ln_rpw_rows"])))
+
+
+def ln_grid_passes(items, K):
+    """md_qkln_*: grid-stride passes over `items` waves' worth of rows (4 waves per workgroup, at most ln_grid_max workgroups)."""
+    waves = 4 * max(1, min(K["ln_grid_max"], -(-items // 4)))
+    return -(-items // waves)
+
+
+def flat_grid_passes(items, K, key):
+    """ew_grid / egrid / rgrid: grid-stride passes over `items` threads' work (256 per workgroup, at most K[key] workgroups)."""
+    threads = 256 * max(1, min(K[key], -(-items // 256)))
+    return -(-items // threads), items % threads
+
+
+def finish_chunks(samples, K):
+    """ln_bwd_finish_kernel: sample chunks (gridDim.y) and the size of the last one."""
+    n = K["finish_chunk"]
+    return -(-samples // n), samples - (-(-samples // n) - 1) * n
+
+
+def loss_finish_strides(B, K):
+    """edm_loss_finish_kernel: how many lane-strided steps lane 0 takes over the batch."""
+    return -(-B // K["loss_finish_stride"])
+
+
+# ---------------------------------------------------------------------------------------------------------------- the cases
+LnFwd = namedtuple("LnFwd", "id rows rps C mod act pos rpw")           # rpw: rows per wave the case is for
+LN_FWD = [
+    LnFwd("rpw4-mb1024-C1024-mod", 65536, 64, 1024, True, 0, False, 4),
+    LnFwd("rpw4-mb1024-C512-plain", 65536, 64, 512, False, 0, False, 4),
+    LnFwd("rpw4-mb1024-C2048-mod-nch4", 65536, 64, 2048, True, 0, False, 4),
+    LnFwd("rpw5-crosses-samples-C1024-mod", 78848, 77, 1024, True, 0, False, 5),
+    LnFwd("rpw5-crosses-samples-C512-mod", 78848, 77, 512, True, 0, False, 5),
+    LnFwd("rpw5-captions-C1024-plain", 78848, 77, 1024, False, 0, False, 5),
+    LnFwd("rpw8-C1024-mod", 131072, 256, 1024, True, 0, False, 8),
+    LnFwd("rpw8-C512-plain", 131072, 256, 512, False, 0, False, 8),
+    LnFwd("rpw2-generic-gelu-tanh-C1024", 16448, 64, 1024, False, 1, False, 2),
+    LnFwd("rpw2-generic-pos-C512", 16448, 64, 512, False, 0, True, 2),
+]
+
+# form: "mod" (dscale / dshift into a 6 C stride, dscale_is_output), "scratch" (plain: zeroed [samples, C] scratch + dw),
+# "rps0" (plain, one sample: rows_per_sample = 0)
+LnBwd = namedtuple("LnBwd", "id rows rps C form accumulate")
+LN_BWD = [
+    LnBwd("mod-rpb64-mb1024-chunks64-acc1", 65536, 64, 1024, "mod", 1),
+    LnBwd("mod-rpb64-B40-3chunks-partial-acc0", 65600, 1640, 1024, "mod", 0),
+    LnBwd("scratch-dw-rpb32-B520-partial-chunk-acc0", 40040, 77, 512, "scratch", 0),
+    LnBwd("scratch-dw-rpb64-B1024-C2048-acc1", 78848, 77, 2048, "scratch", 1),
+    LnBwd("rps0-dw-rpb64-acc1", 65536, 0, 1024, "rps0", 1),
+]
+
+QkLn = namedtuple("QkLn", "id rows width hd S")
+QKLN = [
+    QkLn("grid-stride-5-passes-w1152-nch4", 40192, 1152, 64, 256),
+    QkLn("grid-stride-5-passes-w512-hd32", 40000, 512, 32, 64),
+]
+
+EW_N = 2 ** 24 + 8 * 37          # 2^21 + 37 16-byte items: the second grid-stride pass of ew_grid runs 37 threads
+EW_SMALL = 8
+Ew = namedtuple("Ew", "id n")
+EW = [Ew("second-pass-ragged", EW_N), Ew("n8", EW_SMALL)]
+# (rows, C) of the row-shaped elementwise kernels: > 2^21 16-byte items, last pass partial
+CAST_ROWS = (77 * 213, 1024)
+MEAN_TOKENS = (14564, 2, 1152)    # B, L, C: B * C / 8 = 2^21 + 64 items
+GATHER = (16400, 1024)            # rows moved, C: 2^21 + 2048 items (rgrid)
+
+EDM_B, EDM_C, EDM_HW, EDM_P = 130, 4, 64, 2      # 64 x 64 latents (res 512): T = 1024 tokens; 130 * 16384 items > 2^21
+
+GateBwd = namedtuple("GateBwd", "id B rps C rpb")
+GATE_BWD = [GateBwd(f"nch{nch(C)}-C{C}-rps{rps}-rpb64", 128, rps, C, 64) for C in (256, 1024, 2048) for rps in (64, 77)]

@@ -418,11 +418,13 @@ def test_get_mask_bit_exact(hip, T, ratio):
     assert torch.equal(back, torch.where(m, torch.zeros_like(x), x))
 
 
-@pytest.mark.parametrize("B,S,E,d", [(4, 64, 8, 256), (3, 256, 8, 128), (2, 64, 4, 128)])
-def test_moe_routing_combine(hip, B, S, E, d):
+@pytest.mark.parametrize("B,S,E,d,cap", [(4, 64, 8, 256, 2), (3, 256, 8, 128, 2), (2, 64, 4, 128, 2),
+                                         (2, 1024, 8, 128, 1)],      # res-512 finetune: S = 1024, k = S / E = 128 (no mask)
+                         ids=["4-64-8-256", "3-256-8-128", "2-64-4-128", "2-1024-8-128-k128"])
+def test_moe_routing_combine(hip, B, S, E, d, cap):
     torch.manual_seed(S + E)
     L, st = hip.lib(), hip.stream_ptr()
-    k = int(2.0 * S / E)
+    k = int(cap * S / E)
     ld = 8
     M, Bk = B * S, B * k
     logits = torch.zeros(M, ld, device=DEV)
@@ -440,6 +442,14 @@ def test_moe_routing_combine(hip, B, S, E, d):
     # same SETS (ordering inside top-k for exact ties may differ; values are tie-free here) and same order
     got_idx = rowidx.view(E, B, k).permute(1, 0, 2).cpu().long() - (torch.arange(B) * S).view(B, 1, 1)
     assert torch.equal(got_idx, m.cpu())
+    # exact against the kernel's own probabilities: the k highest per (sample, expert), descending, ties to the lower token
+    pk = probs[:, :E].view(B, S, E).permute(0, 2, 1).cpu()
+    order = torch.sort(-pk, dim=-1, stable=True).indices[..., :k]
+    assert torch.equal(got_idx, order)
+    assert torch.equal(gval.view(E, B, k).permute(1, 0, 2).cpu(), torch.gather(pk, -1, order))
+    want_slot = torch.full((B, E, S), -1, dtype=torch.int64)
+    want_slot.scatter_(-1, order, torch.arange(k).expand(B, E, k).contiguous())
+    assert torch.equal(slot.cpu().long().view(B, S, E).permute(0, 2, 1), want_slot)
     close(gval.view(E, B, k).permute(1, 0, 2), g, rel=1e-5, what="gval")
     # combine forward
     h2 = bf(torch.randn(E, Bk, d, device=DEV))
