@@ -214,6 +214,36 @@ int md_qkln_bwd_hm(const void* dy, int64_t dy_seg_stride, const void* y, int64_t
                    int64_t dseg_stride, int64_t rows, int64_t width, int32_t nseg, int64_t S, int32_t hd, const float* rstd,
                    hipStream_t stream);
 
+/* Deterministic forms (added under ABI 6: the change only ADDS symbols, every existing entry point and struct is untouched, so
+ * MD_ABI_VERSION stays 6 and callers built against the earlier header keep working).
+ *
+ * md_ln_bwd, md_gate_bwd and md_colsum publish their per-column sums with fp32 atomics: the order of the adds, and with it the
+ * last bits of the result, changes from run to run.  The _det entry points compute the same sums with NO float atomic and one
+ * writer per address: every workgroup of the row kernel stores its partial sums into its own slice of a caller-supplied fp32
+ * workspace, and a finish kernel adds the slices of one output element in ascending slice order and adds the total to the
+ * output (+=, as the atomic forms do).  Same binary + same GPU model + same arguments => bit-identical results; another
+ * rows_per_block is another summation order.  Row outputs (dx, dbr) are bit-identical to the atomic forms.
+ *
+ * The workspace needs NO initialisation (every slice element the finish reads is written by the row kernel of the same call) and
+ * may be reused by the next call on the same stream.  md_det_ws_floats answers its size in floats (0 = none needed, ws may be
+ * NULL); a launcher given ws == NULL where one is needed, or ws_floats below that size, returns -1 and launches nothing.
+ *   MD_DET_GATE_BWD  chunks = ceil(rows_per_sample / rows_per_block), samples = rows / rows_per_sample:
+ *                    samples * chunks * C  ([samples][chunks][C]); 0 when chunks == 1 (the workgroup is the only writer of its row)
+ *   MD_DET_LN_BWD    2 * samples * chunks * C  ([2][samples][chunks][C]: dS, dshift; 0 when chunks == 1)
+ *                    + groups * C, groups = ceil(samples / 16)  (weight-gradient partials of 16 samples each, added in ascending
+ *                    order by a third kernel; 0 when groups == 1).  rows_per_sample <= 0 means one sample, as in md_ln_args.
+ *   MD_DET_COLSUM    blocks * C, blocks = ceil(rows / r) with the library's own rows-per-workgroup rule r(rows, C) -- the one md_colsum
+ *                    uses; 0 when blocks == 1.  rows_per_sample and rows_per_block are ignored.
+ * md_ln_bwd_det: dw[c] += sum_b (1 + scale[b, c]) * dS[b, c] in ascending b within a group of 16, groups in ascending order. */
+enum md_det_kind { MD_DET_GATE_BWD = 0, MD_DET_LN_BWD = 1, MD_DET_COLSUM = 2 };
+int md_det_ws_floats(int32_t kind, int64_t rows, int64_t rows_per_sample, int64_t rows_per_block, int64_t C, int64_t* out_floats);
+int md_ln_bwd_det(const md_ln_args* a, const md_ln_bwd_args* b, float* ws, int64_t ws_floats, hipStream_t stream);
+int md_gate_bwd_det(const void* dx, const void* br, const void* gate, int64_t ldgate, void* dbr, float* dgate, int64_t lddg,
+                    int64_t rows, int64_t C, int64_t rows_per_sample, int64_t rows_per_block, float* ws, int64_t ws_floats,
+                    hipStream_t stream);
+int md_colsum_det(const void* x, int32_t x_is_f32, int64_t ld, float* out, int64_t rows, int64_t C, float* ws, int64_t ws_floats,
+                  hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------- attention */
 /* softmax(scale * Q K^T) V per (batch, head), non-causal, no mask.  Row r of head h of batch b of X lives at
  * X + b*sX + r*ldX + h*hsX (bf16; hsX = hd unless set), so packed qkv / kv projection buffers are addressed in place.

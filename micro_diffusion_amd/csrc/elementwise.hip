@@ -1,6 +1,12 @@
 // HBM-bound elementwise / column-reduction kernels of the MicroDiT path (16-byte accesses, grid-stride loops).
 //   SwiGLU (dit.py:88-89), adaLN-Zero gate backward (dit.py:236,238), GELU on the condition vector (dit.py:223),
 //   bias-gradient column sums, token mean pooling (dit.py:484), dtype casts (model.py:132-139).
+//
+//  md_swiglu_fwd / md_swiglu_bwd, md_gate_bwd, md_act_fwd / md_act_bwd, md_colsum, md_cast_f32_bf16(_clear), md_cast_rows_bf16,
+//  md_mean_tokens(_bwd), md_add_bf16, md_fill_zero
+//  md_gate_bwd_det, md_colsum_det   the two column reductions WITHOUT float atomics: per-workgroup partial sums go to a workspace
+//                                   slice each (gate_bwd_kernel<N, true>, colsum_kernel<T, true>), ew_det_sum_kernel adds the slices
+//                                   in a fixed order; md_det_ws_floats sizes the workspace of these and of md_ln_bwd_det
 #include "md_common.h"
 #include "../../include/microdit_hip.h"
 
@@ -124,7 +130,9 @@ inline int64_t swiglu_rows_per_block(int64_t M, int64_t f) {
 }
 
 // dbr = gate[b] * dx ; dgate[b, c] += sum_t dx * br.   grid = (row chunks per sample, samples), wave per row.
-template <int NCH>
+// DET (md_gate_bwd_det): no atomics.  With several chunks per sample `dgate` is the workspace [samples][chunks][C] and every
+// workgroup STORES its sums into its own slice; with one chunk the workgroup is the only writer of dgate[b, :] and adds in place.
+template <int NCH, bool DET = false>
 __global__ __launch_bounds__(256) void gate_bwd_kernel(const bf16* dx, const bf16* br, const bf16* gate, int64_t ldgate,
                                                        bf16* dbr, float* dgate, int64_t lddg, int64_t C, int64_t rps,
                                                        int64_t rows_per_block) {
@@ -169,8 +177,17 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const bf16* dx, const bf1
 #pragma unroll
         for (int e = 0; e < 8; ++e) red[wave][lane * 8 + j * 512 + e] = acc[j][e];
     __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256)
-        unsafeAtomicAdd(dgate + smp * lddg + c, red[0][c] + red[1][c] + red[2][c] + red[3][c]);
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const float v = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+        if (!DET) unsafeAtomicAdd(dgate + smp * lddg + c, v);
+        else if (gridDim.x == 1) dgate[smp * lddg + c] += v;
+        else dgate[(smp * gridDim.x + blockIdx.x) * C + c] = v;
+    }
+}
+
+// stage two of the deterministic reductions of this file (md_common.h: det_slice_sum)
+__global__ __launch_bounds__(256) void ew_det_sum_kernel(const float* ws, int64_t nslices, float* out, int64_t ldo, int64_t C) {
+    det_slice_sum(ws, nslices, out, ldo, C);
 }
 
 __global__ __launch_bounds__(256) void act_fwd_kernel(const bf16* x, bf16* y, int64_t n8, int act) {
@@ -198,7 +215,9 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* dy, const bf1
 }
 
 // out[c] += sum_rows x[row, c]; block = 256 columns x `rows_per_block` rows.
-template <typename T>
+// DET (md_colsum_det): with several row blocks `out` is the workspace [row blocks][C], one stored slice per workgroup; with one
+// row block the thread is the only writer of out[c] and adds in place.
+template <typename T, bool DET = false>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* x, int64_t ld, float* out, int64_t rows, int64_t C,
                                                      int64_t rows_per_block) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -208,7 +227,21 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* x, int64_t ld, flo
     if (r1 > rows) r1 = rows;
     float s = 0.f;
     for (int64_t r = r0; r < r1; ++r) s += (float)x[r * ld + c];
-    unsafeAtomicAdd(out + c, s);
+    if (!DET) unsafeAtomicAdd(out + c, s);
+    else if (gridDim.y == 1) out[c] += s;
+    else out[(int64_t)blockIdx.y * C + c] = s;
+}
+
+// rows per workgroup of colsum_kernel; short inputs (adaLN bias grads: 256 rows) get smaller chunks to fill the chip.  Shared by
+// md_colsum, md_colsum_det and md_det_ws_floats: the deterministic sum is reproducible for one value of this rule only.
+inline int64_t colsum_rows_per_block(int64_t rows, int64_t C) {
+    int64_t rpb = 128;
+    while (rpb > 8 && ((C + 255) / 256) * ((rows + rpb - 1) / rpb) < 512) rpb /= 2;
+    return rpb;
+}
+
+inline bool gate_shape_ok(int64_t rows, int64_t C, int64_t rows_per_sample, int64_t rows_per_block) {
+    return rows > 0 && C > 0 && C % 8 == 0 && C <= 2048 && rows_per_sample > 0 && rows % rows_per_sample == 0 && rows_per_block > 0;
 }
 
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* x, bf16* y, int64_t n8, const float* scale_ptr) {
@@ -354,13 +387,70 @@ extern "C" int md_act_bwd(const float* dy, const void* x, void* dx, int64_t n, i
 
 extern "C" int md_colsum(const void* x, int32_t x_is_f32, int64_t ld, float* out, int64_t rows, int64_t C, hipStream_t st) {
     if (!x || !out || rows <= 0 || C <= 0) return MD_BAD_ARG;
-    int64_t rpb = 128;                       // rows per workgroup; short inputs (adaLN bias grads: 256 rows) get more,
-    while (rpb > 8 && ((C + 255) / 256) * ((rows + rpb - 1) / rpb) < 512) rpb /= 2;   // smaller chunks to fill the chip
+    const int64_t rpb = colsum_rows_per_block(rows, C);
     dim3 grid((unsigned)((C + 255) / 256), (unsigned)((rows + rpb - 1) / rpb));
     if (x_is_f32)
         hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, st, (const float*)x, ld, out, rows, C, rpb);
     else
         hipLaunchKernelGGL(colsum_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)x, ld, out, rows, C, rpb);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_det_ws_floats(int32_t kind, int64_t rows, int64_t rows_per_sample, int64_t rows_per_block, int64_t C,
+                                int64_t* out_floats) {
+    if (!out_floats) return MD_BAD_ARG;
+    if (kind == MD_DET_COLSUM) {
+        if (rows <= 0 || C <= 0) return MD_BAD_ARG;
+        const int64_t rpb = colsum_rows_per_block(rows, C), blocks = (rows + rpb - 1) / rpb;
+        *out_floats = blocks > 1 ? blocks * C : 0;
+        return 0;
+    }
+    if (kind != MD_DET_GATE_BWD && kind != MD_DET_LN_BWD) return MD_BAD_ARG;
+    if (kind == MD_DET_LN_BWD && rows_per_sample <= 0) rows_per_sample = rows;     // md_ln_args.rows_per_sample = 0: one sample
+    if (!gate_shape_ok(rows, C, rows_per_sample, rows_per_block)) return MD_BAD_ARG;
+    const int64_t samples = rows / rows_per_sample, chunks = det_chunks(rows_per_sample, rows_per_block);
+    *out_floats = kind == MD_DET_GATE_BWD ? det_chunk_ws_floats(1, samples, chunks, C) : det_ln_ws_floats(samples, chunks, C);
+    return 0;
+}
+
+extern "C" int md_gate_bwd_det(const void* dx, const void* br, const void* gate, int64_t ldgate, void* dbr, float* dgate,
+                               int64_t lddg, int64_t rows, int64_t C, int64_t rows_per_sample, int64_t rows_per_block, float* ws,
+                               int64_t ws_floats, hipStream_t st) {
+    if (!dx || !br || !gate || !dbr || !dgate || !gate_shape_ok(rows, C, rows_per_sample, rows_per_block) || ldgate % 8)
+        return MD_BAD_ARG;
+    const int64_t samples = rows / rows_per_sample, chunks = det_chunks(rows_per_sample, rows_per_block);
+    const int64_t need = det_chunk_ws_floats(1, samples, chunks, C);
+    if (need > 0 && (!ws || ws_floats < need)) return MD_BAD_ARG;
+    if (chunks > 65535 || samples > 65535) return MD_BAD_ARG;
+    dim3 grid((unsigned)chunks, (unsigned)samples);
+    float* dst = need > 0 ? ws : dgate;
+#define GB(N) hipLaunchKernelGGL((gate_bwd_kernel<N, true>), grid, dim3(256), 0, st, (const bf16*)dx, (const bf16*)br, \
+                                 (const bf16*)gate, ldgate, (bf16*)dbr, dst, lddg, C, rows_per_sample, rows_per_block)
+    if (C <= 512) GB(1); else if (C <= 1024) GB(2); else GB(4);
+#undef GB
+    if (need > 0)
+        hipLaunchKernelGGL(ew_det_sum_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)samples), dim3(256), 0, st, ws, chunks, dgate,
+                           lddg, C);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_colsum_det(const void* x, int32_t x_is_f32, int64_t ld, float* out, int64_t rows, int64_t C, float* ws,
+                             int64_t ws_floats, hipStream_t st) {
+    if (!x || !out || rows <= 0 || C <= 0) return MD_BAD_ARG;
+    const int64_t rpb = colsum_rows_per_block(rows, C), blocks = (rows + rpb - 1) / rpb;
+    const int64_t need = blocks > 1 ? blocks * C : 0;
+    if (need > 0 && (!ws || ws_floats < need)) return MD_BAD_ARG;
+    if (blocks > 65535) return MD_BAD_ARG;
+    dim3 grid((unsigned)((C + 255) / 256), (unsigned)blocks);
+    float* dst = need > 0 ? ws : out;
+    if (x_is_f32)
+        hipLaunchKernelGGL((colsum_kernel<float, true>), grid, dim3(256), 0, st, (const float*)x, ld, dst, rows, C, rpb);
+    else
+        hipLaunchKernelGGL((colsum_kernel<bf16, true>), grid, dim3(256), 0, st, (const bf16*)x, ld, dst, rows, C, rpb);
+    if (need > 0)
+        hipLaunchKernelGGL(ew_det_sum_kernel, dim3((unsigned)((C + 63) / 64), 1), dim3(256), 0, st, ws, blocks, out, (int64_t)0, C);
     MD_LAUNCH_CHECK();
     return 0;
 }

@@ -172,3 +172,42 @@ __device__ __forceinline__ float dsilu_f(float x) {
     float s = fast_rcp(1.f + __expf(-x));
     return s * (1.f + x * (1.f - s));
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Deterministic (atomic-free) column reductions: stage one of md_gate_bwd_det / md_ln_bwd_det / md_colsum_det stores the per-column
+// partial sums of every workgroup into its own slice of a caller-supplied fp32 workspace; det_slice_sum then adds the slices of
+// one output element in a FIXED order.  grid = (column blocks of 64, outer); the four waves of a workgroup take the four
+// contiguous quarters of the slices in ascending order, wave 0 adds the four quarter sums in ascending order: the order is a
+// function of `nslices` alone.  ws [outer][nslices][C]; out[outer * ldo + c] += sum.  One writer per output element.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void det_slice_sum(const float* ws, int64_t nslices, float* out, int64_t ldo, int64_t C) {
+    __shared__ float part[4][64];
+    const int col = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int64_t c = (int64_t)blockIdx.x * 64 + col;
+    const int64_t per = (nslices + 3) / 4;
+    const int64_t k0 = q * per;
+    int64_t k1 = k0 + per;
+    if (k1 > nslices) k1 = nslices;
+    float s = 0.f;
+    if (c < C) {
+        const float* src = ws + (int64_t)blockIdx.y * nslices * C + c;
+        for (int64_t k = k0; k < k1; ++k) s += src[k * C];
+    }
+    part[q][col] = s;
+    __syncthreads();
+    if (q == 0 && c < C) out[(int64_t)blockIdx.y * ldo + c] += ((part[0][col] + part[1][col]) + part[2][col]) + part[3][col];
+}
+
+// Workspace floats of the row-chunked forms (gate_bwd: parts = 1, ln_bwd: parts = 2 for dS and dshift): [parts][samples][chunks][C];
+// with one chunk per sample the workgroup is the only writer of its output row and adds to it directly (no workspace).
+inline int64_t det_chunks(int64_t rows_per_sample, int64_t rows_per_block) { return (rows_per_sample + rows_per_block - 1) / rows_per_block; }
+inline int64_t det_chunk_ws_floats(int64_t parts, int64_t samples, int64_t chunks, int64_t C) {
+    return chunks > 1 ? parts * samples * chunks * C : 0;
+}
+// md_ln_bwd_det: the two chunk regions above, then [groups][C] partial weight gradients of DET_LN_GROUP samples each (none with one group)
+constexpr int64_t DET_LN_GROUP = 16;
+inline int64_t det_ln_groups(int64_t samples) { return (samples + DET_LN_GROUP - 1) / DET_LN_GROUP; }
+inline int64_t det_ln_ws_floats(int64_t samples, int64_t chunks, int64_t C) {
+    const int64_t groups = det_ln_groups(samples);
+    return det_chunk_ws_floats(2, samples, chunks, C) + (groups > 1 ? groups * C : 0);
+}

@@ -3,6 +3,9 @@
 //
 //  md_ln_fwd   y = LN(act(x + pos)) * w ; z = y * (1 + scale[b]) + shift[b]        (w, pos, act, modulate optional)
 //  md_ln_bwd   dx (+)= d/dx ; dS[b] += sum_t dz * xhat ; dshift[b] += sum_t dz ; then (finish) dscale = w * dS, dw += sum_b (1 + scale[b]) * dS
+//  md_ln_bwd_det  the same gradients WITHOUT float atomics: ln_bwd_kernel<N, G, true> stores each workgroup's column sums into its
+//              own workspace slice, ln_det_finish_kernel adds the slices in a fixed order (one owner per (sample, column)) and
+//              forms dscale and per-group weight-gradient partials, ln_det_sum_kernel adds those in a fixed order
 //  md_qkln_*   non-parametric LN over the whole q (or k) hidden width, in place (all heads concatenated)
 //
 // Reference: create_norm / nn.LayerNorm(bias=False) (utils.py:71-78) under Composer's low-precision LayerNorm
@@ -172,7 +175,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(md_ln_args p, int64_t rows_
 // are reduced in registers + LDS and published with one atomicAdd per column (few workgroups per sample -> little
 // contention).  dscale = w * dS and dw = sum_b (1 + scale_b) * dS are finished by ln_bwd_finish_kernel: summing dw with
 // atomics straight from here serialised ~2000 adds per address and tripled the kernel time.
-template <int NCH, bool GENERIC>
+// DET (md_ln_bwd_det): no atomics.  With several chunks per sample b.dscale / b.dshift point at the workspace regions
+// [samples][chunks][C] and every workgroup STORES its sums into its own slice (ln_det_finish_kernel adds them up); with one chunk
+// the workgroup is the only writer of its sample's row and adds in place.
+template <int NCH, bool GENERIC, bool DET = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(md_ln_args p, md_ln_bwd_args b) {
     __shared__ float red[4][64 * 8 * NCH];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -270,8 +276,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(md_ln_args p, md_ln_bwd_arg
         }
     }
     if (!want_cols) return;
-    float* dS = b.dscale ? reinterpret_cast<float*>(b.dscale) + smp * b.ldg : nullptr;
-    float* dshift = b.dshift ? reinterpret_cast<float*>(b.dshift) + smp * b.ldg : nullptr;
+    const bool sliced = DET && gridDim.x > 1;
+    const int64_t off = sliced ? (smp * gridDim.x + blockIdx.x) * p.C : smp * b.ldg;
+    float* dS = b.dscale ? reinterpret_cast<float*>(b.dscale) + off : nullptr;
+    float* dshift = b.dshift ? reinterpret_cast<float*>(b.dshift) + off : nullptr;
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
         float* dst = pass == 0 ? dS : dshift;
@@ -282,7 +290,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(md_ln_args p, md_ln_bwd_arg
 #pragma unroll
             for (int e = 0; e < 8; ++e) red[wave][lane * 8 + j * 512 + e] = pass == 0 ? accS[j][e] : accD[j][e];
         __syncthreads();
-        for (int c = threadIdx.x; c < p.C; c += 256) unsafeAtomicAdd(dst + c, red[0][c] + red[1][c] + red[2][c] + red[3][c]);
+        for (int c = threadIdx.x; c < p.C; c += 256) {
+            const float v = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+            if (!DET) unsafeAtomicAdd(dst + c, v);
+            else if (sliced) dst[c] = v;
+            else dst[c] += v;
+        }
     }
 }
 
@@ -308,6 +321,49 @@ __global__ __launch_bounds__(256) void ln_bwd_finish_kernel(float* dS, int64_t l
         if (to_dscale && b0 + i < B) dS[(b0 + i) * ldg + c] = sv[i] * wc;
     }
     if (dw) unsafeAtomicAdd(dw + c, acc);
+}
+
+// Deterministic finish (md_ln_bwd_det).  grid = (column blocks of 256, groups of DET_LN_GROUP samples); thread = one column, walking
+// the samples of its group in ascending order -- the only writer of every address it touches:
+//   dS[b, c] += sum_chunk wsS[b][chunk][c]     dshift[b, c] += sum_chunk wsH[b][chunk][c]     (ascending chunk; wsS / wsH = NULL: the
+//                                                                                               row kernel already added in place)
+//   acc += (1 + scale[b, c]) * dS[b, c] ;  dS[b, c] *= w[c] when to_dscale
+// and then dw[c] += acc (one group) or wsW[group][c] = acc (ln_det_sum_kernel adds the groups in ascending order).
+__global__ __launch_bounds__(256) void ln_det_finish_kernel(const float* wsS, const float* wsH, int64_t chunks, float* dS, float* dshift,
+                                                            int64_t ldg, const float* w, const bf16* scale, int64_t ldmod, float* dw,
+                                                            float* wsW, int64_t B, int64_t C, int to_dscale) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const int64_t b0 = (int64_t)blockIdx.y * DET_LN_GROUP;
+    int64_t b1 = b0 + DET_LN_GROUP;
+    if (b1 > B) b1 = B;
+    const float wc = w ? w[c] : 1.f;
+    float acc = 0.f;
+    for (int64_t b = b0; b < b1; ++b) {
+        if (dshift && wsH) {
+            const float* src = wsH + b * chunks * C + c;
+            float t = 0.f;
+            for (int64_t k = 0; k < chunks; ++k) t += src[k * C];
+            dshift[b * ldg + c] += t;
+        }
+        if (!dS) continue;
+        float v = dS[b * ldg + c];
+        if (wsS) {
+            const float* src = wsS + b * chunks * C + c;
+            float t = 0.f;
+            for (int64_t k = 0; k < chunks; ++k) t += src[k * C];
+            v += t;
+        }
+        acc += (scale ? 1.f + bf2f(scale[b * ldmod + c]) : 1.f) * v;
+        if (wsS || to_dscale) dS[b * ldg + c] = to_dscale ? v * wc : v;
+    }
+    if (!dS) return;
+    if (wsW) wsW[(int64_t)blockIdx.y * C + c] = acc;
+    else if (dw) dw[c] += acc;
+}
+
+__global__ __launch_bounds__(256) void ln_det_sum_kernel(const float* ws, int64_t nslices, float* out, int64_t ldo, int64_t C) {
+    det_slice_sum(ws, nslices, out, ldo, C);
 }
 
 template <int NCH>
@@ -600,6 +656,47 @@ extern "C" int md_ln_bwd(const md_ln_args* a, const md_ln_bwd_args* b, hipStream
                            reinterpret_cast<float*>(b->dscale), b->ldg, reinterpret_cast<const float*>(a->w),
                            reinterpret_cast<const bf16*>(a->scale), a->ldmod, reinterpret_cast<float*>(b->dw), nsmp, a->C,
                            b->dscale_is_output);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_ln_bwd_det(const md_ln_args* a, const md_ln_bwd_args* b, float* ws, int64_t ws_floats, hipStream_t stream) {
+    if (!ln_args_ok(a) || !b || !b->dz || !a->mean || !a->rstd || b->lddz % 8) return MD_BAD_ARG;
+    if (b->dx && b->lddx % 8) return MD_BAD_ARG;
+    if (b->rows_per_block <= 0) return MD_BAD_ARG;
+    if (b->dw && !b->dscale) return MD_BAD_ARG;
+    const int64_t rps = a->rows_per_sample > 0 ? a->rows_per_sample : a->rows;
+    if (a->rows % rps) return MD_BAD_ARG;
+    const int64_t nsmp = a->rows / rps, chunks = det_chunks(rps, b->rows_per_block), groups = det_ln_groups(nsmp);
+    if (chunks > 65535 || nsmp > 65535) return MD_BAD_ARG;
+    const bool want_cols = b->dscale || b->dshift;
+    const int64_t region = det_chunk_ws_floats(1, nsmp, chunks, a->C), need = det_ln_ws_floats(nsmp, chunks, a->C);
+    if (want_cols && need > 0 && (!ws || ws_floats < need)) return MD_BAD_ARG;
+    float* wsS = region > 0 && b->dscale ? ws : nullptr;                 // [samples][chunks][C] each
+    float* wsH = region > 0 && b->dshift ? ws + region : nullptr;
+    float* wsW = groups > 1 && b->dw ? ws + 2 * region : nullptr;        // [groups][C]
+    md_ln_bwd_args k = *b;
+    if (region > 0) {
+        k.dscale = wsS;
+        k.dshift = wsH;
+    }
+    dim3 grid((unsigned)chunks, (unsigned)nsmp, 1);
+    const bool generic = a->act != MD_ACT_NONE || a->pos != nullptr;
+#define LNB(N, G) hipLaunchKernelGGL((ln_bwd_kernel<N, G, true>), grid, dim3(256), 0, stream, *a, k)
+    if (generic) {
+        if (a->C <= 512) LNB(1, true); else if (a->C <= 1024) LNB(2, true); else LNB(4, true);
+    } else {
+        if (a->C <= 512) LNB(1, false); else if (a->C <= 1024) LNB(2, false); else LNB(4, false);
+    }
+#undef LNB
+    if ((want_cols && region > 0) || (b->dscale && (b->dw || b->dscale_is_output)))
+        hipLaunchKernelGGL(ln_det_finish_kernel, dim3((unsigned)((a->C + 255) / 256), (unsigned)groups), dim3(256), 0, stream, wsS, wsH,
+                           chunks, reinterpret_cast<float*>(b->dscale), reinterpret_cast<float*>(b->dshift), b->ldg,
+                           reinterpret_cast<const float*>(a->w), reinterpret_cast<const bf16*>(a->scale), a->ldmod,
+                           reinterpret_cast<float*>(b->dw), wsW, nsmp, a->C, b->dscale_is_output);
+    if (wsW)
+        hipLaunchKernelGGL(ln_det_sum_kernel, dim3((unsigned)((a->C + 63) / 64), 1), dim3(256), 0, stream, wsW, groups,
+                           reinterpret_cast<float*>(b->dw), (int64_t)0, a->C);
     MD_LAUNCH_CHECK();
     return 0;
 }

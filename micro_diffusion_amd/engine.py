@@ -116,6 +116,12 @@ class DiTEngine:
         # profiles/r6_head_major_qk.txt) -- v / o / dO / dv stay in packed rows unless the GEMM epilogues re-lay them.  Off by default
         # (it costs 2/3 of a qkv buffer per block of tape); MD_QK_HEAD_MAJOR=1 or this attribute turns it on.
         self.qk_head_major = os.environ.get("MD_QK_HEAD_MAJOR", "0") == "1"
+        # Deterministic mode (opt-in: MD_DETERMINISTIC=1, or set this before the first step): the four float-atomic column reductions of
+        # the training path (md_ln_bwd: dS / dshift and dw, md_gate_bwd: dgate, md_colsum: bias gradients) go through their _det entry
+        # points -- per-workgroup partial sums in a workspace, added in a fixed order -- so two runs of one step on one GPU give
+        # bit-identical gradients.  Off: the launch sequence is unchanged.  (DESIGN.md "Deterministic mode")
+        self.deterministic = os.environ.get("MD_DETERMINISTIC", "0") == "1"
+        self._det_ws_floats = {}           # (kind, rows, rows per sample, rows per block, C) -> md_det_ws_floats
         self.gemm_log = None               # tests: list that receives (variant actually requested, M, N, K, batch) per launch
         self.before_segment = None         # data parallelism: callable(bucket key) run before the first kernel that reads the bf16
         #                                    weights of a bucket ("rest", block names, "final_layer"): waits for their all-gather
@@ -209,6 +215,37 @@ class DiTEngine:
         e1.record()
         kp.setdefault(name, []).append((e0, e1, float(nbytes)))
 
+    def _det_ws(self, kind, rows, rps, rpb, C):
+        """(pointer, floats) of the workspace a deterministic reduction of this shape needs ((None, 0): none).  The size is asked once
+        per shape; the buffer comes from the current arena (or the allocator) and is dead when the launch has run."""
+        key = (kind, rows, rps, rpb, C)
+        n = self._det_ws_floats.get(key)
+        if n is None:
+            out = ctypes.c_int64(0)
+            hip.check(self.L.md_det_ws_floats(kind, rows, rps, rpb, C, byref(out)), "md_det_ws_floats")
+            n = self._det_ws_floats[key] = int(out.value)
+        if n == 0:
+            return None, 0
+        return self.empty(n, dtype=F32).data_ptr(), n
+
+    def _colsum(self, src_ptr, is_f32, ld, out_ptr, rows, C):
+        """out[c] += column sums (bias gradients)."""
+        nbytes = (4.0 if is_f32 else 2.0) * rows * C
+        if not self.deterministic:
+            return self._prof("colsum", nbytes, lambda: hip.check(self.L.md_colsum(src_ptr, is_f32, ld, out_ptr, rows, C, self._st()), "colsum"))
+        ws, n = self._det_ws(hip.DET_COLSUM, rows, 0, 0, C)
+        self._prof("colsum", nbytes,
+                   lambda: hip.check(self.L.md_colsum_det(src_ptr, is_f32, ld, out_ptr, rows, C, ws, n, self._st()), "colsum_det"))
+
+    def _gate_bwd(self, dx, br, gate_ptr, ldgate, dbr, dgate_ptr, lddg, M, d, S, rpb):
+        """adaLN-Zero gate backward: dbr = gate * dx, dgate += per-sample column sums of dx * br."""
+        if not self.deterministic:
+            return self._prof("gate_bwd", 6.0 * M * d, lambda: hip.check(self.L.md_gate_bwd(
+                dx.data_ptr(), br.data_ptr(), gate_ptr, ldgate, dbr.data_ptr(), dgate_ptr, lddg, M, d, S, rpb, self._st()), "gate_bwd"))
+        ws, n = self._det_ws(hip.DET_GATE_BWD, M, S, rpb, d)
+        self._prof("gate_bwd", 6.0 * M * d, lambda: hip.check(self.L.md_gate_bwd_det(
+            dx.data_ptr(), br.data_ptr(), gate_ptr, ldgate, dbr.data_ptr(), dgate_ptr, lddg, M, d, S, rpb, ws, n, self._st()), "gate_bwd_det"))
+
     def _qkln_fwd(self, ptr, rows, ld, off, width, rstd_ptr, nseg=1):
         """nseg = 2: the q and the k half (adjacent, `width` apart) of a packed qkv row in one launch; rstd [nseg][rows]."""
         self._prof("qk_layernorm", 4.0 * rows * width * nseg, lambda: hip.check(
@@ -240,6 +277,9 @@ class DiTEngine:
         may_refuse = kw.pop("_try", False)        # True: a launch the library may refuse (NOT_ELIGIBLE, nothing launched) -> returns False
         for k, v in kw.items():
             setattr(a, k, v)
+        if self.deterministic and a.mode == hip.EPI_ATOMIC_F32 and a.ksplit > 1:
+            raise RuntimeError("deterministic mode: a split-K GEMM with the fp32-atomic epilogue sums in an order that changes from run "
+                               "to run; use the workspace slices + md_splitk_reduce (gemm_f32_acc)")
         prof = self.gemm_profile
         if prof is not None:      # per-launch HIP events on the launch stream (bench.py roofline leg)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -395,8 +435,8 @@ class DiTEngine:
         gb = self.G.get(wname + ".bias")
         if gb is not None:
             src = dy if bias_from is None else bias_from
-            hip.check(self.L.md_colsum(src.data_ptr() + (0 if bias_from is not None else 2 * dyoff),
-                                       1 if src.dtype == F32 else 0, lddy or N, gb.data_ptr(), M, N, self._st()), "colsum")
+            self._colsum(src.data_ptr() + (0 if bias_from is not None else 2 * dyoff), 1 if src.dtype == F32 else 0, lddy or N,
+                         gb.data_ptr(), M, N)
         grp = self._wgroup
         if defer and grp is not None and M % 128 == 0 and K % 8 == 0 and (not grp or grp[0]["tokens"] == M) and len(grp) < hip.GEMM_MAX_PROBLEMS:
             grp.append(dict(tokens=M, A=dy.data_ptr() + 2 * dyoff, lda=lddy or N, B=x.data_ptr() + 2 * xoff, ldb=ldx or K, M=N, N=K,
@@ -507,6 +547,11 @@ class DiTEngine:
             dscale, ldg = scratch.data_ptr(), a.C
         b = hip.LnBwdArgs(dz.data_ptr(), _p(dx), dscale, dshift, _p(self.G[wname + ".weight"]) if wname else None,
                           a.C, a.C, ldg, rpb, 1 if accumulate else 0, is_out)
+        if self.deterministic:
+            ws, n = self._det_ws(hip.DET_LN_BWD, a.rows, rps, rpb, a.C)
+            self._prof("layernorm", (8.0 if accumulate else 6.0) * a.rows * a.C,
+                       lambda: hip.check(self.L.md_ln_bwd_det(byref(a), byref(b), ws, n, self._st()), "md_ln_bwd_det"))
+            return
         self._prof("layernorm", (8.0 if accumulate else 6.0) * a.rows * a.C,
                    lambda: hip.check(self.L.md_ln_bwd(byref(a), byref(b), self._st()), "md_ln_bwd"))
 
@@ -721,8 +766,7 @@ class DiTEngine:
         rpb = self._rows_per_block(M, S)
         # ---------------- feed-forward branch
         dbr3 = self.empty(M, d)
-        self._prof("gate_bwd", 6.0 * M * d, lambda: hip.check(L.md_gate_bwd(dx.data_ptr(), t.br3.data_ptr(), mp + 2 * 5 * d, ldm, dbr3.data_ptr(),
-                                                                          dmp + 4 * 5 * d, 6 * d, M, d, S, rpb, st), "gate_bwd"))
+        self._gate_bwd(dx, t.br3, mp + 2 * 5 * d, ldm, dbr3, dmp + 4 * 5 * d, 6 * d, M, d, S, rpb)
         dxm3 = self.empty(M, d)
         if not bp.moe:
             self.lin_wgrad(dbr3, t.a, n + ".mlp.w3", M, d, f, defer=True)
@@ -816,8 +860,7 @@ class DiTEngine:
         self.ln_bwd(a2, dxn2, dx, accumulate=True, wname=n + ".norm2")
         # ---------------- self-attention branch
         dbr1 = self.empty(M, d)
-        self._prof("gate_bwd", 6.0 * M * d, lambda: hip.check(L.md_gate_bwd(dx.data_ptr(), t.br1.data_ptr(), mp + 2 * 2 * d, ldm, dbr1.data_ptr(),
-                                                                          dmp + 4 * 2 * d, 6 * d, M, d, S, rpb, st), "gate_bwd"))
+        self._gate_bwd(dx, t.br1, mp + 2 * 2 * d, ldm, dbr1, dmp + 4 * 2 * d, 6 * d, M, d, S, rpb)
         self.lin_wgrad(dbr1, t.sa.o, n + ".attn.proj", M, d, h, defer=True)
         do = self.empty(M, h)
         self.lin_dgrad(dbr1, n + ".attn.proj", do, M, d, h)
@@ -1248,7 +1291,7 @@ class DiTEngine:
             dtok_e = dx
         self.gemm_f32_acc(out_ptr=self.G["x_embedder.proj.weight"].data_ptr(), M=D, N=pv, K=B * T, ldo=pv,
                           A=dtok_e.data_ptr(), B=tp.patches.data_ptr(), lda=D, ldb=pv, a_kcontig=0, b_kcontig=0)
-        hip.check(L.md_colsum(dtok_e.data_ptr(), 0, D, self.G["x_embedder.proj.bias"].data_ptr(), B * T, D, st), "colsum")
+        self._colsum(dtok_e.data_ptr(), 0, D, self.G["x_embedder.proj.bias"].data_ptr(), B * T, D)
         # ---- condition vector: c = temb + pooled ; gc = gelu(c)
         if grp_b is not None:
             self._adaln_dgrad_grouped(grp_b, B, 6 * self.backbone[0].dim, dgc)

@@ -22,6 +22,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-
 # enums (mirror include/microdit_hip.h)
 ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU = 0, 1, 2, 3
 EPI_STORE_BF16, EPI_RESIDUAL, EPI_STORE_F32, EPI_ACCUM_F32, EPI_ATOMIC_F32, EPI_DACT, EPI_SWIGLU_BWD = 0, 1, 2, 3, 4, 5, 6
+DET_GATE_BWD, DET_LN_BWD, DET_COLSUM = 0, 1, 2      # md_det_kind
 GEMM_AUTO, GEMM_REG128, GEMM_DMA128, GEMM_PACED256, GEMM_PP256, GEMM_W4 = 0, 1, 2, 3, 4, 5
 GEMM_VARIANT_NAMES = {"auto": 0, "reg128": 1, "dma128": 2, "paced256": 3, "pp256": 4, "w4": 5}
 # md_attn_args.bwd_split: backward kernel selector (0 = the library's rule; the others force a kernel: tests, A/B runs)
@@ -211,6 +212,11 @@ _sig("md_sumsq_finish", P, I64, P, P)
 _sig("md_checksum_u16", P, I64, P, P)
 _sig("md_adamw_step", POINTER(AdamWArgs), P)
 _sig("md_adamw_step_ranges", POINTER(AdamWArgs), P, P, I32, P)
+# deterministic (atomic-free) forms of the three column reductions; md_det_ws_floats sizes their workspace
+_sig("md_det_ws_floats", I32, I64, I64, I64, I64, POINTER(c_int64))
+_sig("md_ln_bwd_det", POINTER(LnArgs), POINTER(LnBwdArgs), P, I64, P)
+_sig("md_gate_bwd_det", P, P, P, I64, P, P, I64, I64, I64, I64, I64, P, I64, P)
+_sig("md_colsum_det", P, I32, I64, P, I64, I64, P, I64, P)
 
 
 def exported_symbols():

@@ -408,7 +408,8 @@ class GradSync:
         # (another fp32 summation order): a LIVE completion poll therefore makes a data-parallel run not bit-reproducible from run
         # to run (replicas stay identical: gradients are reduced).  MD_DP_DETERMINISTIC=1 answers from host state instead (issued
         # and not yet consumed): reproducible, the grids give up their CUs for longer.
-        self.deterministic = os.environ.get("MD_DP_DETERMINISTIC", "0") == "1"
+        # MD_DETERMINISTIC=1 (the engine's deterministic mode, DiTEngine.deterministic) implies it; the Trainer also copies the engine's switch.
+        self.deterministic = os.environ.get("MD_DP_DETERMINISTIC", "0") == "1" or os.environ.get("MD_DETERMINISTIC", "0") == "1"
         self.store_bf16 = os.environ.get("MD_DP_STORE_BF16", "1") != "0"    # one-microbatch steps: begin_backward() (A/B: 0 = off)
         self.last_stored = 0
         self.active = False
@@ -692,6 +693,8 @@ class Trainer:
                              transport=transport)
         optimizer.ensure_norm_slots(len(self.sync.bucket_list))     # one slot per bucket: the sharded norm has no other source
         self.sync.norm_partials = optimizer.partials
+        if getattr(model.dit.engine, "deterministic", False):
+            self.sync.deterministic = True
         self.world = self.sync.world
         self.sharded = self.sync.enabled and self.sync.mode == "sharded"
         self.stale_foreign_chunks = False    # sharded: fp32 masters / moments of the other ranks' chunks are out of date
