@@ -389,6 +389,44 @@ int md_adamw_step(const md_adamw_args* a, hipStream_t stream);
 #define MD_ADAMW_MAX_RANGES 64
 int md_adamw_step_ranges(const md_adamw_args* a, const int64_t* flat_off, const int64_t* count, int32_t n_ranges, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------- training health */
+/* (Added under ABI 6: new symbols only, no existing entry point or struct changes.)
+ *
+ * Per-tensor statistics of a flat buffer -- the gradient norms composer.callbacks.OptimizerMonitor logs (the stage configs'
+ * optimizer_monitor), plus max |x| and a non-finite count -- as a segmented two-stage reduction shaped like md_sumsq /
+ * md_sumsq_finish.  The caller cuts every tensor into WORK ITEMS of 1 <= count <= MD_STATS_ITEM_MAX elements at src_off (in
+ * elements of x, src_off % 8 == 0 so that 16-byte loads are legal for fp32 and bf16; count is arbitrary, the last partial vector
+ * is read element by element and nothing past it is touched), sorted by tensor; item_begin[n_tensors + 1] gives each tensor's run
+ * of items (empty runs allowed: 0 / 0 / 0).  items and item_begin are DEVICE arrays.
+ *   md_tensor_stats_partial  one workgroup per item: part_sumsq / part_absmax / part_nonfinite [item].  Several calls may fill
+ *                            disjoint slices of one partial array (pass offset pointers): e.g. the packed chunk buffer and the
+ *                            small region of the sharded exchange.  x must be 16-byte aligned.
+ *   md_tensor_stats_finish   one wave per tensor adds its items' partials in a fixed order: sumsq / absmax / nonfinite [tensor].
+ * A non-finite element (NaN, +-Inf) is counted in nonfinite and EXCLUDED from sumsq and absmax.  fp32 accumulation, no atomics:
+ * two calls on the same data and table give bit-identical results. */
+#define MD_STATS_ITEM_MAX 65536
+typedef struct md_stats_item {
+    int64_t src_off; /* first element of the piece inside x */
+    int32_t count;   /* 1 .. MD_STATS_ITEM_MAX */
+    int32_t tensor;  /* row of the result table */
+} md_stats_item;
+int md_tensor_stats_partial(const void* x, int32_t x_is_bf16, const md_stats_item* items, int64_t n_items, float* part_sumsq,
+                            float* part_absmax, int32_t* part_nonfinite, hipStream_t stream);
+int md_tensor_stats_finish(const float* part_sumsq, const float* part_absmax, const int32_t* part_nonfinite,
+                           const int32_t* item_begin, int32_t n_tensors, float* sumsq, float* absmax, int32_t* nonfinite,
+                           hipStream_t stream);
+/* Device-side non-finite step guard (micro_diffusion.models.callbacks.NaNCatcher without a host sync, and BEFORE the update
+ * reaches the weights).  md_step_guard (one thread, plain stores): state[0] = isfinite(*sumsq) ? 1 : 0 -- the step's go flag --
+ * and state[1] += 1 when it is not -- the running count of skipped steps; state is int32 [4] on the device, [2] and [3] reserved.
+ * The _guarded forms are md_adamw_step / md_adamw_step_ranges with that flag as one more kernel argument (guard == NULL: exactly
+ * the unguarded pass).  With *guard == 0 the pass leaves p, m, v (and ema in ema_mode 2) untouched bit for bit, and still zeroes
+ * g when zero_grad, still writes shadow = bf16(p) (the sharded all-gather sends that buffer) and in ema_mode 1 still copies p
+ * into ema (the host flips to mode 2 after that step regardless). */
+int md_step_guard(const float* sumsq, int32_t* state, hipStream_t stream);
+int md_adamw_step_guarded(const md_adamw_args* a, const int32_t* guard, hipStream_t stream);
+int md_adamw_step_ranges_guarded(const md_adamw_args* a, const int64_t* flat_off, const int64_t* count, int32_t n_ranges,
+                                 const int32_t* guard, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

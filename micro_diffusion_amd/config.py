@@ -11,7 +11,9 @@ from typing import Any, Dict, List
 import yaml
 
 # reference `_target_` -> native implementation ("module:attr"); None = accepted and ignored (host-side observability
-# that has no counterpart on the hot path: loggers / monitors; see DESIGN.md "out of scope").
+# that has no counterpart on the hot path: loggers / monitors; see DESIGN.md "out of scope").  Two of the ignored callbacks are
+# honoured by train.py through switches instead of objects: OptimizerMonitor -> misc.optimizer_monitor_interval
+# (names_target below tells whether the config lists it), NaNCatcher -> the per-step loss check or misc.skip_nonfinite_steps.
 TARGETS = {
     "micro_diffusion.models.model.create_latent_diffusion": "micro_diffusion_amd.model:create_latent_diffusion",
     "torch.optim.AdamW": "micro_diffusion_amd.trainer:FusedAdamW",
@@ -98,6 +100,15 @@ def load_config(config_path: str, config_name: str, overrides: List[str] = ()) -
         cfg = coerce_numbers(yaml.safe_load(fh))
     apply_overrides(cfg, list(overrides))
     return coerce_numbers(resolve(cfg))
+
+
+def names_target(cfg: Any, target: str) -> bool:
+    """True when any node of the config carries `_target_: <target>`."""
+    if isinstance(cfg, dict):
+        return cfg.get("_target_") == target or any(names_target(v, target) for v in cfg.values())
+    if isinstance(cfg, list):
+        return any(names_target(v, target) for v in cfg)
+    return False
 
 
 def locate(target: str):

@@ -5,6 +5,8 @@
 //   md_adamw_step                clip (coef = min(1, max_norm / (||g|| + 1e-6)), read from the device-side sum: no host sync)
 //                                + decoupled-weight-decay Adam + bf16 shadow-weight emit + gradient zeroing + optional EMA of the
 //                                weights, one pass: 34 B / parameter (p, m, v read + write, g read + zero, shadow write; +8 with EMA)
+//   md_step_guard                go flag of the step from the same device-side sum (finite or not) + running count of skipped steps;
+//   md_adamw_step[_ranges]_guarded  the AdamW pass with that flag: a non-finite step leaves weights and moments untouched (no host sync)
 // Gradients may be supplied as bf16 (the data-parallel exchange buffer) instead of the fp32 accumulators.
 // Replaces clip_grad_norm_ (train.py:85-86), torch.optim.AdamW (train.py:39-43; configs/*.yaml optimizer) and the EMA algorithm
 // named by configs/res_512_*.yaml:4-9 (diffusion.algorithms.ema.EMA: ema = s * ema + (1 - s) * p every batch after ema_start).
@@ -70,8 +72,45 @@ struct AdamWRanges {
     int64_t flat[ADAMW_MAX_RANGES];
 };
 
+// Flat float4 index of packed float4 `ip` (md_adamw_step_ranges): the last range whose start <= the element.
+__device__ __forceinline__ int64_t range_flat4(const AdamWRanges& rg, int64_t ip) {
+    int lo = 0, hi = rg.n - 1;
+    const int64_t e = ip * 4;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (rg.start[mid] <= e) lo = mid; else hi = mid - 1;
+    }
+    return (rg.flat[lo] + (e - rg.start[lo])) >> 2;
+}
+
+// `guard` (md_adamw_step_guarded; NULL = no guard): the go flag md_step_guard derived from the step's gradient norm.  One uniform
+// read per wave; at 0 the workgroup runs the skip loop instead of the update.
 template <bool GBF16, int EMA, bool RANGES>
-__global__ __launch_bounds__(256) void adamw_kernel(md_adamw_args a, AdamWRanges rg) {
+__global__ __launch_bounds__(256) void adamw_kernel(md_adamw_args a, AdamWRanges rg, const int32_t* guard) {
+    if (guard && *guard == 0) {
+        // Skipped step (non-finite gradient norm): p, m, v and a live EMA stay as they are, bit for bit.  What the rest of the step
+        // relies on still happens: the accumulators are zeroed, the bf16 weights are (re-)emitted from the unchanged masters (the
+        // sharded all-gather sends that buffer) and the first EMA batch still copies the weights.
+        const float* P = reinterpret_cast<const float*>(a.p);
+        float* G = reinterpret_cast<float*>(a.g);
+        float* Em = reinterpret_cast<float*>(a.ema);
+        bf16* S = reinterpret_cast<bf16*>(a.shadow);
+        const int64_t n4 = a.n / 4;
+        for (int64_t ip = (int64_t)blockIdx.x * 256 + threadIdx.x; ip < n4; ip += (int64_t)gridDim.x * 256) {
+            const int64_t i = RANGES ? range_flat4(rg, ip) : ip;
+            if (EMA == 1 || S) {
+                const float4 p = nt_load4(P + i * 4);
+                if (EMA == 1) nt_store4(Em + i * 4, p);
+                if (S) {
+                    bf16x4 o;
+                    o[0] = f2bf(p.x); o[1] = f2bf(p.y); o[2] = f2bf(p.z); o[3] = f2bf(p.w);
+                    st_bf16x4(S + ip * 4, o);
+                }
+            }
+            if (a.zero_grad) nt_store4(G + i * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+        }
+        return;
+    }
     float coef = a.grad_scale;
     if (a.sumsq && a.max_norm > 0.f) {
         const float nrm = sqrtf(*reinterpret_cast<const float*>(a.sumsq)) * a.grad_scale;
@@ -94,16 +133,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(md_adamw_args a, AdamWRanges
     for (int64_t ip = (int64_t)blockIdx.x * 256 + threadIdx.x; ip < n4; ip += (int64_t)gridDim.x * 256) {
         // RANGES: ip indexes the PACKED space (where the bf16 gradient and the bf16 weight output live); i is the same float4 in
         // the flat buffers (masters, moments, EMA, fp32 gradient).  Chunks are multiples of 64 elements: a float4 never straddles.
-        int64_t i = ip;
-        if (RANGES) {
-            int lo = 0, hi = rg.n - 1;
-            const int64_t e = ip * 4;
-            while (lo < hi) {                      // last range whose start <= e
-                const int mid = (lo + hi + 1) >> 1;
-                if (rg.start[mid] <= e) lo = mid; else hi = mid - 1;
-            }
-            i = (rg.flat[lo] + (e - rg.start[lo])) >> 2;
-        }
+        const int64_t i = RANGES ? range_flat4(rg, ip) : ip;
         float4 p = nt_load4(P + i * 4);
         float4 m = nt_load4(Mo + i * 4);
         float4 v = nt_load4(Vo + i * 4);
@@ -199,7 +229,21 @@ extern "C" int md_checksum_u16(const void* x, int64_t n, uint64_t* out2, hipStre
     return 0;
 }
 
-extern "C" int md_adamw_step(const md_adamw_args* a, hipStream_t st) {
+// state[0] = go flag of this step, state[1] = running count of skipped steps (one thread, plain stores)
+__global__ void step_guard_kernel(const float* sumsq, int32_t* state) {
+    const bool ok = isfinite(*sumsq);
+    state[0] = ok ? 1 : 0;
+    if (!ok) state[1] += 1;
+}
+
+extern "C" int md_step_guard(const float* sumsq, int32_t* state, hipStream_t st) {
+    if (!sumsq || !state) return MD_BAD_ARG;
+    hipLaunchKernelGGL(step_guard_kernel, dim3(1), dim3(1), 0, st, sumsq, state);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_adamw_step_guarded(const md_adamw_args* a, const int32_t* guard, hipStream_t st) {
     if (!a || !a->p || !a->g || !a->m || !a->v || a->n <= 0 || a->n % 4) return MD_BAD_ARG;
     if (a->ema_mode < 0 || a->ema_mode > 2 || (a->ema_mode && !a->ema)) return MD_BAD_ARG;
     // one 256-thread workgroup per 4 KiB of every stream and iteration; 8 workgroups resident per CU x 256 CUs x 4 rounds
@@ -208,7 +252,7 @@ extern "C" int md_adamw_step(const md_adamw_args* a, hipStream_t st) {
     const dim3 gd((unsigned)grid), bd(256);
     AdamWRanges none;
     none.n = 0;
-#define ADAMW(GB, E) hipLaunchKernelGGL((adamw_kernel<GB, E, false>), gd, bd, 0, st, *a, none)
+#define ADAMW(GB, E) hipLaunchKernelGGL((adamw_kernel<GB, E, false>), gd, bd, 0, st, *a, none, guard)
     if (a->g_bf16) {
         if (a->ema_mode == 0) ADAMW(true, 0); else if (a->ema_mode == 1) ADAMW(true, 1); else ADAMW(true, 2);
     } else {
@@ -219,8 +263,10 @@ extern "C" int md_adamw_step(const md_adamw_args* a, hipStream_t st) {
     return 0;
 }
 
-extern "C" int md_adamw_step_ranges(const md_adamw_args* a, const int64_t* flat_off, const int64_t* count, int32_t n_ranges,
-                                    hipStream_t st) {
+extern "C" int md_adamw_step(const md_adamw_args* a, hipStream_t st) { return md_adamw_step_guarded(a, nullptr, st); }
+
+extern "C" int md_adamw_step_ranges_guarded(const md_adamw_args* a, const int64_t* flat_off, const int64_t* count, int32_t n_ranges,
+                                            const int32_t* guard, hipStream_t st) {
     if (!a || !a->p || !a->g || !a->m || !a->v || !a->g_bf16 || !flat_off || !count || n_ranges < 1 || n_ranges > ADAMW_MAX_RANGES)
         return MD_BAD_ARG;
     if (a->ema_mode < 0 || a->ema_mode > 2 || (a->ema_mode && !a->ema) || a->zero_grad) return MD_BAD_ARG;
@@ -239,9 +285,14 @@ extern "C" int md_adamw_step_ranges(const md_adamw_args* a, const int64_t* flat_
     int64_t grid = (tot / 4 + 255) / 256;
     if (grid > 8192) grid = 8192;
     const dim3 gd((unsigned)grid), bd(256);
-#define ADAMWR(E) hipLaunchKernelGGL((adamw_kernel<true, E, true>), gd, bd, 0, st, b, rg)
+#define ADAMWR(E) hipLaunchKernelGGL((adamw_kernel<true, E, true>), gd, bd, 0, st, b, rg, guard)
     if (a->ema_mode == 0) ADAMWR(0); else if (a->ema_mode == 1) ADAMWR(1); else ADAMWR(2);
 #undef ADAMWR
     MD_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int md_adamw_step_ranges(const md_adamw_args* a, const int64_t* flat_off, const int64_t* count, int32_t n_ranges,
+                                    hipStream_t st) {
+    return md_adamw_step_ranges_guarded(a, flat_off, count, n_ranges, nullptr, st);
 }

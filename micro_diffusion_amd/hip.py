@@ -165,6 +165,12 @@ class AdamWArgs(Structure):
 
 
 SUMSQ_PARTIALS = 1024    # MD_SUMSQ_PARTIALS
+STATS_ITEM_MAX = 65536   # MD_STATS_ITEM_MAX
+
+
+class StatsItem(Structure):
+    """md_stats_item: one piece (<= STATS_ITEM_MAX elements) of one tensor inside the buffer md_tensor_stats_partial reads."""
+    _fields_ = [("src_off", c_int64), ("count", c_int32), ("tensor", c_int32)]
 
 
 _sig("md_gemm_bf16", POINTER(GemmArgs), P)
@@ -212,6 +218,12 @@ _sig("md_sumsq_finish", P, I64, P, P)
 _sig("md_checksum_u16", P, I64, P, P)
 _sig("md_adamw_step", POINTER(AdamWArgs), P)
 _sig("md_adamw_step_ranges", POINTER(AdamWArgs), P, P, I32, P)
+# training health: per-tensor statistics (optimizer monitor) and the device-side non-finite step guard
+_sig("md_tensor_stats_partial", P, I32, P, I64, P, P, P, P)
+_sig("md_tensor_stats_finish", P, P, P, P, I32, P, P, P, P)
+_sig("md_step_guard", P, P, P)
+_sig("md_adamw_step_guarded", POINTER(AdamWArgs), P, P)
+_sig("md_adamw_step_ranges_guarded", POINTER(AdamWArgs), P, P, I32, P, P)
 # deterministic (atomic-free) forms of the three column reductions; md_det_ws_floats sizes their workspace
 _sig("md_det_ws_floats", I32, I64, I64, I64, I64, POINTER(c_int64))
 _sig("md_ln_bwd_det", POINTER(LnArgs), POINTER(LnBwdArgs), P, I64, P)

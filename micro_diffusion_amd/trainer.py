@@ -15,7 +15,11 @@ configs/*.yaml), re-designed for one process per GPU with RCCL over xGMI:
     the whole optimiser pass).  Transport: torch.distributed (default) or libmicrodit_comm.so (`transport="native"`);
   * the squared gradient norm is taken per reduced bucket on a side stream behind its collective (fixed-order partial sums:
     the clip coefficient is bit-identical on all ranks, no host sync), then one fused pass clips, applies AdamW, re-emits the
-    bf16 shadow weights and (all-reduce form) zeroes the gradients.
+    bf16 shadow weights and (all-reduce form) zeroes the gradients;
+  * training health (opt-in): `Trainer(monitor_interval=N)` takes per-tensor gradient / weight statistics every N batches
+    (md_tensor_stats_*: Composer's OptimizerMonitor, configs/*.yaml callbacks.optimizer_monitor) and
+    `FusedAdamW(skip_nonfinite=True)` turns a step whose gradient norm is not finite into a no-op on the device (md_step_guard:
+    the reference's NaNCatcher, but before the update reaches the weights and without a host sync).
 """
 from __future__ import annotations
 
@@ -76,6 +80,92 @@ class LRSchedule:
         return self.alpha_f + (1 - self.alpha_f) * 0.5 * (1 + math.cos(math.pi * frac))
 
 
+def stats_items(offs, numels, present, item_max: int = hip.STATS_ITEM_MAX):
+    """Work items of md_tensor_stats_partial (pure host code).  `offs` / `numels`: flat offset and exact element count of every
+    tensor, in the order of the result table.  `present`: [(flat_lo, count, src_off)] -- the stretches of the flat index space the
+    source buffer holds, and where (in elements of that buffer): the whole flat buffer is [(0, total, 0)], a rank's packed chunk
+    buffer [(lo + rank * chunk, chunk, olo) for ... in shard_plan(...)[0]], the small region inside the whole-size bf16 exchange
+    buffer [(lo, hi - lo, lo)].  Every tensor's intersection with `present` is cut into pieces of at most `item_max` elements.
+    Returns (items, item_begin): items = [(src_off, count, tensor)] sorted by tensor, item_begin[t] .. item_begin[t + 1] = the run of
+    tensor t (empty when the buffer holds nothing of it)."""
+    if item_max <= 0 or item_max % 8:
+        raise ValueError("item_max must be a positive multiple of 8 (16-byte loads)")
+    stretches = sorted(present)
+    items, item_begin = [], [0]
+    for t, (o, n) in enumerate(zip(offs, numels)):
+        for lo, cnt, src in stretches:
+            a, b = max(o, lo), min(o + n, lo + cnt)
+            if a >= b:
+                continue
+            so = src + (a - lo)
+            if so % 8:
+                raise ValueError(f"tensor {t}: source offset {so} is not a multiple of 8 elements")
+            while a < b:
+                c = min(item_max, b - a)
+                items.append((so, c, t))
+                so += c
+                a += c
+        item_begin.append(len(items))
+    return items, item_begin
+
+
+def combine_rank_tables(table: torch.Tensor, small: torch.Tensor) -> torch.Tensor:
+    """Per-rank statistics tables [world, 3, T] (rows: sum of squares, max |x|, non-finite count; rank r's table at index r) -> the
+    table of the whole buffer [3, T]: rows reduced in RANK ORDER (sum, max, sum), the tensors of the small region (`small`: bool
+    [T]), which every rank holds whole, taken from rank 0.  Every element is counted once; the order is fixed, so every rank that
+    holds the same [world, 3, T] gets the same bits."""
+    out = table[0].clone()
+    for r in range(1, table.shape[0]):
+        out[0] += table[r, 0]
+        out[1] = torch.maximum(out[1], table[r, 1])
+        out[2] += table[r, 2]
+    return torch.where(small.unsqueeze(0), table[0], out)
+
+
+class _StatsPlan:
+    """Device-side item tables and result buffers of one statistics pass (cached per layout and exchange mode).
+    sources = [(buffer, present)]: one md_tensor_stats_partial call each, into consecutive slices of the partial arrays."""
+
+    def __init__(self, offs, numels, sources, device):
+        import numpy as np
+        self.sources, items_all = [], []
+        for buf, present in sources:
+            items, _ = stats_items(offs, numels, present)
+            if items:
+                self.sources.append((buf, 1 if buf.dtype == torch.bfloat16 else 0, len(items_all), len(items)))
+                items_all += items
+        if any(a[2] > b[2] for a, b in zip(items_all, items_all[1:])):
+            raise RuntimeError("statistics items of the sources do not concatenate in tensor order")
+        T = self.n_tensors = len(offs)
+        begin = [0] * (T + 1)
+        for _, _, t in items_all:
+            begin[t + 1] += 1
+        for t in range(T):
+            begin[t + 1] += begin[t]
+        arr = np.zeros(max(len(items_all), 1), dtype=np.dtype([("o", "<i8"), ("c", "<i4"), ("t", "<i4")]))    # md_stats_item
+        for i, it in enumerate(items_all):
+            arr[i] = it
+        self.items = torch.from_numpy(arr.view(np.int64).reshape(-1, 2).copy()).to(device)
+        self.item_begin = torch.tensor(begin, dtype=torch.int32, device=device)
+        n = max(len(items_all), 1)
+        self.part_f = torch.zeros(2, n, device=device)
+        self.part_i = torch.zeros(n, device=device, dtype=torch.int32)
+        self.out_f = torch.zeros(2, T, device=device)                       # sum of squares, max |x|
+        self.out_i = torch.zeros(T, device=device, dtype=torch.int32)       # non-finite count
+
+    def run(self):
+        L, st = hip.lib(), torch.cuda.current_stream().cuda_stream
+        pf, pi = self.part_f, self.part_i
+        for buf, is_bf16, first, n in self.sources:
+            hip.check(L.md_tensor_stats_partial(buf.data_ptr(), is_bf16, self.items.data_ptr() + 16 * first, n,
+                                                pf[0].data_ptr() + 4 * first, pf[1].data_ptr() + 4 * first, pi.data_ptr() + 4 * first, st),
+                      "md_tensor_stats_partial")
+        hip.check(L.md_tensor_stats_finish(pf[0].data_ptr(), pf[1].data_ptr(), pi.data_ptr(), self.item_begin.data_ptr(), self.n_tensors,
+                                           self.out_f[0].data_ptr(), self.out_f[1].data_ptr(), self.out_i.data_ptr(), st),
+                  "md_tensor_stats_finish")
+        return self.out_f, self.out_i
+
+
 class FusedAdamW:
     """torch.optim.AdamW semantics (train.py:39-43) on the DiT's flat buffers, one HIP kernel per step; optionally the
     EMA of the weights the res-512 configs name (configs/res_512_pretrain.yaml:4-9: smoothing 0.99975, every batch, from
@@ -84,7 +174,13 @@ class FusedAdamW:
     MAX_BUCKETS = 64      # per-bucket partial sums of the gradient norm (data-parallel exchange), MD_SUMSQ_PARTIALS floats each
 
     def __init__(self, dit, lr: float = 2.4e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.1,
-                 ema_smoothing: Optional[float] = None, ema_start: int = 0):
+                 ema_smoothing: Optional[float] = None, ema_start: int = 0, skip_nonfinite: bool = False):
+        """`skip_nonfinite`: guard the step on the device.  The squared gradient norm is then taken on every step (also with
+        max_norm == 0), md_step_guard derives a go flag from it and the AdamW pass runs in its guarded form: when the norm is not
+        finite (a NaN or an Inf anywhere in the gradient) weights, moments and a live EMA stay untouched bit for bit, the
+        accumulators are still zeroed and the bf16 weights re-emitted.  No host sync; skipped_steps() reads the device counter.
+        A skipped step is a consumed batch with a zero update: the host-side step_count (bias corrections), the LR-schedule
+        position (Trainer.batches_seen) and ema_live advance as on any other step."""
         self.dit = dit
         f = dit.flat_buffers()
         self.lr, self.betas, self.eps, self.weight_decay = lr, tuple(betas), eps, weight_decay
@@ -98,6 +194,15 @@ class FusedAdamW:
         self.ema = torch.zeros_like(f["p"]) if ema_smoothing is not None else None
         self.ema_live = False
         self.last_grad_scale = 1.0
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guard_state = torch.zeros(4, device=f["p"].device, dtype=torch.int32) if self.skip_nonfinite else None    # md_step_guard
+
+    def skipped_steps(self) -> int:
+        """Steps the device-side guard turned into a no-op so far (synchronises: the only host read of the guard)."""
+        return int(self.guard_state[1].item()) if self.guard_state is not None else 0
+
+    def _guard(self, st) -> None:
+        hip.check(hip.lib().md_step_guard(self.sumsq.data_ptr(), self.guard_state.data_ptr(), st), "md_step_guard")
 
     def ensure_norm_slots(self, n: int) -> None:
         """Room for `n` per-bucket partial sums of the gradient norm (a model with more data-parallel buckets than MAX_BUCKETS:
@@ -118,7 +223,10 @@ class FusedAdamW:
                           (self.ema.data_ptr() + 4 * off) if self.ema is not None else None, n, lr, b1, b2, self.eps,
                           self.weight_decay, 1 - b1 ** self.step_count, 1 - b2 ** self.step_count, max_norm or 0.0, grad_scale,
                           self.ema_smoothing or 0.0, zero_grad, ema_mode)
-        hip.check(L.md_adamw_step(byref(a), st), "md_adamw_step")
+        if self.skip_nonfinite:
+            hip.check(L.md_adamw_step_guarded(byref(a), self.guard_state.data_ptr(), st), "md_adamw_step_guarded")
+        else:
+            hip.check(L.md_adamw_step(byref(a), st), "md_adamw_step")
 
     def _begin_step(self, grad_scale: float) -> int:
         self.step_count += 1
@@ -137,13 +245,15 @@ class FusedAdamW:
         L, st = hip.lib(), torch.cuda.current_stream().cuda_stream
         ema_mode = self._begin_step(grad_scale)
         ss = None
-        if max_norm and max_norm > 0:
+        if (max_norm and max_norm > 0) or self.skip_nonfinite:
             if norm_partials <= 0:
                 src = g_bf16 if g_bf16 is not None else f["g"]
                 hip.check(L.md_sumsq(src.data_ptr(), 1 if g_bf16 is not None else 0, f["total"], self.partials.data_ptr(), st), "md_sumsq")
                 norm_partials = hip.SUMSQ_PARTIALS
             hip.check(L.md_sumsq_finish(self.partials.data_ptr(), norm_partials, self.sumsq.data_ptr(), st), "md_sumsq_finish")
             ss = self.sumsq.data_ptr()
+            if self.skip_nonfinite:
+                self._guard(st)
         self._launch(0, f["total"], self.lr if lr is None else lr, max_norm, grad_scale, ss,
                      g_bf16.data_ptr() if g_bf16 is not None else None, f["s"].data_ptr(), 1, ema_mode)
         self.dit.mark_shadow_fresh()
@@ -160,9 +270,11 @@ class FusedAdamW:
         ema_mode = self._begin_step(grad_scale)
         lr = self.lr if lr is None else lr
         ss = None
-        if max_norm and max_norm > 0:
+        if (max_norm and max_norm > 0) or self.skip_nonfinite:
             sync.finish_sharded_norm(norm_slots, self.sumsq)
             ss = self.sumsq.data_ptr()
+            if self.skip_nonfinite:
+                self._guard(torch.cuda.current_stream().cuda_stream)
         # ONE launch over the rank's chunks (md_adamw_step_ranges: the kernel walks the packed space the reduce-scattered gradient
         # and the send buffer live in, a range table maps it onto the flat masters / moments)
         ranges = [(lo + sync.rank * chunk, chunk if chunk_of is None else (hi - lo) // chunk_of // 64 * 64) for _, lo, hi, chunk, _ in sync.plan]
@@ -179,8 +291,13 @@ class FusedAdamW:
                               sync.gred.data_ptr(), self.ema.data_ptr() if self.ema is not None else None, 0, lr, b1, b2, self.eps,
                               self.weight_decay, 1 - b1 ** self.step_count, 1 - b2 ** self.step_count, max_norm or 0.0, grad_scale,
                               self.ema_smoothing or 0.0, 0, ema_mode)
-            hip.check(hip.lib().md_adamw_step_ranges(byref(a), self._range_off, self._range_cnt, len(ranges),
-                                                     torch.cuda.current_stream().cuda_stream), "md_adamw_step_ranges")
+            if self.skip_nonfinite:
+                hip.check(hip.lib().md_adamw_step_ranges_guarded(byref(a), self._range_off, self._range_cnt, len(ranges),
+                                                                 self.guard_state.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                          "md_adamw_step_ranges_guarded")
+            else:
+                hip.check(hip.lib().md_adamw_step_ranges(byref(a), self._range_off, self._range_cnt, len(ranges),
+                                                         torch.cuda.current_stream().cuda_stream), "md_adamw_step_ranges")
         else:                                   # more buckets than the kernel's table holds: chunk by chunk
             for _, lo, hi, chunk, olo in sync.plan:
                 self._launch(lo + sync.rank * chunk, chunk, lr, max_norm, grad_scale, ss, sync.gred.data_ptr() + 2 * olo,
@@ -193,7 +310,7 @@ class FusedAdamW:
 
     def grad_norm(self) -> torch.Tensor:
         """||g||_2 of the last step's (rank-averaged) gradient before clipping (device scalar; valid after step() with
-        max_norm > 0).  The sum of squares is taken over the rank-SUMMED gradient; the 1 / world factor is applied here as in
+        max_norm > 0 or skip_nonfinite).  The sum of squares is taken over the rank-SUMMED gradient; the 1 / world factor is applied here as in
         the optimiser kernel."""
         return self.sumsq.sqrt() * self.last_grad_scale
 
@@ -675,8 +792,11 @@ class GradSync:
 class Trainer:
     def __init__(self, model, optimizer: FusedAdamW, schedule: Optional[LRSchedule] = None, clip_norm: float = 0.0,
                  microbatch_size: int = 256, process_group=None, log: Optional[Callable[[dict], None]] = None,
-                 exchange: str = "auto", single_rank_exchange: bool = False, dp_mode: str = "auto", transport: str = "auto"):
-        """dp_mode: "sharded" (reduce-scatter + sharded AdamW + all-gather of the bf16 weights, the reference's SHARD_GRAD_OP;
+                 exchange: str = "auto", single_rank_exchange: bool = False, dp_mode: str = "auto", transport: str = "auto",
+                 monitor_interval: int = 0):
+        """monitor_interval: N > 0 takes the per-tensor statistics (collect_tensor_stats) on every batch whose number is a multiple
+        of N, between the gradient exchange and the optimiser pass; 0 = never (no launch, no buffer).
+        dp_mode: "sharded" (reduce-scatter + sharded AdamW + all-gather of the bf16 weights, the reference's SHARD_GRAD_OP;
         default for N > 1 over RCCL) or "allreduce" (every rank runs the whole optimiser pass); "auto" also honours the
         MD_DP_MODE environment variable."""
         import os
@@ -714,6 +834,9 @@ class Trainer:
         model.dit._ensure_flat()
         model.dit.engine.use_arena = True
         self.batches_seen = 0
+        self.monitor_interval = int(monitor_interval)
+        self._stats_plans: Dict[str, _StatsPlan] = {}
+        self._stats_last = None
         self.log = log
         self._win: List[tuple] = []
         self.measure_comm = False          # bench.py: event pairs around GradSync.finish() (exposed exchange time)
@@ -747,6 +870,8 @@ class Trainer:
         if self.measure_comm:
             e1.record()                                  # behind the waits on the collectives / side-stream norms
             self._comm_events.append((e0, e1))
+        if self.monitor_interval > 0 and (self.batches_seen + 1) % self.monitor_interval == 0:
+            self.collect_tensor_stats()                  # reads the gradients the optimiser pass is about to consume and clear
         fac = self.schedule.factor(self.batches_seen) if self.schedule is not None else 1.0
         if self.measure_comm:
             o0, o1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -764,6 +889,82 @@ class Trainer:
             self._opt_events.append((o0, o1))
         self.batches_seen += 1
         return total.reshape(())
+
+    # ------------------------------------------------------------------ per-tensor statistics (optimizer monitor)
+    def _stats_names(self) -> List[str]:
+        """Rows of the statistics tables: the parameters in FLAT order (matrix-shaped tensors first, the small region last), so the
+        items of the sharded exchange's two gradient buffers concatenate in tensor order."""
+        f = self.model.dit.flat_buffers()
+        return sorted(f["P"], key=lambda n: f["offs"][n])
+
+    def _stats_plan(self, kind: str) -> _StatsPlan:
+        if kind not in self._stats_plans:
+            f, s = self.model.dit.flat_buffers(), self.sync
+            names = self._stats_names()
+            offs, numels = [f["offs"][n] for n in names], [f["P"][n].numel() for n in names]
+            if self.sharded:
+                own = [(lo + s.rank * chunk, chunk, olo) for _, lo, hi, chunk, olo in s.plan]
+                small = [(s.small[0], s.small[1] - s.small[0], s.small[0])] if s.small is not None else []
+                if kind == "grad":          # reduced chunks packed in gred; the small region all-reduced inside the whole-size gbf
+                    sources = [(s.gred, own), (s.gbf, small)]
+                else:                       # fp32 masters: this rank's chunks and the small region are current, foreign chunks stale
+                    sources = [(f["p"], [(lo, cnt, lo) for lo, cnt, _ in own] + small)]
+            elif kind == "grad":
+                sources = [(s.gbf if (s.enabled and s.gbf is not None) else f["g"], [(0, f["total"], 0)])]
+            else:
+                sources = [(f["p"], [(0, f["total"], 0)])]
+            self._stats_plans[kind] = _StatsPlan(offs, numels, sources, f["p"].device)
+        return self._stats_plans[kind]
+
+    def collect_tensor_stats(self) -> None:
+        """One statistics pass over the step's gradients and the fp32 masters (train_step calls it between GradSync.finish() and the
+        optimiser pass on monitor steps).  Gradient source: the fp32 accumulators without an exchange, the bf16 exchange buffer in
+        all-reduce mode, the packed reduced chunks plus the small region in sharded mode.  Sharded with more than one rank: every
+        rank writes its rows into a zero [world, 3, T] table at its rank index, ONE SUM all-reduce (the exchange's transport)
+        distributes it and combine_rank_tables reduces the rows in rank order -- bit-identical on all ranks, no MAX collective.
+        Enqueues only; tensor_stats() reads."""
+        last = {}
+        for kind in ("grad", "param"):
+            out_f, out_i = self._stats_plan(kind).run()
+            if self.sharded and self.world > 1:
+                T = out_f.shape[1]
+                table = torch.zeros(self.world, 3, T, device=out_f.device)
+                table[self.sync.rank, :2] = out_f
+                table[self.sync.rank, 2] = out_i.float()
+                w = self.sync._all_reduce(table.view(-1))
+                if w is not None:
+                    w.wait()
+                f = self.model.dit.flat_buffers()
+                lo = self.sync.small[0] if self.sync.small is not None else f["total"]
+                small = torch.tensor([f["offs"][n] >= lo for n in self._stats_names()], device=out_f.device)
+                comb = combine_rank_tables(table, small)
+                out_f, out_i = comb[:2], comb[2].to(torch.int32)
+            last[kind] = (out_f, out_i)
+        last["grad_scale"] = 1.0 / self.world
+        last["batch"] = self.batches_seen + 1
+        self._stats_last = last
+
+    def tensor_stats(self) -> dict:
+        """The last statistics pass as Python numbers (synchronises; {} before the first pass), keyed Composer-style:
+          l2_norm/grad/<name>, l2_norm/grad/global, l2_norm/param/<name>, absmax/grad/<name>, nonfinite/grad/<name>
+        with the parameter names of dit.flat_buffers()["P"].  Gradient values describe the UNCLIPPED, rank-averaged gradient (the
+        rank-summed buffer times 1 / world, as FusedAdamW.grad_norm()); non-finite elements are counted and left out of norm and
+        maximum.  Composer's source is not available offline: the key names are pinned from memory of its OptimizerMonitor
+        (`l2_norm/grad/<parameter>`, `l2_norm/grad/global`), in the same sense as SURVEY.md Appendix C; absmax/ and nonfinite/ have
+        no Composer counterpart."""
+        if self._stats_last is None:
+            return {}
+        last, names = self._stats_last, self._stats_names()
+        (gf, gi), (pf, _) = last["grad"], last["param"]
+        gf, gi, pf = gf.double().cpu(), gi.cpu(), pf.double().cpu()
+        sc, out = last["grad_scale"], {}
+        for t, n in enumerate(names):
+            out[f"l2_norm/grad/{n}"] = math.sqrt(float(gf[0, t])) * sc
+            out[f"absmax/grad/{n}"] = float(gf[1, t]) * sc
+            out[f"nonfinite/grad/{n}"] = int(gi[t])
+            out[f"l2_norm/param/{n}"] = math.sqrt(float(pf[0, t]))
+        out["l2_norm/grad/global"] = math.sqrt(float(gf[0].sum())) * sc
+        return out
 
     def exposed_comm_ms(self, last: int = 0) -> Optional[float]:
         """Mean time per step the compute stream spent waiting for the gradient exchange after the last backward kernel was

@@ -63,8 +63,18 @@ def train(cfg: dict):
         if ema_cfg.get("half_life") is not None or parse_batches(ema_cfg.get("update_interval", "1ba")) != 1:
             raise ValueError("ema: only `smoothing` with update_interval 1ba is supported (the values the stage configs use)")
         ema_kw = dict(ema_smoothing=float(ema_cfg["smoothing"]), ema_start=parse_batches(ema_cfg.get("ema_start", "0ba")))
+    misc = cfg.get("misc") or {}
+    # Training health, both off by default.  misc.skip_nonfinite_steps: the device-side guard replaces the per-step
+    # host check of the loss (NaNCatcher) -- a non-finite step leaves the weights untouched and is counted.
+    # misc.optimizer_monitor_interval: the YAML's callbacks.optimizer_monitor (composer.callbacks.OptimizerMonitor) every N batches.
+    skip_nonfinite = bool(misc.get("skip_nonfinite_steps", False))
+    max_skipped = int(misc.get("max_skipped_steps", 10))
+    monitor_every = int(misc.get("optimizer_monitor_interval", 0) or 0)
+    if not mdcfg.names_target(cfg, "composer.callbacks.OptimizerMonitor"):
+        monitor_every = 0
+    guard_kw = dict(skip_nonfinite=True) if skip_nonfinite else {}
     opt = FusedAdamW(model.dit, lr=ocfg["lr"], betas=tuple(ocfg.get("betas", (0.9, 0.999))), eps=ocfg.get("eps", 1e-8),
-                     weight_decay=ocfg.get("weight_decay", 0.0), **ema_kw)
+                     weight_decay=ocfg.get("weight_decay", 0.0), **ema_kw, **guard_kw)
     if carried_opt is not None:
         opt.load_state_dict(carried_opt)          # keyed by parameter name; raises on a mismatch with this model
     max_ba = parse_batches(cfg["trainer"]["max_duration"])
@@ -82,7 +92,9 @@ def train(cfg: dict):
     ds = cfg["dataset"]
     loader = mdcfg.instantiate(ds["train"], image_size=ds["image_size"], batch_size=ds["train_batch_size"] // world,
                                cap_seq_size=seq, cap_emb_dim=emb, cap_drop_prob=ds["cap_drop_prob"])
-    trainer = Trainer(model, opt, sched, clip_norm=clip, microbatch_size=int(cfg["trainer"]["device_train_microbatch_size"]))
+    monitor_kw = dict(monitor_interval=monitor_every) if monitor_every > 0 else {}
+    trainer = Trainer(model, opt, sched, clip_norm=clip, microbatch_size=int(cfg["trainer"]["device_train_microbatch_size"]),
+                      **monitor_kw)
     save_every = parse_batches(cfg["trainer"].get("save_interval", "0ba"))
     folder = cfg["trainer"].get("save_folder")
     log_every = int(cfg.get("misc", {}).get("log_interval", 10))
@@ -113,8 +125,13 @@ def train(cfg: dict):
     trainer.sync_replicas()        # rank 0's weights / moments everywhere (same-seed init and resume make them equal already)
     check_every = int(cfg.get("misc", {}).get("replica_check_interval", 500))
     t_last = time.time()
+    skipped_logged = 0
     for step, batch in zip(range(start, max_ba), loader):
         loss = trainer.train_step(batch)
+        if monitor_every > 0 and (step + 1) % monitor_every == 0:
+            stats = trainer.tensor_stats()                         # a collective-free read (every rank holds the same table)
+            if rank == 0:
+                print(json.dumps({"batch": step + 1, "optimizer_monitor": stats}), flush=True)
         if eval_loader is not None and (step + 1) % eval_every == 0:
             trainer.consolidate()                                  # sharded optimiser: whole fp32 weights / EMA on every rank
             ev = evaluate(model, eval_loader, world, microbatch=trainer.microbatch_size, opt=opt)
@@ -122,13 +139,22 @@ def train(cfg: dict):
                 print(json.dumps({"batch": step + 1, "metrics/eval/loss": ev}), flush=True)
         if world > 1 and check_every and (step + 1) % check_every == 0 and not trainer.replicas_in_sync():
             raise RuntimeError(f"data-parallel replicas diverged at batch {step + 1} (weight checksums differ across ranks)")
-        if not torch.isfinite(loss):                               # NaNCatcher (callbacks.py:47-64)
+        if not skip_nonfinite and not torch.isfinite(loss):        # NaNCatcher (callbacks.py:47-64)
             raise RuntimeError(f"Train loss contains a NaN at batch {step}")
+        if skip_nonfinite and (step + 1) % log_every == 0:         # every rank: the guard's counter is identical on all of them
+            skipped = opt.skipped_steps()
+            if skipped - skipped_logged > max_skipped:
+                raise RuntimeError(f"{skipped - skipped_logged} optimizer steps since batch {max(step + 1 - log_every, start)} had a "
+                                   f"non-finite gradient norm and were skipped (misc.max_skipped_steps = {max_skipped})")
+            skipped_logged = skipped
         if rank == 0 and (step + 1) % log_every == 0:
             torch.cuda.synchronize()
             dt, t_last = time.time() - t_last, time.time()
-            print(json.dumps({"batch": step + 1, "loss": float(loss), "lr": opt.lr * sched.factor(step),
-                              "samples_per_sec": ds["train_batch_size"] * log_every / dt}), flush=True)
+            line = {"batch": step + 1, "loss": float(loss), "lr": opt.lr * sched.factor(step),
+                    "samples_per_sec": ds["train_batch_size"] * log_every / dt}
+            if skip_nonfinite:
+                line["skipped_steps"] = skipped_logged
+            print(json.dumps(line), flush=True)
         if folder and save_every and (step + 1) % save_every == 0:
             trainer.consolidate()                                  # a collective under the sharded optimiser: every rank calls it
         if rank == 0 and folder and save_every and (step + 1) % save_every == 0:
