@@ -353,6 +353,18 @@ int md_edm_sampler_input(const double* x, float* out, int64_t n, float sigma, fl
 int md_edm_heun_update(const double* x_hat, const double* x_in, const float* F, double* d_cur, double* x_next, int64_t n, float cfg,
                        int32_t has_uncond, double t_in, double t_hat, double t_next, float sigma_data, int32_t second,
                        hipStream_t stream);
+/* The same two steps in token space (the cached sampling path: the fp64 state is the only image-shaped tensor).
+ * md_edm_sampler_patchify: patches[row(b,ti,tj), c*p*p + ph*p + pw] = bf16(c_in(sigma) * (float)x[b,c,ti*p+ph,tj*p+pw]), bf16
+ * [B*T, C*p*p] (T = H/p * W/p); with `duplicate`, rows [B*T, 2*B*T) repeat rows [0, B*T).  The bits of md_edm_sampler_input followed
+ * by md_patchify(scale = NULL).
+ * md_edm_heun_update_tok: F of image element (b,c,h,w) is read from the network's token output, element (ph*p+pw)*C + c of row
+ * b*T + t (the unconditional half starts at row B*T), then exactly md_edm_heun_update.  The bits of md_unpatchify(ids_restore =
+ * NULL) followed by md_edm_heun_update. */
+int md_edm_sampler_patchify(const double* x, void* patches_bf16, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float sigma,
+                            float sigma_data, int32_t duplicate, hipStream_t stream);
+int md_edm_heun_update_tok(const double* x_hat, const double* x_in, const void* tok_bf16, double* d_cur, double* x_next, int64_t B,
+                           int32_t C, int32_t H, int32_t W, int32_t p, float cfg, int32_t has_uncond, double t_in, double t_hat,
+                           double t_next, float sigma_data, int32_t second, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------- optimiser */
 /* Sum of squares of a gradient buffer (fp32, or bf16 when g_is_bf16), deterministic: workgroup b of a fixed grid writes

@@ -155,11 +155,36 @@ inline int egrid(int64_t work) {
 //   heun_update   : F = Fu + cfg * (Fc - Fu);  D = c_skip * float(x_in) + c_out * F;  d = (x_in - D) / sigma;
 //                   first half-step : d_cur = d, x_next = x_hat + (t_next - t_hat) * d
 //                   second half-step: x_next = x_hat + (t_next - t_hat) * (0.5 d_cur + 0.5 d)
+//   sampler_patchify / heun_update_tok: the same two, writing bf16 patch rows / reading the bf16 token output directly
 // ---------------------------------------------------------------------------------------------------------------------
+// The per-element arithmetic, shared by the image-space and the token-space kernels below.  Every multiply-add is written as an
+// explicit fma: left to the compiler, the same expression was contracted in one kernel and evaluated as multiply, multiply, add in
+// another (it vectorises the two products first), and the two forms of a step must give the same bits.
+__device__ __forceinline__ float sampler_c_in(float sigma, float sigma_data) {
+    return 1.f / sqrtf(fmaf(sigma, sigma, sigma_data * sigma_data));
+}
+__device__ __forceinline__ float sampler_net_in(float c_in, double x) { return c_in * (float)x; }
+__device__ __forceinline__ void heun_coef(double t_in, float sigma_data, float& c_skip, float& c_out) {
+    const float sg = (float)t_in;
+    const float den = fmaf(sg, sg, sigma_data * sigma_data);
+    c_skip = sigma_data * sigma_data / den;
+    c_out = sg * sigma_data / sqrtf(den);
+}
+__device__ __forceinline__ float cfg_combine(float fc, float fu, float cfg) { return fmaf(cfg, fc - fu, fu); }
+// Returns x_next of one element; d receives the slope of this evaluation (the first half-step stores it as d_cur), d_prev is the
+// d_cur the second half-step reads.  Values in, values out: the callers load before they store, so x_next may alias x_in or x_hat.
+__device__ __forceinline__ double heun_element(double xi, double xh, float f, float c_skip, float c_out, double t_in, double t_hat,
+                                               double t_next, int second, double d_prev, double& d) {
+    const double D = (double)fmaf(c_skip, (float)xi, c_out * f);
+    d = (xi - D) / t_in;
+    if (!second) return fma(t_next - t_hat, d, xh);
+    return fma(t_next - t_hat, fma(0.5, d, 0.5 * d_prev), xh);
+}
+
 __global__ __launch_bounds__(256) void sampler_input_kernel(const double* x, float* out, int64_t n, float sigma, float sigma_data, int dup) {
-    const float c_in = 1.f / sqrtf(sigma_data * sigma_data + sigma * sigma);
+    const float c_in = sampler_c_in(sigma, sigma_data);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float v = c_in * (float)x[i];
+        const float v = sampler_net_in(c_in, x[i]);
         out[i] = v;
         if (dup) out[n + i] = v;
     }
@@ -168,28 +193,114 @@ __global__ __launch_bounds__(256) void sampler_input_kernel(const double* x, flo
 __global__ __launch_bounds__(256) void heun_update_kernel(const double* x_hat, const double* x_in, const float* F, double* d_cur,
                                                           double* x_next, int64_t n, float cfg, int has_uncond, double t_in, double t_hat,
                                                           double t_next, float sigma_data, int second) {
-    const float sg = (float)t_in;
-    const float den = sg * sg + sigma_data * sigma_data;
-    const float c_skip = sigma_data * sigma_data / den;
-    const float c_out = sg * sigma_data / sqrtf(den);
+    float c_skip, c_out;
+    heun_coef(t_in, sigma_data, c_skip, c_out);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double xi = x_in[i];
         float f = F[i];
-        if (has_uncond) {
-            const float fu = F[n + i];
-            f = fu + cfg * (f - fu);
+        if (has_uncond) f = cfg_combine(f, F[n + i], cfg);
+        double d;
+        x_next[i] = heun_element(xi, x_hat[i], f, c_skip, c_out, t_in, t_hat, t_next, second, second ? d_cur[i] : 0.0, d);
+        if (!second) d_cur[i] = d;
+    }
+}
+
+// Token-space forms of the two kernels above: the network reads bf16 patch rows and writes bf16 token rows, so the fp32 images
+// md_edm_sampler_input -> md_patchify and md_unpatchify -> md_edm_heun_update pass through memory are skipped; the fp64 sampler state
+// is the only image-shaped tensor.  A work item is one 8-element (16-byte) segment of one token row; items are ordered
+// (b, ti, segment, tj) with tj fastest, so the lanes of a wave walk along w: the fp64 rows are read / written along w and every
+// lane moves its bf16 segment as one 16-byte piece (VEC; rows that are no multiple of 8 wide, or a misaligned base, go element
+// by element).
+struct tok_item {
+    int64_t b, row;     // sample, token row b * T + ti * gw + tj
+    int ti, tj, e0;     // grid position, first element of the segment
+};
+__device__ __forceinline__ tok_item tok_item_of(int64_t i, int gh, int gw, int nseg) {
+    tok_item t;
+    t.tj = (int)(i % gw);
+    const int64_t r = i / gw;
+    t.e0 = (int)(r % nseg) * 8;
+    const int64_t bt = r / nseg;
+    t.ti = (int)(bt % gh);
+    t.b = bt / gh;
+    t.row = (t.b * gh + t.ti) * gw + t.tj;
+    return t;
+}
+
+// patches[row, c*p*p + ph*p + pw] = bf16(c_in * float(x[b, c, ti*p+ph, tj*p+pw]));  rows [B*T, 2*B*T) repeat them when dup
+template <bool VEC>
+__global__ __launch_bounds__(256) void sampler_patchify_kernel(const double* x, bf16* out, int64_t B, int C, int H, int W, int p,
+                                                               float sigma, float sigma_data, int dup) {
+    const float c_in = sampler_c_in(sigma, sigma_data);
+    const int gh = H / p, gw = W / p, pp = p * p, pv = C * pp, nseg = (pv + 7) / 8;
+    const int64_t rows = B * gh * gw, total = rows * nseg;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const tok_item t = tok_item_of(i, gh, gw, nseg);
+        U128 v;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int e = t.e0 + j;
+            if (!VEC && e >= pv) break;
+            const int c = e / pp, ph = (e / p) % p, pw = e % p;
+            const bf16 r = f2bf(sampler_net_in(c_in, x[((t.b * C + c) * H + t.ti * p + ph) * W + t.tj * p + pw]));
+            if (VEC) {
+                v.e[j] = r;
+            } else {
+                out[t.row * pv + e] = r;
+                if (dup) out[(rows + t.row) * pv + e] = r;
+            }
         }
-        const double D = (double)(c_skip * (float)xi + c_out * f);
-        const double d = (xi - D) / t_in;
-        const double xh = x_hat[i];
-        if (!second) {
-            d_cur[i] = d;
-            x_next[i] = xh + (t_next - t_hat) * d;
-        } else {
-            x_next[i] = xh + (t_next - t_hat) * (0.5 * d_cur[i] + 0.5 * d);
+        if (VEC) {
+            st_bf16x8(out + t.row * pv + t.e0, v.h);
+            if (dup) st_bf16x8(out + (rows + t.row) * pv + t.e0, v.h);
         }
     }
 }
+
+// F[b, c, ti*p+ph, tj*p+pw] = tok[row, (ph*p + pw)*C + c] (the unconditional half: row + B*T), then heun_element on that pixel
+template <bool VEC>
+__global__ __launch_bounds__(256) void heun_update_tok_kernel(const double* x_hat, const double* x_in, const bf16* tok, double* d_cur,
+                                                              double* x_next, int64_t B, int C, int H, int W, int p, float cfg,
+                                                              int has_uncond, double t_in, double t_hat, double t_next,
+                                                              float sigma_data, int second) {
+    float c_skip, c_out;
+    heun_coef(t_in, sigma_data, c_skip, c_out);
+    const int gh = H / p, gw = W / p, pv = C * p * p, nseg = (pv + 7) / 8;
+    const int64_t rows = B * gh * gw, total = rows * nseg;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const tok_item t = tok_item_of(i, gh, gw, nseg);
+        const bf16* fc = tok + t.row * pv + t.e0;
+        const bf16* fu = fc + rows * pv;
+        U128 vc, vu;
+        if (VEC) {
+            vc.h = ld_bf16x8(fc);
+            if (has_uncond) vu.h = ld_bf16x8(fu);
+        }
+        int64_t pix[8];
+        double xi[8], xh[8], dp[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {          // every load of the item before its first store (x_next may alias x_in / x_hat)
+            const int e = t.e0 + j;
+            if (!VEC && e >= pv) break;
+            const int c = e % C, pw = (e / C) % p, ph = e / (C * p);
+            pix[j] = ((t.b * C + c) * H + t.ti * p + ph) * W + t.tj * p + pw;
+            xi[j] = x_in[pix[j]];
+            xh[j] = x_hat[pix[j]];
+            dp[j] = second ? d_cur[pix[j]] : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (!VEC && t.e0 + j >= pv) break;
+            float f = bf2f(VEC ? vc.e[j] : fc[j]);
+            if (has_uncond) f = cfg_combine(f, bf2f(VEC ? vu.e[j] : fu[j]), cfg);
+            double d;
+            x_next[pix[j]] = heun_element(xi[j], xh[j], f, c_skip, c_out, t_in, t_hat, t_next, second, dp[j], d);
+            if (!second) d_cur[pix[j]] = d;
+        }
+    }
+}
+
+inline bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
 
 }  // namespace
 
@@ -276,6 +387,39 @@ extern "C" int md_edm_heun_update(const double* x_hat, const double* x_in, const
     if (!x_hat || !x_in || !F || !d_cur || !x_next || n <= 0 || t_in <= 0) return MD_BAD_ARG;
     hipLaunchKernelGGL(heun_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_hat, x_in, F, d_cur, x_next, n, cfg, has_uncond, t_in,
                        t_hat, t_next, sigma_data, second);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_edm_sampler_patchify(const double* x, void* patches_bf16, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p,
+                                       float sigma, float sigma_data, int32_t duplicate, hipStream_t st) {
+    if (!x || !patches_bf16 || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p) return MD_BAD_ARG;
+    const int pv = C * p * p;
+    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
+    if (pv % 8 == 0 && aligned16(patches_bf16))
+        hipLaunchKernelGGL(sampler_patchify_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x, (bf16*)patches_bf16, B, C, H, W, p,
+                           sigma, sigma_data, duplicate);
+    else
+        hipLaunchKernelGGL(sampler_patchify_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x, (bf16*)patches_bf16, B, C, H, W, p,
+                           sigma, sigma_data, duplicate);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_edm_heun_update_tok(const double* x_hat, const double* x_in, const void* tok_bf16, double* d_cur, double* x_next,
+                                      int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg, int32_t has_uncond, double t_in,
+                                      double t_hat, double t_next, float sigma_data, int32_t second, hipStream_t st) {
+    if (!x_hat || !x_in || !tok_bf16 || !d_cur || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
+        t_in <= 0)
+        return MD_BAD_ARG;
+    const int pv = C * p * p;
+    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
+    if (pv % 8 == 0 && aligned16(tok_bf16))
+        hipLaunchKernelGGL(heun_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, (const bf16*)tok_bf16, d_cur,
+                           x_next, B, C, H, W, p, cfg, has_uncond, t_in, t_hat, t_next, sigma_data, second);
+    else
+        hipLaunchKernelGGL(heun_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, (const bf16*)tok_bf16, d_cur,
+                           x_next, B, C, H, W, p, cfg, has_uncond, t_in, t_hat, t_next, sigma_data, second);
     MD_LAUNCH_CHECK();
     return 0;
 }

@@ -105,6 +105,7 @@ class DiT(nn.Module):
         self._engine: Optional[DiTEngine] = None
         self._flat = None
         self._shadow_version = -1
+        self._shadow_epoch = 0       # times the bf16 shadow was rewritten (never reset): what a cached Conditioning is valid for
         self._grad_anchor = None
         self._build_and_init()
 
@@ -243,11 +244,19 @@ class DiT(nn.Module):
         if force or ver != self._shadow_version:
             hip.check(hip.lib().md_cast_f32_bf16(f["p"].data_ptr(), f["s"].data_ptr(), f["total"], None,
                                                  torch.cuda.current_stream().cuda_stream), "md_cast_f32_bf16")
-            self._shadow_version = ver
+            self._shadow_written(ver)
 
     def mark_shadow_fresh(self) -> None:
         """Called by the fused optimiser, which writes the masters AND the shadow in one pass."""
-        self._shadow_version = self._param_version()
+        self._shadow_written(self._param_version())
+
+    def _shadow_written(self, ver: int) -> None:
+        """The bf16 weights changed: (parameter version, rewrite count) is the engine's weight version.  The count also catches the
+        writers that bypass the parameters' version counters (refresh_shadow(force=True) after a write through `.data`)."""
+        self._shadow_version = ver
+        self._shadow_epoch += 1
+        if self._engine is not None:
+            self._engine.weights_version = (ver, self._shadow_epoch)
 
     @property
     def engine(self) -> DiTEngine:
@@ -267,7 +276,24 @@ class DiT(nn.Module):
                 p.grad = f["G"][spec.name]
 
     # ------------------------------------------------------------------------------------------ forward
-    def forward_without_cfg(self, x, t, y, mask_ratio: float = 0, mask_noise: Optional[torch.Tensor] = None, **kwargs):
+    @staticmethod
+    def _caption_input(y):
+        yin = y.detach()
+        if yin.dtype not in (torch.float16, torch.float32):
+            yin = yin.float()
+        return yin.contiguous()
+
+    @torch.no_grad()
+    def encode_condition(self, y):
+        """Everything the network derives from the captions alone, computed once (DiTEngine.encode_condition): hold the result and
+        pass it as `forward_without_cfg(..., cond=...)` to sample many seeds / steps for one prompt set.  Inference only; valid
+        until the weights change (a stale one raises)."""
+        self._ensure_flat()
+        self.refresh_shadow()
+        return self._engine.encode_condition(self._caption_input(y))
+
+    def forward_without_cfg(self, x, t, y, mask_ratio: float = 0, mask_noise: Optional[torch.Tensor] = None, cond=None, **kwargs):
+        """cond: an encode_condition(y) result for these captions (y is then not read)."""
         self._ensure_flat()
         self.refresh_shadow()
         self.h = x.shape[-2] // self.patch_size
@@ -277,14 +303,13 @@ class DiT(nn.Module):
             mask_noise = torch.rand(B, self.h * self.w, device=x.device)     # same draw as utils.py:390
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         xin = x.detach().to(torch.float32).contiguous()
-        yin = y.detach()
-        if yin.dtype not in (torch.float16, torch.float32):
-            yin = yin.float()
-        yin = yin.contiguous()
+        yin = self._caption_input(y) if y is not None else None
         if need_grad:
+            if cond is not None:
+                raise RuntimeError("cond is inference-only: call under torch.no_grad() (or with frozen parameters)")
             sample, mask = _DiTFunction.apply(self, self._grad_anchor, xin, t.detach(), yin, float(mask_ratio), mask_noise)
         else:
-            tape = self._engine.forward(xin, t.detach(), yin, mask_ratio=float(mask_ratio), mask_noise=mask_noise)
+            tape = self._engine.forward(xin, t.detach(), yin, mask_ratio=float(mask_ratio), mask_noise=mask_noise, cond=cond)
             sample, mask = self._engine.sample_image(tape), tape.mask
         return {"sample": sample, "mask": mask}
 

@@ -91,6 +91,24 @@ class _Arena:
         return self.buf[off:off + nbytes].view(dtype).view(*shape)
 
 
+class Conditioning:
+    """What a forward pass derives from the captions alone (DiTEngine.encode_condition): computed once per prompt set and handed to
+    every network evaluation of a sampling run (`forward(..., cond=...)`).
+      kv      {block name: (kv [B*Lc, 2*hx] with K normalised and V raw -- the buffer _block_fwd leaves after md_qkln_fwd,
+               head-major normalised K [B, H, Lc, hd] or None)} for every mixer and backbone block
+      pooled  [B, D]: LayerNorm+GELU output of pooled_y_emb_process, the input of its fc2 (fc2 itself runs per evaluation, its
+               epilogue adds the timestep embedding: c is rounded once, as in the uncached pass)
+      B, Lc, head_major, version (DiTEngine.weights_version it was computed from), nbytes"""
+
+    def __init__(self, B, Lc, head_major, version, pooled, kv):
+        self.B, self.Lc, self.head_major, self.version, self.pooled, self.kv = B, Lc, head_major, version, pooled, kv
+
+    @property
+    def nbytes(self) -> int:
+        ts = [self.pooled] + [t for pair in self.kv.values() for t in pair if t is not None]
+        return sum(t.numel() * t.element_size() for t in ts)
+
+
 def _p(t):
     return None if t is None else t.data_ptr()
 
@@ -156,6 +174,7 @@ class DiTEngine:
         # accumulator, no cast + clear pass afterwards.  (g_lo, g_hi, gbf address, {fp32 address: elements stored} of this step)
         self.wgrad_bf16 = None
         self.fuse_swiglu_bwd = os.environ.get("MD_FUSE_SWIGLU_BWD", "1") != "0"   # A/B: 0 = data gradient + md_swiglu_bwd as two launches
+        self.weights_version = 0    # set by the owning DiT whenever it rewrites the bf16 shadow: a Conditioning is valid for one version
         self.cu_limit_fn = None     # data parallelism: callable() -> CUs the persistent GEMM may occupy right now (0 = all): the
         #                             Trainer leaves the CUs of RCCL's channels free while a collective is in flight
 
@@ -631,7 +650,25 @@ class DiTEngine:
         return dxin
 
     # ------------------------------------------------------------------------------------------ DiT block
-    def _block_fwd(self, bp: BlockPlan, x, ycond, B, S, Lc, gc, mod_all=None):
+    def _kv_linear_fwd(self, n, ycond, Mc, hx, d):
+        """Packed [K | V] rows of a block's cross-attention from the caption tokens (utils.py:172-176)."""
+        kv = self.empty(Mc, 2 * hx)
+        self.lin_fwd(ycond, n + ".cross_attn.kv_linear", kv, Mc, 2 * hx, d)
+        return kv
+
+    def _k_norm_fwd(self, kv, Mc, hx, Lc):
+        """QK-LayerNorm of the K half of kv: in place, or (head-major layout) to a [B, H, Lc, hd] buffer.  Returns (rstd, that buffer or None)."""
+        rk = self.empty(Mc, dtype=F32)
+        if self.qk_head_major:
+            kn = self.empty(Mc, hx)
+            self._qkln_fwd_hm(kv.data_ptr(), Mc, 2 * hx, 0, hx, kn, Lc, rk.data_ptr())
+            return rk, kn
+        self._qkln_fwd(kv.data_ptr(), Mc, 2 * hx, 0, hx, rk.data_ptr())
+        return rk, None
+
+    def _block_fwd(self, bp: BlockPlan, x, ycond, B, S, Lc, gc, mod_all=None, kv=None):
+        """kv: this block's entry of Conditioning.kv -- the caption-side projection and its K-LayerNorm are then skipped (ycond is not
+        read; inference only: the tape holds no K rstd for a backward)."""
         L, st, cfg = self.L, self._st(), self.cfg
         d, h, hx, f = bp.dim, bp.attn_hidden, bp.xattn_hidden, bp.ffn_hidden
         M, Mc, D = B * S, B * Lc, cfg.dim
@@ -666,21 +703,25 @@ class DiTEngine:
         # head-major: the raw q is dead once md_qkln_fwd_hm has read it -- it is staged in the buffer attention then writes o into
         t.q2 = t.o2 if self.qk_head_major else self.empty(M, hx)
         self.lin_fwd(t.xn2, n + ".cross_attn.q_linear", t.q2, M, hx, d)
-        t.kv = self.empty(Mc, 2 * hx)
-        self.lin_fwd(ycond, n + ".cross_attn.kv_linear", t.kv, Mc, 2 * hx, d)
+        if kv is None:
+            t.kv = self._kv_linear_fwd(n, ycond, Mc, hx, d)
+        else:
+            t.kv, t.k2n = kv
+            t.rk2 = None
         t.rq2 = self.empty(M, dtype=F32)
-        t.rk2 = self.empty(Mc, dtype=F32)
         t.lse2 = self.empty(B, bp.xheads, S, dtype=F32)
         if self.qk_head_major:
-            t.q2n, t.k2n = self.empty(M, hx), self.empty(Mc, hx)        # normalised q [B, H, S, hd], k [B, H, Lc, hd]
+            t.q2n = self.empty(M, hx)                                   # normalised q [B, H, S, hd] (k: [B, H, Lc, hd])
             self._qkln_fwd_hm(t.q2.data_ptr(), M, hx, 0, hx, t.q2n, S, t.rq2.data_ptr())
-            self._qkln_fwd_hm(t.kv.data_ptr(), Mc, 2 * hx, 0, hx, t.k2n, Lc, t.rk2.data_ptr())
+            if kv is None:
+                t.rk2, t.k2n = self._k_norm_fwd(t.kv, Mc, hx, Lc)
             ax = self.attn_args(t.q2n.data_ptr(), t.k2n.data_ptr(), t.kv.data_ptr() + 2 * hx, t.o2, t.lse2, B, bp.xheads, S, Lc,
                                 0, 0, 2 * hx, hx, hm_qk=True)
         else:
-            t.q2n = t.k2n = None
+            t.q2n = None
             self._qkln_fwd(t.q2.data_ptr(), M, hx, 0, hx, t.rq2.data_ptr())
-            self._qkln_fwd(t.kv.data_ptr(), Mc, 2 * hx, 0, hx, t.rk2.data_ptr())
+            if kv is None:
+                t.rk2, t.k2n = self._k_norm_fwd(t.kv, Mc, hx, Lc)
             ax = self.attn_args(t.q2.data_ptr(), t.kv.data_ptr(), t.kv.data_ptr() + 2 * hx, t.o2, t.lse2, B, bp.xheads, S, Lc,
                                 hx, 2 * hx, 2 * hx, hx)
         self._attn_fwd(ax)
@@ -965,8 +1006,8 @@ class DiTEngine:
         hip.check(self.L.md_splitk_reduce(self.ws.data_ptr(), dgc_f32.data_ptr(), B, D, D, 0, ks, 1, 1, self._st()), "md_splitk_reduce")
 
     # ------------------------------------------------------------------------------------------ small MLPs (Mlp with norm)
-    def _mlp_norm_fwd(self, pre, xin, rows, cin, rps, res=None):
-        """fc2(LN(gelu(fc1(x)))) (utils.py:63-68); optional residual add on the output.  Returns (out, tape)."""
+    def _mlp_norm_hidden(self, pre, xin, rows, cin, rps):
+        """The first half of _mlp_norm_fwd: tape with hn = gelu(LN(fc1(x))), the input of fc2."""
         D = self.cfg.dim
         t = Tape()
         t.xin = xin
@@ -975,12 +1016,22 @@ class DiTEngine:
         t.hn = self.empty(rows, D)
         t.st = self.empty(2, rows, dtype=F32)
         self.ln_fwd(self.ln_args(t.h, pre + ".norm", t.hn, rows, D, mean=t.st[0], rstd=t.st[1], act=hip.ACT_GELU_TANH, rps=rps))
+        return t
+
+    def _mlp_norm_out(self, pre, hn, rows, res=None):
+        """The second half: fc2(hn), optional residual add in the epilogue."""
+        D = self.cfg.dim
         out = self.empty(rows, D)
         if res is None:
-            self.lin_fwd(t.hn, pre + ".fc2", out, rows, D, D)
+            self.lin_fwd(hn, pre + ".fc2", out, rows, D, D)
         else:
-            self.lin_fwd(t.hn, pre + ".fc2", out, rows, D, D, mode=hip.EPI_RESIDUAL, res=res)
-        return out, t
+            self.lin_fwd(hn, pre + ".fc2", out, rows, D, D, mode=hip.EPI_RESIDUAL, res=res)
+        return out
+
+    def _mlp_norm_fwd(self, pre, xin, rows, cin, rps, res=None):
+        """fc2(LN(gelu(fc1(x)))) (utils.py:63-68); optional residual add on the output.  Returns (out, tape)."""
+        t = self._mlp_norm_hidden(pre, xin, rows, cin, rps)
+        return self._mlp_norm_out(pre, t.hn, rows, res), t
 
     def _mlp_norm_bwd(self, pre, t, dout, rows, cin, rps, need_dx):
         D = self.cfg.dim
@@ -998,31 +1049,56 @@ class DiTEngine:
         return dx
 
     # ------------------------------------------------------------------------------------------ whole model
-    def forward(self, x_img: torch.Tensor, t_in: torch.Tensor, y: torch.Tensor, *, mask_ratio: float = 0.0,
+    def forward(self, x_img: Optional[torch.Tensor], t_in: torch.Tensor, y: Optional[torch.Tensor] = None, *, mask_ratio: float = 0.0,
                 mask_noise: Optional[torch.Tensor] = None, in_scale: Optional[torch.Tensor] = None,
-                y_rowscale: Optional[torch.Tensor] = None, record_tape: bool = False, arena: bool = False) -> Tape:
+                y_rowscale: Optional[torch.Tensor] = None, record_tape: bool = False, arena: bool = False,
+                cond: Optional[Conditioning] = None, patches: Optional[torch.Tensor] = None) -> Tape:
         """x_img f32 [B,C,H,W] (multiplied by in_scale[b] if given), t_in f32 [B], y f16|f32 [B,(1,)L,Dc]
         (rows multiplied by y_rowscale[b] if given).  Returns the tape; tape.out_tok is the network output for the
         kept tokens, bf16 [B*Tk, p*p*C].
         record_tape: a backward() will follow — keep every block's activations (inference passes drop them as they go).
         arena: additionally place the tape in the fixed-address arena (needs `use_arena`; the caller promises forward ->
         backward strictly in turn).  Both are explicit arguments: torch disables grad mode inside autograd.Function.forward,
-        so probing torch.is_grad_enabled() here would never see a training pass."""
-        cfg, L, st = self.cfg, self.L, self._st()
-        B = x_img.shape[0]
-        C, H, W, p = cfg.in_channels, x_img.shape[-2], x_img.shape[-1], cfg.patch_size
-        T, D, Dm = (H // p) * (W // p), cfg.dim, cfg.patch_mixer_dim
-        assert T == cfg.tokens, "input resolution does not match the model's position table"
-        Lc, Dc = y.shape[-2], y.shape[-1]
-        assert x_img.dtype == F32 and x_img.is_contiguous() and y.is_contiguous() and y.dtype in (torch.float16, F32)
+        so probing torch.is_grad_enabled() here would never see a training pass.
+        cond: the result of encode_condition() for these captions -- the caption stream and every block's kv_linear / K-LayerNorm
+        are skipped and the cached buffers used instead (y is not read and may be None).
+        patches: bf16 [B*T, patch_vec] patch rows as md_patchify writes them -- used in place of patchifying x_img (which may be
+        None: the latent grid is then the model's input_size).  cond and patches are inference-only."""
+        cfg = self.cfg
+        if cond is not None or patches is not None:
+            if record_tape or arena or mask_ratio > 0:
+                raise RuntimeError("cond / patches are inference-only: they cannot be combined with record_tape, arena or mask_ratio > 0")
+        if patches is not None:
+            assert patches.dtype == BF16 and patches.is_contiguous() and patches.dim() == 2 and patches.shape[1] == cfg.patch_vec
+            B, rem = divmod(patches.shape[0], cfg.tokens)
+            assert rem == 0 and B > 0, "patches must hold whole samples of the model's token grid"
+            H, W = (x_img.shape[-2], x_img.shape[-1]) if x_img is not None else (cfg.input_size, cfg.input_size)
+        else:
+            assert x_img.dtype == F32 and x_img.is_contiguous()
+            B, H, W = x_img.shape[0], x_img.shape[-2], x_img.shape[-1]
+        assert (H // cfg.patch_size) * (W // cfg.patch_size) == cfg.tokens, "input resolution does not match the model's position table"
+        if cond is not None:
+            if cond.B != B:
+                raise RuntimeError(f"conditioning mismatch: encoded for batch {cond.B}, the input has batch {B}")
+            if y is not None and y.shape[-2] != cond.Lc:
+                raise RuntimeError(f"conditioning mismatch: encoded for caption length {cond.Lc}, y has {y.shape[-2]}")
+            if cond.version != self.weights_version:
+                raise RuntimeError(f"conditioning mismatch: encoded with weight version {cond.version}, the weights are now at "
+                                   f"{self.weights_version} (encode_condition again after the weights change)")
+            if cond.head_major != self.qk_head_major:
+                raise RuntimeError("conditioning mismatch: encoded with another q / k layout (qk_head_major)")
+            Lc, Dc, ydt = cond.Lc, 0, ""
+        else:
+            assert y.is_contiguous() and y.dtype in (torch.float16, F32)
+            Lc, Dc, ydt = y.shape[-2], y.shape[-1], str(y.dtype)
         grad_pass = self.use_arena and arena and record_tape
         self._record = record_tape or self.keep_last_tape
         if grad_pass:
-            self._tape_arena.begin((B, H, W, Lc, Dc, float(mask_ratio), str(y.dtype)))
+            self._tape_arena.begin((B, H, W, Lc, Dc, float(mask_ratio), ydt))
             self._arena = self._tape_arena
         ok = False
         try:
-            tp = self._forward(x_img, t_in, y, mask_ratio, mask_noise, in_scale, y_rowscale)
+            tp = self._forward(x_img, t_in, y, mask_ratio, mask_noise, in_scale, y_rowscale, cond, patches, B, H, W, Lc)
             ok = True
             return tp
         finally:
@@ -1030,35 +1106,11 @@ class DiTEngine:
                 self._tape_arena.end(ok)
             self._arena = None
 
-    def _forward(self, x_img, t_in, y, mask_ratio, mask_noise, in_scale, y_rowscale) -> Tape:
+    def _caption_fwd(self, y, y_rowscale, B, Lc, tp) -> torch.Tensor:
+        """Caption projection + caption block (dit.py:482-483) and the token mean the pooled MLP reads: everything that depends on
+        the captions alone up to there.  Activations go to tp (ycap, yproj, y0, cb, y2, ymean); returns y2 [B*Lc, D]."""
         cfg, L, st = self.cfg, self.L, self._st()
-        B = x_img.shape[0]
-        C, H, W, p = cfg.in_channels, x_img.shape[-2], x_img.shape[-1], cfg.patch_size
-        T, D, Dm = (H // p) * (W // p), cfg.dim, cfg.patch_mixer_dim
-        Lc, Dc = y.shape[-2], y.shape[-1]
-        seg = self.before_segment if self.before_segment is not None else (lambda key: None)
-        seg("rest")
-        tp = Tape()
-        tp.arena = self._arena is not None
-        tp.B, tp.T, tp.Lc, tp.H, tp.W = B, T, Lc, H, W
-        # ---- patch embedding (+ pos), dit.py:479
-        tp.patches = self.empty(B * T, cfg.patch_vec)
-        hip.check(L.md_patchify(x_img.data_ptr(), _p(in_scale), tp.patches.data_ptr(), B, C, H, W, p, st), "patchify")
-        tok = self.empty(B * T, D)
-        self._gemm(A=tp.patches.data_ptr(), B=self.S["x_embedder.proj.weight"].data_ptr(), C=tok.data_ptr(),
-                   bias=self.P["x_embedder.proj.bias"].data_ptr(), M=B * T, N=D, K=cfg.patch_vec, lda=cfg.patch_vec,
-                   ldb=cfg.patch_vec, ldc=D, batch=1, ksplit=1, a_kcontig=1, b_kcontig=1, mode=hip.EPI_STORE_BF16, act=0, alpha=1.0)
-        tp.tok = tok
-        # ---- timestep embedding, dit.py:480
-        tp.tfreq = self.empty(B, 512)
-        t_f = t_in if (t_in.dtype == F32 and t_in.numel() == B and t_in.is_contiguous()) else t_in.to(F32).expand(B).contiguous()
-        hip.check(L.md_timestep_embed(t_f.data_ptr(), tp.tfreq.data_ptr(), B, 512, st), "timestep_embed")
-        tp.t_pre = self.empty(B, D)
-        tp.t_h = self.empty(B, D)
-        self.lin_fwd(tp.tfreq, "t_embedder.mlp.0", tp.t_h, B, D, 512, act=hip.ACT_GELU_TANH, C2=tp.t_pre)
-        temb = self.empty(B, D)
-        self.lin_fwd(tp.t_h, "t_embedder.mlp.2", temb, B, D, D)
-        # ---- caption projection + caption block, dit.py:482-483
+        D, Dc = cfg.dim, y.shape[-1]
         Mc = B * Lc
         tp.ycap = self.empty(Mc, Dc)
         hip.check(L.md_cast_rows_bf16(y.data_ptr(), 0 if y.dtype == torch.float16 else 1, tp.ycap.data_ptr(), Mc, Dc,
@@ -1090,10 +1142,83 @@ class DiTEngine:
         y2 = self.empty(Mc, D)
         self.lin_fwd(cb.a, "y_emb_preprocess.mlp.w3", y2, Mc, D, fc, mode=hip.EPI_RESIDUAL, res=y1)
         tp.cb, tp.y2 = cb, y2
-        # ---- pooled caption -> condition vector c = t_emb + Mlp(mean(y)), dit.py:484-485
         tp.ymean = self.empty(B, D)
         hip.check(L.md_mean_tokens(y2.data_ptr(), tp.ymean.data_ptr(), B, Lc, D, st), "mean_tokens")
-        c, tp.pool = self._mlp_norm_fwd("pooled_y_emb_process", tp.ymean, B, D, 1, res=temb)
+        return y2
+
+    def _map_y_fwd(self, y2, Mc, tp) -> torch.Tensor:
+        """Caption tokens in the patch mixer's width (patch_mixer_map_y, dit.py:489-493; only with has_maps)."""
+        D, Dm = self.cfg.dim, self.cfg.patch_mixer_dim
+        tp.y_ln = self.empty(Mc, D)
+        tp.st_y = self.empty(2, Mc, dtype=F32)
+        self.ln_fwd(self.ln_args(y2, "patch_mixer_map_y.0", tp.y_ln, Mc, D, mean=tp.st_y[0], rstd=tp.st_y[1], rps=tp.Lc))
+        ym = self.empty(Mc, Dm)
+        self.lin_fwd(tp.y_ln, "patch_mixer_map_y.1", ym, Mc, Dm, D)
+        return ym
+
+    def encode_condition(self, y: torch.Tensor) -> Conditioning:
+        """The caption-only part of the forward pass, once (inference: nothing is kept for a backward): caption stream, pooled
+        hidden, patch_mixer_map_y and, for every block, kv_linear + the QK-LayerNorm of K -- the same launches on the same operands
+        as in _forward / _block_fwd, so a pass with `cond=` gives the bits of a pass without.  y as in forward()."""
+        cfg = self.cfg
+        assert y.is_contiguous() and y.dtype in (torch.float16, F32)
+        Lc = y.shape[-2]
+        B = y.numel() // (Lc * y.shape[-1])
+        Mc, D = B * Lc, cfg.dim
+        seg = self.before_segment if self.before_segment is not None else (lambda key: None)
+        seg("rest")
+        tp = Tape()
+        tp.Lc = Lc
+        y2 = self._caption_fwd(y, None, B, Lc, tp)
+        pooled = self._mlp_norm_hidden("pooled_y_emb_process", tp.ymean, B, D, 1).hn
+        ym = self._map_y_fwd(y2, Mc, tp) if (cfg.use_patch_mixer and cfg.has_maps) else y2
+        kv = {}
+        for blocks, ycond in ((self.mixer, ym), (self.backbone, y2)):
+            for bp in blocks:
+                seg(bp.name)
+                k = self._kv_linear_fwd(bp.name, ycond, Mc, bp.xattn_hidden, bp.dim)
+                kv[bp.name] = (k, self._k_norm_fwd(k, Mc, bp.xattn_hidden, Lc)[1])
+        return Conditioning(B, Lc, self.qk_head_major, self.weights_version, pooled, kv)
+
+    def _forward(self, x_img, t_in, y, mask_ratio, mask_noise, in_scale, y_rowscale, cond, patches, B, H, W, Lc) -> Tape:
+        cfg, L, st = self.cfg, self.L, self._st()
+        C, p = cfg.in_channels, cfg.patch_size
+        T, D, Dm = (H // p) * (W // p), cfg.dim, cfg.patch_mixer_dim
+        seg = self.before_segment if self.before_segment is not None else (lambda key: None)
+        seg("rest")
+        tp = Tape()
+        tp.arena = self._arena is not None
+        tp.B, tp.T, tp.Lc, tp.H, tp.W = B, T, Lc, H, W
+        # ---- patch embedding (+ pos), dit.py:479
+        if patches is None:
+            tp.patches = self.empty(B * T, cfg.patch_vec)
+            hip.check(L.md_patchify(x_img.data_ptr(), _p(in_scale), tp.patches.data_ptr(), B, C, H, W, p, st), "patchify")
+        else:
+            tp.patches = patches
+        tok = self.empty(B * T, D)
+        self._gemm(A=tp.patches.data_ptr(), B=self.S["x_embedder.proj.weight"].data_ptr(), C=tok.data_ptr(),
+                   bias=self.P["x_embedder.proj.bias"].data_ptr(), M=B * T, N=D, K=cfg.patch_vec, lda=cfg.patch_vec,
+                   ldb=cfg.patch_vec, ldc=D, batch=1, ksplit=1, a_kcontig=1, b_kcontig=1, mode=hip.EPI_STORE_BF16, act=0, alpha=1.0)
+        tp.tok = tok
+        # ---- timestep embedding, dit.py:480
+        tp.tfreq = self.empty(B, 512)
+        t_f = t_in if (t_in.dtype == F32 and t_in.numel() == B and t_in.is_contiguous()) else t_in.to(F32).expand(B).contiguous()
+        hip.check(L.md_timestep_embed(t_f.data_ptr(), tp.tfreq.data_ptr(), B, 512, st), "timestep_embed")
+        tp.t_pre = self.empty(B, D)
+        tp.t_h = self.empty(B, D)
+        self.lin_fwd(tp.tfreq, "t_embedder.mlp.0", tp.t_h, B, D, 512, act=hip.ACT_GELU_TANH, C2=tp.t_pre)
+        temb = self.empty(B, D)
+        self.lin_fwd(tp.t_h, "t_embedder.mlp.2", temb, B, D, D)
+        # ---- caption projection + caption block, dit.py:482-483; pooled caption -> condition vector c = t_emb + Mlp(mean(y)),
+        # dit.py:484-485.  With `cond` everything up to the input of the pooled MLP's fc2 comes from the cache.
+        Mc = B * Lc
+        if cond is None:
+            y2 = self._caption_fwd(y, y_rowscale, B, Lc, tp)
+            tp.pool = self._mlp_norm_hidden("pooled_y_emb_process", tp.ymean, B, D, 1)
+            pooled = tp.pool.hn
+        else:
+            y2, pooled = None, cond.pooled
+        c = self._mlp_norm_out("pooled_y_emb_process", pooled, B, res=temb)
         tp.c = c
         gc = self.empty(B, D)
         hip.check(L.md_act_fwd(c.data_ptr(), gc.data_ptr(), B * D, hip.ACT_GELU_TANH, st), "act_fwd")
@@ -1107,11 +1232,7 @@ class DiTEngine:
                                      pos=pos, pos_rows=T, rps=T))
             x = self.empty(B * T, Dm)
             self.lin_fwd(tp.xin_ln, "patch_mixer_map_xin.1", x, B * T, Dm, D)
-            tp.y_ln = self.empty(Mc, D)
-            tp.st_y = self.empty(2, Mc, dtype=F32)
-            self.ln_fwd(self.ln_args(y2, "patch_mixer_map_y.0", tp.y_ln, Mc, D, mean=tp.st_y[0], rstd=tp.st_y[1], rps=Lc))
-            ym = self.empty(Mc, Dm)
-            self.lin_fwd(tp.y_ln, "patch_mixer_map_y.1", ym, Mc, Dm, D)
+            ym = self._map_y_fwd(y2, Mc, tp) if cond is None else None
         else:
             # Identity maps (patch_mixer_dim == dim, dit.py:389-392): x = tok + pos
             x = self.empty(B * T, D)
@@ -1128,7 +1249,7 @@ class DiTEngine:
         tp.mixer = []
         for bp in self.mixer:
             seg(bp.name)
-            x, bt = self._block_fwd(bp, x, ym, B, T, Lc, gc, mod_all)
+            x, bt = self._block_fwd(bp, x, ym, B, T, Lc, gc, mod_all, kv=cond.kv[bp.name] if cond is not None else None)
             if self._record:
                 tp.mixer.append(bt)
         # ---- masking, dit.py:495-504
@@ -1161,7 +1282,7 @@ class DiTEngine:
         tp.blocks = []
         for bp in self.backbone:
             seg(bp.name)
-            x, bt = self._block_fwd(bp, x, y2, B, Tk, Lc, gc, mod_all)
+            x, bt = self._block_fwd(bp, x, y2, B, Tk, Lc, gc, mod_all, kv=cond.kv[bp.name] if cond is not None else None)
             if self._record:
                 tp.blocks.append(bt)
         # ---- final layer, dit.py:513

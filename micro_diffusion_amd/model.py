@@ -8,6 +8,7 @@ Sampling (`edm_sampler_loop` / `generate`) is inference-only glue around the sam
 from __future__ import annotations
 
 from functools import partial
+import os
 import warnings
 from types import SimpleNamespace
 from typing import Optional
@@ -30,6 +31,11 @@ def text_encoder_embedding_format(enc: str):
     if enc == "DeepFloyd/t5-v1_1-xxl":
         return 120, 4096
     raise ValueError(f"Please specify the sequence and embedding size of {enc} encoder")
+
+
+def sampler_cache_enabled(flag: Optional[bool] = None) -> bool:
+    """The `cond_cache` argument of the sampler: None reads the environment variable MD_SAMPLER_CACHE (default off)."""
+    return os.environ.get("MD_SAMPLER_CACHE", "0") == "1" if flag is None else bool(flag)
 
 
 class DistLoss:
@@ -218,17 +224,23 @@ class LatentDiffusion(nn.Module):
 
     # ---------------------------------------------------------------------------------------- sampling (inference glue)
     @torch.no_grad()
-    def edm_sampler_loop(self, x, y, steps: Optional[int] = None, cfg: float = 1.0, fused: Optional[bool] = None, **kwargs):
+    def edm_sampler_loop(self, x, y, steps: Optional[int] = None, cfg: float = 1.0, fused: Optional[bool] = None,
+                         cond_cache: Optional[bool] = None, **kwargs):
         """Heun 2nd-order EDM sampler, fp64 state (model.py:231-297).  `fused` (None = whenever possible) selects the loop whose
         per-step arithmetic runs in two fused HIP kernels; False keeps the reference's tensor-op formulation (generic forward
-        functions, S_churn > 0)."""
+        functions, S_churn > 0).
+        `cond_cache` (None = the environment variable MD_SAMPLER_CACHE, default off): encode the captions once for the whole run
+        and step in token space (see _edm_sampler_fused); needs the fused loop.  Results are bit-identical to the uncached loop."""
         ec = self.edm_config
         can_fuse = ec.S_churn == 0 and not kwargs and x.is_cuda
+        cond_cache = sampler_cache_enabled(cond_cache)
+        if cond_cache and (fused is False or not can_fuse):
+            raise RuntimeError("cond_cache needs the fused sampler: S_churn == 0, no extra forward arguments, CUDA tensors")
         if fused is None:
             fused = can_fuse
         if fused:
             assert can_fuse, "the fused sampler needs S_churn == 0 and no extra forward arguments"
-            return self._edm_sampler_fused(x, y, steps, cfg)
+            return self._edm_sampler_fused(x, y, steps, cfg, cond_cache)
         fwd = partial(self.dit.forward, cfg=cfg) if cfg > 1.0 else self.dit.forward
         n = ec.num_steps if steps is None else steps
         idx = torch.arange(n, dtype=torch.float64, device=x.device)
@@ -251,10 +263,13 @@ class LatentDiffusion(nn.Module):
         return x_next.to(torch.float32)
 
     @torch.no_grad()
-    def _edm_sampler_fused(self, x, y, steps: Optional[int], cfg: float):
+    def _edm_sampler_fused(self, x, y, steps: Optional[int], cfg: float, cond_cache: bool = False):
         """The same Heun loop (S_churn = 0, the reference's setting: x_hat = x_cur) with everything around the network evaluations in
         two fused HIP kernels: md_edm_sampler_input (c_in scaling + guidance batch doubling) and md_edm_heun_update (guidance
-        combine + preconditioning + fp64 Euler / Heun update)."""
+        combine + preconditioning + fp64 Euler / Heun update).
+        cond_cache: the captions (doubled under guidance) are encoded once (dit.encode_condition) and every evaluation runs
+        md_edm_sampler_patchify -> engine.forward(patches=, cond=) -> md_edm_heun_update_tok on the token output: no caption-side
+        work per evaluation and no fp32 image between the fp64 state and the network's bf16 rows."""
         ec, L, st = self.edm_config, hip.lib(), torch.cuda.current_stream().cuda_stream
         n = ec.num_steps if steps is None else steps
         idx = torch.arange(n, dtype=torch.float64)
@@ -265,29 +280,50 @@ class LatentDiffusion(nn.Module):
         B, numel = x.shape[0], x.numel()
         x_cur = (x.to(torch.float64) * t_steps[0]).contiguous()
         x_nxt, d_cur = torch.empty_like(x_cur), torch.empty_like(x_cur)
-        net_in = torch.empty((2 * B if guided else B,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
         y2 = torch.cat([y, torch.zeros_like(y)], 0) if guided else y
+        Bn, dup = (2 * B if guided else B), (1 if guided else 0)
+        if cond_cache:
+            dit = self.dit
+            C, H, W, p = x.shape[1], x.shape[2], x.shape[3], dit.patch_size
+            cond = dit.encode_condition(y2)
+            patches = torch.empty(Bn * (H // p) * (W // p), dit.config.patch_vec, device=x.device, dtype=torch.bfloat16)
+        else:
+            net_in = torch.empty((Bn,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
 
         def network(xs, sigma):
-            hip.check(L.md_edm_sampler_input(xs.data_ptr(), net_in.data_ptr(), numel, float(sigma), ec.sigma_data, 1 if guided else 0, st),
+            """The network output for state xs at noise level sigma: the fp32 image F, or (cond_cache) the bf16 token rows."""
+            c_noise = float(np.log(np.float32(sigma)) / 4)
+            if cond_cache:
+                hip.check(L.md_edm_sampler_patchify(xs.data_ptr(), patches.data_ptr(), B, C, H, W, p, float(sigma), ec.sigma_data, dup, st),
+                          "md_edm_sampler_patchify")
+                t = torch.full((Bn,), c_noise, device=x.device, dtype=torch.float32)
+                return dit._engine.forward(None, t, None, cond=cond, patches=patches).out_tok
+            hip.check(L.md_edm_sampler_input(xs.data_ptr(), net_in.data_ptr(), numel, float(sigma), ec.sigma_data, dup, st),
                       "md_edm_sampler_input")
-            t = torch.full((1,), float(np.log(np.float32(sigma)) / 4), device=x.device, dtype=torch.float32)
+            t = torch.full((1,), c_noise, device=x.device, dtype=torch.float32)
             return self.dit.forward_without_cfg(net_in, t, y2, 0)["sample"].contiguous()
+
+        def update(F, x_in, t_in, t_hat, t_next, second):
+            """x_nxt (and, on the first half-step, d_cur) from x_cur, the evaluated state x_in and the network output F."""
+            if cond_cache:
+                hip.check(L.md_edm_heun_update_tok(x_cur.data_ptr(), x_in.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(),
+                                                   B, C, H, W, p, float(cfg), dup, t_in, t_hat, t_next, ec.sigma_data, second, st),
+                          "md_edm_heun_update_tok")
+            else:
+                hip.check(L.md_edm_heun_update(x_cur.data_ptr(), x_in.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(), numel,
+                                               float(cfg), dup, t_in, t_hat, t_next, ec.sigma_data, second, st), "md_edm_heun_update")
         for i, (t_cur, t_next) in enumerate(zip(t_steps[:-1], t_steps[1:])):
-            F = network(x_cur, t_cur)
-            hip.check(L.md_edm_heun_update(x_cur.data_ptr(), x_cur.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(), numel,
-                                           float(cfg), 1 if guided else 0, t_cur, t_cur, t_next, ec.sigma_data, 0, st), "md_edm_heun_update")
+            update(network(x_cur, t_cur), x_cur, t_cur, t_cur, t_next, 0)
             if i < n - 1:
-                F = network(x_nxt, t_next)
-                hip.check(L.md_edm_heun_update(x_cur.data_ptr(), x_nxt.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(), numel,
-                                               float(cfg), 1 if guided else 0, t_next, t_cur, t_next, ec.sigma_data, 1, st), "md_edm_heun_update")
+                update(network(x_nxt, t_next), x_nxt, t_next, t_cur, t_next, 1)
             x_cur, x_nxt = x_nxt, x_cur
         return x_cur.to(torch.float32)
 
     @torch.no_grad()
     def generate(self, prompt: Optional[list] = None, tokenized_prompts=None, attention_mask=None, guidance_scale: float = 5.0,
-                 num_inference_steps: int = 30, seed: Optional[int] = None, return_only_latents: bool = False, **kwargs):
-        """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353)."""
+                 num_inference_steps: int = 30, seed: Optional[int] = None, return_only_latents: bool = False,
+                 cond_cache: Optional[bool] = None, **kwargs):
+        """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache: as in edm_sampler_loop."""
         assert prompt or tokenized_prompts is not None, "Must provide either prompt or tokenized prompts"
         device = next(self.dit.parameters()).device
         gen = torch.Generator(device=device)
@@ -300,7 +336,7 @@ class LatentDiffusion(nn.Module):
         emb = self.text_encoder.encode(tokenized_prompts.to(device),
                                        attention_mask=attention_mask.to(device) if attention_mask is not None else None)[0]
         latents = torch.randn((len(emb), self.dit.in_channels, self.latent_res, self.latent_res), device=device, generator=gen)
-        latents = self.edm_sampler_loop(latents, emb, num_inference_steps, cfg=guidance_scale)
+        latents = self.edm_sampler_loop(latents, emb, num_inference_steps, cfg=guidance_scale, cond_cache=cond_cache)
         if return_only_latents:
             return latents
         image = self.vae.decode((latents / self.latent_scale).to(DATA_TYPES[self.dtype])).sample
