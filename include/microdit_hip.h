@@ -439,6 +439,36 @@ int md_adamw_step_guarded(const md_adamw_args* a, const int32_t* guard, hipStrea
 int md_adamw_step_ranges_guarded(const md_adamw_args* a, const int64_t* flat_off, const int64_t* count, int32_t n_ranges,
                                  const int32_t* guard, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------- model diagnostics */
+/* (Added under ABI 6: new symbols only.)  Two reductions over what a training step already leaves on the device, in the style of
+ * md_tensor_stats_*: no float atomic, fp64 sums in an order that is a function of the shape alone (two calls on the same inputs
+ * give identical bits), no allocation, no synchronisation.  Every output is ADDED TO: the caller zeroes the tables when a
+ * reporting interval starts.
+ *
+ * md_loss_sigma_hist: the EDM loss (models/model.py:181-210: one sigma per sample, log-normal with P_mean / P_std, and the
+ * per-sample loss md_edm_loss(_train) writes) split by noise level.  Sample i goes to bin
+ *   floor((logf(sigma[i]) - log_lo) * nbins / (log_hi - log_lo)),  fp32, clamped to [0, nbins - 1]
+ * (a sigma outside [exp(log_lo), exp(log_hi)) lands in an end bin): sum[bin] += loss_per_sample[i], count[bin] += 1.  A sample
+ * whose loss is not finite is counted in nonfinite[0] and left out of sum and count (the policy of md_tensor_stats_*).  One
+ * workgroup; per bin the samples are added in a fixed order.  1 <= nbins <= 64, log_hi > log_lo, B >= 1. */
+int md_loss_sigma_hist(const float* sigma, const float* loss_per_sample, int64_t B, float log_lo, float log_hi, int32_t nbins,
+                       double* sum, int64_t* count, int64_t* nonfinite, hipStream_t stream);
+/* md_moe_route_stats: the state of one expert-choice routing layer (models/dit.py:131-133) from what md_moe_route leaves: slot
+ * [B*S, E] (position in the expert's list, or -1), probs [B*S, ldp] (ldp >= E; columns >= E are padding and are NOT read), gval
+ * [E, B*k].  E <= 16, k <= S.
+ *   cover_hist[c], c = 0 .. E    += number of tokens that exactly c experts took (c entries >= 0 in the token's slot row);
+ *                                   the sum over c of c * cover_hist[c] grows by E * B * k
+ *   fstats[0]                    += sum over tokens of the router entropy -sum_e p ln p (per token in fp32; p == 0 adds 0)
+ *   fstats[1 + e]                += sum over tokens of probs[t, e]        (router marginal)
+ *   fstats[1 + E + e]            += sum of gval[e, 0 .. B*k)              (gate values of the chosen entries)
+ * Two stages in one call: per-workgroup fp64 partials stored into ws (written before it is read: needs no initialisation; 8-byte
+ * aligned; at least md_moe_route_stats_ws_floats(B, S, E) floats, which covers every k), then one wave adds them in ascending
+ * workgroup order.  Integer atomics for cover_hist only.  16-byte loads when E % 4 == 0, ldp % 4 == 0 (B*k % 4 == 0 for gval) and
+ * the bases are 16-byte aligned, element by element otherwise. */
+int md_moe_route_stats_ws_floats(int64_t B, int64_t S, int32_t E, int64_t* out);
+int md_moe_route_stats(const int32_t* slot, const float* probs, int64_t ldp, const float* gval, int64_t B, int64_t S, int32_t E,
+                       int32_t k, float* ws, int64_t ws_floats, int64_t* cover_hist, double* fstats, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,16 @@ def names_target(cfg: Any, target: str) -> bool:
     return False
 
 
+def diagnostics_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The Trainer's diagnostics switches from the `misc` section, all off unless the config sets them:
+    misc.diagnostics_interval (batches between reports), misc.loss_by_sigma_bins (0 = no loss-by-sigma histogram),
+    misc.moe_routing_monitor (expert-choice routing statistics on the report batches)."""
+    misc = cfg.get("misc") or {}
+    return {"diagnostics_interval": int(misc.get("diagnostics_interval", 0) or 0),
+            "loss_by_sigma_bins": int(misc.get("loss_by_sigma_bins", 0) or 0),
+            "moe_routing": bool(misc.get("moe_routing_monitor", False))}
+
+
 def locate(target: str):
     native = TARGETS.get(target, target)
     if native is None:

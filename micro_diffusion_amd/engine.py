@@ -146,6 +146,10 @@ class DiTEngine:
         self.keep_last_tape = False        # tests: keep the most recent forward's tape in self.last_tape (per-block activations)
         self.last_tape = None
         self.route_override = None         # tests: {block name: top-k token indices [B, E, k]} replacing the router's choice
+        # Routing diagnostics (opt-in): a diagnostics.RouteStats; every routed layer then adds its coverage / entropy /
+        # marginals to its row right behind md_moe_route (one md_moe_route_stats call).  None: no launch, no buffer.  Its tables and
+        # workspace are its own allocations: arena sizes, addresses and the tape are those of an unarmed pass.
+        self.route_stats = None
         self.ws = torch.empty(128 << 20, device=self.dev, dtype=F32)  # 512 MiB split-K workspace
         # Fixed-address activation memory (opt-in: the caller must run forward -> backward strictly in turn, as the Trainer
         # does; two forwards in flight would share the tape arena).
@@ -763,6 +767,8 @@ class DiTEngine:
                                      t.gval.data_ptr(), t.slot.data_ptr(), st), "moe_route")
             if self.route_override is not None and n in self.route_override:
                 self._override_routing(t, self.route_override[n], B, S, E, k)
+            if self.route_stats is not None:    # after the injection: the statistics describe the routing the layer runs with
+                self.route_stats.record(n, t.slot, t.probs, ldl, t.gval, B, S, k)
             t.xin = self.empty(E, Bk, d)
             hip.check(L.md_gather_rows(t.xm3.data_ptr(), d, t.rowidx.data_ptr(), t.xin.data_ptr(), d, E * Bk, d, st), "gather")
             t.hpre = self.empty(E, Bk, f)         # the pre-activation -- or, with moe_cache_dact, gelu'(pre-activation): nothing but

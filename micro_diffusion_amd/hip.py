@@ -232,6 +232,10 @@ _sig("md_det_ws_floats", I32, I64, I64, I64, I64, POINTER(c_int64))
 _sig("md_ln_bwd_det", POINTER(LnArgs), POINTER(LnBwdArgs), P, I64, P)
 _sig("md_gate_bwd_det", P, P, P, I64, P, P, I64, I64, I64, I64, I64, P, I64, P)
 _sig("md_colsum_det", P, I32, I64, P, I64, I64, P, I64, P)
+# model diagnostics: loss by noise level, expert-choice routing statistics (md_moe_route_stats_ws_floats sizes the workspace)
+_sig("md_loss_sigma_hist", P, P, I64, F32, F32, I32, P, P, P, P)
+_sig("md_moe_route_stats_ws_floats", I64, I64, I32, POINTER(c_int64))
+_sig("md_moe_route_stats", P, P, I64, P, I64, I64, I32, I32, P, I64, P, P, P)
 
 
 def exported_symbols():

@@ -74,6 +74,9 @@ class LatentDiffusion(nn.Module):
                                      rho=7, S_churn=0, S_min=0, S_max=float("inf"), S_noise=1)
         self.train_mask_ratio = train_mask_ratio
         self.eval_mask_ratio = 0.0
+        # Loss by noise level (opt-in): a diagnostics.LossBySigma; every EDM loss evaluation then adds its per-sample
+        # losses to the train or eval table (one md_loss_sigma_hist launch).  None: no launch, no buffer.
+        self.loss_by_sigma = None
         assert self.train_mask_ratio >= 0, "Masking ratio must be non-negative!"
         self.randn_like = torch.randn_like
         self.latent_scale = self.vae.config.scaling_factor
@@ -384,6 +387,8 @@ def _edm_forward(model: LatentDiffusion, anchor, x, y, rnd, eps, mnoise, mask_ra
                                 loss.data_ptr(), None if dtok is None else dtok.data_ptr(), B, tape.Tk, C, H, W, dit.patch_size,
                                 ec.sigma_data, st), "md_edm_loss")
     tape.loss_per_sample = lps
+    if model.loss_by_sigma is not None:
+        model.loss_by_sigma.accumulate(sigma, lps, dit.training)
     return loss.reshape(()), tape, dtok
 
 

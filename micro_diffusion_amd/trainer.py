@@ -19,7 +19,10 @@ configs/*.yaml), re-designed for one process per GPU with RCCL over xGMI:
   * training health (opt-in): `Trainer(monitor_interval=N)` takes per-tensor gradient / weight statistics every N batches
     (md_tensor_stats_*: Composer's OptimizerMonitor, configs/*.yaml callbacks.optimizer_monitor) and
     `FusedAdamW(skip_nonfinite=True)` turns a step whose gradient norm is not finite into a no-op on the device (md_step_guard:
-    the reference's NaNCatcher, but before the update reaches the weights and without a host sync).
+    the reference's NaNCatcher, but before the update reaches the weights and without a host sync);
+  * model diagnostics (opt-in): `Trainer(diagnostics_interval=N, loss_by_sigma_bins=n, moe_routing=True)` keeps the EDM loss split by
+    noise level and, on every N-th batch, the token coverage / entropy / marginals of every expert-choice router
+    (diagnostics.py, md_loss_sigma_hist / md_moe_route_stats); `Trainer.diagnostics()` reads them.
 """
 from __future__ import annotations
 
@@ -36,6 +39,7 @@ import torch
 import torch.distributed as dist
 
 from . import hip
+from . import diagnostics as mddiag
 
 
 def parse_batches(v) -> int:
@@ -793,8 +797,12 @@ class Trainer:
     def __init__(self, model, optimizer: FusedAdamW, schedule: Optional[LRSchedule] = None, clip_norm: float = 0.0,
                  microbatch_size: int = 256, process_group=None, log: Optional[Callable[[dict], None]] = None,
                  exchange: str = "auto", single_rank_exchange: bool = False, dp_mode: str = "auto", transport: str = "auto",
-                 monitor_interval: int = 0):
-        """monitor_interval: N > 0 takes the per-tensor statistics (collect_tensor_stats) on every batch whose number is a multiple
+                 monitor_interval: int = 0, diagnostics_interval: int = 0, loss_by_sigma_bins: int = 0, moe_routing: bool = False):
+        """diagnostics_interval / loss_by_sigma_bins / moe_routing (all off by default: no launch, no buffer): see diagnostics().
+        loss_by_sigma_bins = n > 0 arms model.loss_by_sigma (n bins over P_mean +- 3 P_std in ln sigma): every microbatch of every
+        step adds to the histogram.  moe_routing arms the engine's route_stats for the microbatches of the batches whose number is a
+        multiple of diagnostics_interval (tables zeroed when armed, accumulated over the step's microbatches).
+        monitor_interval: N > 0 takes the per-tensor statistics (collect_tensor_stats) on every batch whose number is a multiple
         of N, between the gradient exchange and the optimiser pass; 0 = never (no launch, no buffer).
         dp_mode: "sharded" (reduce-scatter + sharded AdamW + all-gather of the bf16 weights, the reference's SHARD_GRAD_OP;
         default for N > 1 over RCCL) or "allreduce" (every rank runs the whole optimiser pass); "auto" also honours the
@@ -837,6 +845,11 @@ class Trainer:
         self.monitor_interval = int(monitor_interval)
         self._stats_plans: Dict[str, _StatsPlan] = {}
         self._stats_last = None
+        self.diagnostics_interval = int(diagnostics_interval)
+        if loss_by_sigma_bins > 0 and model.loss_by_sigma is None:
+            ec = model.edm_config
+            model.loss_by_sigma = mddiag.LossBySigma(int(loss_by_sigma_bins), ec.P_mean, ec.P_std)
+        self._route_stats = mddiag.RouteStats(model.dit.engine) if moe_routing else None     # armed by train_step on report batches
         self.log = log
         self._win: List[tuple] = []
         self.measure_comm = False          # bench.py: event pairs around GradSync.finish() (exposed exchange time)
@@ -854,6 +867,10 @@ class Trainer:
         starts = list(range(0, n, mb))
         total = torch.empty(1, device=model.dit.flat_buffers()["p"].device)       # a fresh scalar per step: callers keep them
         hip.check(hip.lib().md_fill_zero(total.data_ptr(), 4, torch.cuda.current_stream().cuda_stream), "md_fill_zero")
+        if (self._route_stats is not None and self.diagnostics_interval > 0
+                and (self.batches_seen + 1) % self.diagnostics_interval == 0):
+            self._route_stats.zero()
+            model.dit.engine.route_stats = self._route_stats
         for i, s in enumerate(starts):
             part = {k: (v[s:s + mb] if torch.is_tensor(v) and v.shape[0] == n else v) for k, v in batch.items()}
             self.sync.active = (i == len(starts) - 1)
@@ -863,6 +880,8 @@ class Trainer:
             model.train_microbatch(part, grad_scale=w, loss_accum=total, accum_weight=w)
         self.sync.active = False
         self.sync.end_backward()
+        if self._route_stats is not None:
+            model.dit.engine.route_stats = None
         if self.measure_comm:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()                                  # behind the last backward kernel on the compute stream
@@ -964,6 +983,34 @@ class Trainer:
             out[f"nonfinite/grad/{n}"] = int(gi[t])
             out[f"l2_norm/param/{n}"] = math.sqrt(float(pf[0, t]))
         out["l2_norm/grad/global"] = math.sqrt(float(gf[0].sum())) * sc
+        return out
+
+    # ------------------------------------------------------------------ model diagnostics (loss by sigma, expert-choice routing)
+    def diagnostics(self, tables=("train", "eval"), routing: bool = True) -> dict:
+        """What the model diagnostics hold, as plain Python numbers, and ZERO what was read (synchronises; with more than one rank a
+        collective over the exchange's process group: every rank calls it with the same arguments and gets the same numbers -- the
+        ranks' tables are gathered and added in rank order, diagnostics.gather_rank_diagnostics).  Keys:
+          loss_by_sigma/{train,eval}/ln_sigma_edges, /count, /mean_loss, /nonfinite      for every table named in `tables`
+                                              (needs loss_by_sigma_bins; everything accumulated since the table was last read)
+          moe/<block>/coverage, /dropped_frac, /router_entropy, /expert_prob_mean, /expert_gate_mean   for every routed layer
+                                              (needs moe_routing; the microbatches of the last batch that was a multiple of
+                                              diagnostics_interval, absent before the first)."""
+        out, model, pg = {}, self.model, self.sync.pg
+        lbs = getattr(model, "loss_by_sigma", None)
+        dev = model.dit.flat_buffers()["p"].device
+        if lbs is not None:
+            for which in tables:
+                cnt, sm = lbs.tables(which, dev)
+                c, s = mddiag.gather_rank_diagnostics(cnt, sm, pg)
+                lbs.zero(which)
+                out.update(mddiag.format_loss_by_sigma(which, lbs.edges, s.tolist(), c[:-1].tolist(), int(c[-1])))
+        rs = self._route_stats
+        if routing and rs is not None:
+            c, s = mddiag.gather_rank_diagnostics(rs.cover_hist.reshape(-1), rs.fstats.reshape(-1), pg)
+            rs.zero()
+            c, s = c.view(len(rs.names), -1), s.view(len(rs.names), -1)
+            for i, name in enumerate(rs.names):
+                out.update(mddiag.format_route_stats(name, c[i].tolist(), s[i].tolist()))
         return out
 
     def exposed_comm_ms(self, last: int = 0) -> Optional[float]:

@@ -93,8 +93,11 @@ def train(cfg: dict):
     loader = mdcfg.instantiate(ds["train"], image_size=ds["image_size"], batch_size=ds["train_batch_size"] // world,
                                cap_seq_size=seq, cap_emb_dim=emb, cap_drop_prob=ds["cap_drop_prob"])
     monitor_kw = dict(monitor_interval=monitor_every) if monitor_every > 0 else {}
+    # Model diagnostics, all off by default: misc.diagnostics_interval, misc.loss_by_sigma_bins, misc.moe_routing_monitor
+    diag_kw = {k: v for k, v in mdcfg.diagnostics_options(cfg).items() if v}
+    diag_every = diag_kw.get("diagnostics_interval", 0)
     trainer = Trainer(model, opt, sched, clip_norm=clip, microbatch_size=int(cfg["trainer"]["device_train_microbatch_size"]),
-                      **monitor_kw)
+                      **monitor_kw, **diag_kw)
     save_every = parse_batches(cfg["trainer"].get("save_interval", "0ba"))
     folder = cfg["trainer"].get("save_folder")
     log_every = int(cfg.get("misc", {}).get("log_interval", 10))
@@ -132,11 +135,20 @@ def train(cfg: dict):
             stats = trainer.tensor_stats()                         # a collective-free read (every rank holds the same table)
             if rank == 0:
                 print(json.dumps({"batch": step + 1, "optimizer_monitor": stats}), flush=True)
+        if diag_every > 0 and (step + 1) % diag_every == 0:
+            diag = trainer.diagnostics(tables=("train",))          # every rank: the tables are gathered, all ranks get the same numbers
+            if rank == 0:
+                print(json.dumps({"batch": step + 1, "diagnostics": diag}), flush=True)
         if eval_loader is not None and (step + 1) % eval_every == 0:
             trainer.consolidate()                                  # sharded optimiser: whole fp32 weights / EMA on every rank
+            if model.loss_by_sigma is not None:
+                model.loss_by_sigma.zero("eval")                   # the eval histogram describes this pass alone
             ev = evaluate(model, eval_loader, world, microbatch=trainer.microbatch_size, opt=opt)
+            line = {"batch": step + 1, "metrics/eval/loss": ev}
+            if model.loss_by_sigma is not None:
+                line.update(trainer.diagnostics(tables=("eval",), routing=False))
             if rank == 0:
-                print(json.dumps({"batch": step + 1, "metrics/eval/loss": ev}), flush=True)
+                print(json.dumps(line), flush=True)
         if world > 1 and check_every and (step + 1) % check_every == 0 and not trainer.replicas_in_sync():
             raise RuntimeError(f"data-parallel replicas diverged at batch {step + 1} (weight checksums differ across ranks)")
         if not skip_nonfinite and not torch.isfinite(loss):        # NaNCatcher (callbacks.py:47-64)
