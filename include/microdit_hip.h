@@ -365,6 +365,21 @@ int md_edm_sampler_patchify(const double* x, void* patches_bf16, int64_t B, int3
 int md_edm_heun_update_tok(const double* x_hat, const double* x_in, const void* tok_bf16, double* d_cur, double* x_next, int64_t B,
                            int32_t C, int32_t H, int32_t W, int32_t p, float cfg, int32_t has_uncond, double t_in, double t_hat,
                            double t_next, float sigma_data, int32_t second, hipStream_t stream);
+/* One step of a linear multistep solver on the denoised value (Euler, DPM-Solver++(2M); opt-in, the Heun loop above is the default):
+ *   F = Fu + cfg * (Fc - Fu) (has_uncond; else F = Fc);  den = c_skip(t_in) * (float)x_in + c_out(t_in) * F  (fp32, as md_edm_heun_update);
+ *   x_next = a * x_in + b * (c1 * den - c2 * hist);  hist = den.
+ * hist is one f64 buffer of the state's shape: read only when c2 != 0, always written.  x_next may alias x_in.  The host computes a, b,
+ * c1, c2 in fp64 (Euler: a = t_next / t_in, b = 1 - a, c1 = 1, c2 = 0; 2M: a = t_next / t_in, b = -expm1(-h), c1 = 1 + 1/(2r), c2 = 1/(2r)).
+ * md_edm_solver_update_tok reads F from the network's bf16 token output as md_edm_heun_update_tok does: the bits of
+ * md_unpatchify(ids_restore = NULL) followed by md_edm_solver_update. */
+int md_edm_solver_update(const double* x_in, const float* F, double* hist, double* x_next, int64_t n, float cfg, int32_t has_uncond,
+                         double t_in, float sigma_data, double a, double b, double c1, double c2, hipStream_t stream);
+int md_edm_solver_update_tok(const double* x_in, const void* tok_bf16, double* hist, double* x_next, int64_t B, int32_t C, int32_t H,
+                             int32_t W, int32_t p, float cfg, int32_t has_uncond, double t_in, float sigma_data, double a, double b,
+                             double c1, double c2, hipStream_t stream);
+/* Stochastic churn (model.py:254-258): x_hat = x + coef * noise in fp64, one fma per element; coef = sqrt(t_hat^2 - t_cur^2) * S_noise
+ * from the host.  x_hat may alias x. */
+int md_edm_churn(const double* x, const double* noise, double* x_hat, int64_t n, double coef, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------- optimiser */
 /* Sum of squares of a gradient buffer (fp32, or bf16 when g_is_bf16), deterministic: workgroup b of a fixed grid writes

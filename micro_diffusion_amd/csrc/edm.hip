@@ -171,14 +171,27 @@ __device__ __forceinline__ void heun_coef(double t_in, float sigma_data, float& 
     c_out = sg * sigma_data / sqrtf(den);
 }
 __device__ __forceinline__ float cfg_combine(float fc, float fu, float cfg) { return fmaf(cfg, fc - fu, fu); }
+// D = c_skip * float(x_in) + c_out * F in fp32 (model.py:177), widened to the fp64 of the state.
+__device__ __forceinline__ double sampler_denoised(double xi, float f, float c_skip, float c_out) {
+    return (double)fmaf(c_skip, (float)xi, c_out * f);
+}
 // Returns x_next of one element; d receives the slope of this evaluation (the first half-step stores it as d_cur), d_prev is the
 // d_cur the second half-step reads.  Values in, values out: the callers load before they store, so x_next may alias x_in or x_hat.
 __device__ __forceinline__ double heun_element(double xi, double xh, float f, float c_skip, float c_out, double t_in, double t_hat,
                                                double t_next, int second, double d_prev, double& d) {
-    const double D = (double)fmaf(c_skip, (float)xi, c_out * f);
+    const double D = sampler_denoised(xi, f, c_skip, c_out);
     d = (xi - D) / t_in;
     if (!second) return fma(t_next - t_hat, d, xh);
     return fma(t_next - t_hat, fma(0.5, d, 0.5 * d_prev), xh);
+}
+
+// One step of a linear multistep solver on the denoised value (Euler, DPM-Solver++(2M)): x_next = a * x_in + b * (c1 * den - c2 * hist);
+// den goes back to the caller, which stores it as the next step's hist.  hist is 0.0 when c2 == 0 (the callers do not load it then),
+// so c1 * den - c2 * hist is c1 * den exactly and a stale or non-finite history buffer never reaches x_next.
+__device__ __forceinline__ double solver_element(double xi, float f, float c_skip, float c_out, double a, double b, double c1, double c2,
+                                                 double hist, double& den) {
+    den = sampler_denoised(xi, f, c_skip, c_out);
+    return fma(a, xi, b * fma(c1, den, -(c2 * hist)));
 }
 
 __global__ __launch_bounds__(256) void sampler_input_kernel(const double* x, float* out, int64_t n, float sigma, float sigma_data, int dup) {
@@ -203,6 +216,27 @@ __global__ __launch_bounds__(256) void heun_update_kernel(const double* x_hat, c
         x_next[i] = heun_element(xi, x_hat[i], f, c_skip, c_out, t_in, t_hat, t_next, second, second ? d_cur[i] : 0.0, d);
         if (!second) d_cur[i] = d;
     }
+}
+
+__global__ __launch_bounds__(256) void solver_update_kernel(const double* x_in, const float* F, double* hist, double* x_next, int64_t n,
+                                                            float cfg, int has_uncond, double t_in, float sigma_data, double a, double b,
+                                                            double c1, double c2) {
+    float c_skip, c_out;
+    heun_coef(t_in, sigma_data, c_skip, c_out);
+    const bool use_hist = c2 != 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double xi = x_in[i];
+        float f = F[i];
+        if (has_uncond) f = cfg_combine(f, F[n + i], cfg);
+        double den;
+        x_next[i] = solver_element(xi, f, c_skip, c_out, a, b, c1, c2, use_hist ? hist[i] : 0.0, den);
+        hist[i] = den;
+    }
+}
+
+// x_hat = x + coef * noise: the stochastic churn of model.py:258, coef = sqrt(t_hat^2 - t_cur^2) * S_noise from the host.
+__global__ __launch_bounds__(256) void churn_kernel(const double* x, const double* noise, double* x_hat, int64_t n, double coef) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x_hat[i] = fma(coef, noise[i], x[i]);
 }
 
 // Token-space forms of the two kernels above: the network reads bf16 patch rows and writes bf16 token rows, so the fp32 images
@@ -296,6 +330,48 @@ __global__ __launch_bounds__(256) void heun_update_tok_kernel(const double* x_ha
             double d;
             x_next[pix[j]] = heun_element(xi[j], xh[j], f, c_skip, c_out, t_in, t_hat, t_next, second, dp[j], d);
             if (!second) d_cur[pix[j]] = d;
+        }
+    }
+}
+
+// The token-space form of solver_update_kernel: F as in heun_update_tok_kernel, then solver_element on that pixel
+template <bool VEC>
+__global__ __launch_bounds__(256) void solver_update_tok_kernel(const double* x_in, const bf16* tok, double* hist, double* x_next, int64_t B,
+                                                                int C, int H, int W, int p, float cfg, int has_uncond, double t_in,
+                                                                float sigma_data, double a, double b, double c1, double c2) {
+    float c_skip, c_out;
+    heun_coef(t_in, sigma_data, c_skip, c_out);
+    const bool use_hist = c2 != 0.0;
+    const int gh = H / p, gw = W / p, pv = C * p * p, nseg = (pv + 7) / 8;
+    const int64_t rows = B * gh * gw, total = rows * nseg;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const tok_item t = tok_item_of(i, gh, gw, nseg);
+        const bf16* fc = tok + t.row * pv + t.e0;
+        const bf16* fu = fc + rows * pv;
+        U128 vc, vu;
+        if (VEC) {
+            vc.h = ld_bf16x8(fc);
+            if (has_uncond) vu.h = ld_bf16x8(fu);
+        }
+        int64_t pix[8];
+        double xi[8], hp[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {          // every load of the item before its first store (x_next may alias x_in)
+            const int e = t.e0 + j;
+            if (!VEC && e >= pv) break;
+            const int c = e % C, pw = (e / C) % p, ph = e / (C * p);
+            pix[j] = ((t.b * C + c) * H + t.ti * p + ph) * W + t.tj * p + pw;
+            xi[j] = x_in[pix[j]];
+            hp[j] = use_hist ? hist[pix[j]] : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (!VEC && t.e0 + j >= pv) break;
+            float f = bf2f(VEC ? vc.e[j] : fc[j]);
+            if (has_uncond) f = cfg_combine(f, bf2f(VEC ? vu.e[j] : fu[j]), cfg);
+            double den;
+            x_next[pix[j]] = solver_element(xi[j], f, c_skip, c_out, a, b, c1, c2, hp[j], den);
+            hist[pix[j]] = den;
         }
     }
 }
@@ -420,6 +496,40 @@ extern "C" int md_edm_heun_update_tok(const double* x_hat, const double* x_in, c
     else
         hipLaunchKernelGGL(heun_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, (const bf16*)tok_bf16, d_cur,
                            x_next, B, C, H, W, p, cfg, has_uncond, t_in, t_hat, t_next, sigma_data, second);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_edm_solver_update(const double* x_in, const float* F, double* hist, double* x_next, int64_t n, float cfg,
+                                    int32_t has_uncond, double t_in, float sigma_data, double a, double b, double c1, double c2,
+                                    hipStream_t st) {
+    if (!x_in || !F || !hist || !x_next || n <= 0 || t_in <= 0) return MD_BAD_ARG;
+    hipLaunchKernelGGL(solver_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_in, F, hist, x_next, n, cfg, has_uncond, t_in, sigma_data,
+                       a, b, c1, c2);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_edm_solver_update_tok(const double* x_in, const void* tok_bf16, double* hist, double* x_next, int64_t B, int32_t C,
+                                        int32_t H, int32_t W, int32_t p, float cfg, int32_t has_uncond, double t_in, float sigma_data,
+                                        double a, double b, double c1, double c2, hipStream_t st) {
+    if (!x_in || !tok_bf16 || !hist || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p || t_in <= 0)
+        return MD_BAD_ARG;
+    const int pv = C * p * p;
+    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
+    if (pv % 8 == 0 && aligned16(tok_bf16))
+        hipLaunchKernelGGL(solver_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_in, (const bf16*)tok_bf16, hist, x_next,
+                           B, C, H, W, p, cfg, has_uncond, t_in, sigma_data, a, b, c1, c2);
+    else
+        hipLaunchKernelGGL(solver_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_in, (const bf16*)tok_bf16, hist, x_next,
+                           B, C, H, W, p, cfg, has_uncond, t_in, sigma_data, a, b, c1, c2);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_edm_churn(const double* x, const double* noise, double* x_hat, int64_t n, double coef, hipStream_t st) {
+    if (!x || !noise || !x_hat || n <= 0) return MD_BAD_ARG;
+    hipLaunchKernelGGL(churn_kernel, dim3(egrid(n)), dim3(256), 0, st, x, noise, x_hat, n, coef);
     MD_LAUNCH_CHECK();
     return 0;
 }

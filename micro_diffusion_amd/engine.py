@@ -108,6 +108,17 @@ class Conditioning:
         ts = [self.pooled] + [t for pair in self.kv.values() for t in pair if t is not None]
         return sum(t.numel() * t.element_size() for t in ts)
 
+    def narrow(self, B: int) -> "Conditioning":
+        """The first B samples as a Conditioning of batch B: views of the same buffers (every buffer is sample-major, so the first B
+        samples are its leading rows), same layout and weight version.  The sampler's guidance interval runs the conditional half of
+        a cache encoded for [captions; zeroed captions] through it."""
+        if not 0 < B <= self.B:
+            raise ValueError(f"cannot narrow a conditioning of batch {self.B} to {B}")
+        if B == self.B:
+            return self
+        kv = {name: (k[:B * self.Lc], None if khm is None else khm[:B * self.Lc]) for name, (k, khm) in self.kv.items()}
+        return Conditioning(B, self.Lc, self.head_major, self.version, self.pooled[:B], kv)
+
 
 def _p(t):
     return None if t is None else t.data_ptr()

@@ -216,6 +216,11 @@ _sig("md_edm_heun_update", P, P, P, P, P, I64, F32, I32, ctypes.c_double, ctypes
 # token-space forms (the cached sampling path): no fp32 image between the fp64 sampler state and the network's bf16 rows
 _sig("md_edm_sampler_patchify", P, P, I64, I32, I32, I32, I32, F32, F32, I32, P)
 _sig("md_edm_heun_update_tok", P, P, P, P, P, I64, I32, I32, I32, I32, F32, I32, ctypes.c_double, ctypes.c_double, ctypes.c_double, F32, I32, P)
+# opt-in sampler solvers: one linear-multistep update (Euler, DPM-Solver++(2M)) in image and token space, and the churn step
+_sig("md_edm_solver_update", P, P, P, P, I64, F32, I32, ctypes.c_double, F32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, P)
+_sig("md_edm_solver_update_tok", P, P, P, P, I64, I32, I32, I32, I32, F32, I32, ctypes.c_double, F32, ctypes.c_double, ctypes.c_double,
+     ctypes.c_double, ctypes.c_double, P)
+_sig("md_edm_churn", P, P, P, I64, ctypes.c_double, P)
 _sig("md_sumsq", P, I32, I64, P, P)
 _sig("md_sumsq_finish", P, I64, P, P)
 _sig("md_checksum_u16", P, I64, P, P)

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from . import dit as model_zoo
 from . import hip
+from . import samplers
 
 DATA_TYPES = {"float16": torch.float16, "bfloat16": torch.bfloat16, "float32": torch.float32}
 
@@ -226,65 +227,92 @@ class LatentDiffusion(nn.Module):
         metric.update(outputs[0])
 
     # ---------------------------------------------------------------------------------------- sampling (inference glue)
+    def _churned_levels(self, t_steps, n):
+        """t_hat of every step (model.py:254-257) from the host-side noise levels: t_cur * (1 + gamma), gamma > 0 inside [S_min, S_max]."""
+        ec = self.edm_config
+        return [t + (min(ec.S_churn / n, np.sqrt(2) - 1) if ec.S_min <= t <= ec.S_max else 0) * t for t in t_steps[:-1]]
+
     @torch.no_grad()
     def edm_sampler_loop(self, x, y, steps: Optional[int] = None, cfg: float = 1.0, fused: Optional[bool] = None,
-                         cond_cache: Optional[bool] = None, **kwargs):
-        """Heun 2nd-order EDM sampler, fp64 state (model.py:231-297).  `fused` (None = whenever possible) selects the loop whose
-        per-step arithmetic runs in two fused HIP kernels; False keeps the reference's tensor-op formulation (generic forward
-        functions, S_churn > 0).
+                         cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, **kwargs):
+        """EDM sampler, fp64 state (model.py:231-297).  `fused` (None = whenever possible) selects the loop whose per-step arithmetic
+        runs in fused HIP kernels; False keeps the reference's tensor-op formulation (generic forward functions).
         `cond_cache` (None = the environment variable MD_SAMPLER_CACHE, default off): encode the captions once for the whole run
-        and step in token space (see _edm_sampler_fused); needs the fused loop.  Results are bit-identical to the uncached loop."""
+        and step in token space (see _edm_sampler_fused); needs the fused loop.  Results are bit-identical to the uncached loop.
+        `sampler`: "heun" (the reference's 2nd-order loop, 2 * steps - 1 network evaluations), "euler" or "dpmpp_2m" (DPM-Solver++(2M),
+        2nd order); the last two take one evaluation per step (samplers.py).  S_churn > 0 is defined for heun and euler.
+        `guidance_interval` = (sigma_lo, sigma_hi): an evaluation at noise level sigma is guided (batch doubled) only while
+        sigma_lo <= sigma <= sigma_hi; outside it the conditional half runs alone.  None: every evaluation is guided when cfg > 1."""
         ec = self.edm_config
-        can_fuse = ec.S_churn == 0 and not kwargs and x.is_cuda
+        samplers.check_sampler(sampler, ec.S_churn)
+        interval = samplers.guidance_interval_bounds(guidance_interval)
+        can_fuse = not kwargs and x.is_cuda
         cond_cache = sampler_cache_enabled(cond_cache)
         if cond_cache and (fused is False or not can_fuse):
-            raise RuntimeError("cond_cache needs the fused sampler: S_churn == 0, no extra forward arguments, CUDA tensors")
+            raise RuntimeError("cond_cache needs the fused sampler: no extra forward arguments, CUDA tensors")
         if fused is None:
             fused = can_fuse
         if fused:
-            assert can_fuse, "the fused sampler needs S_churn == 0 and no extra forward arguments"
-            return self._edm_sampler_fused(x, y, steps, cfg, cond_cache)
+            assert can_fuse, "the fused sampler needs CUDA tensors and no extra forward arguments"
+            return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval)
         fwd = partial(self.dit.forward, cfg=cfg) if cfg > 1.0 else self.dit.forward
+
+        def denoise(xs, sigma):
+            f = fwd if interval is None or interval[0] <= float(sigma) <= interval[1] else self.dit.forward
+            return self.model_forward_wrapper(xs.to(torch.float32), sigma.to(torch.float32), y, f, mask_ratio=0, **kwargs)["sample"].to(torch.float64)
         n = ec.num_steps if steps is None else steps
         idx = torch.arange(n, dtype=torch.float64, device=x.device)
         inv_rho = 1 / ec.rho
         t_steps = (ec.sigma_max ** inv_rho + idx / (n - 1) * (ec.sigma_min ** inv_rho - ec.sigma_max ** inv_rho)) ** ec.rho
         t_steps = torch.cat([t_steps, torch.zeros_like(t_steps[:1])])
+        if sampler != "heun":
+            levels = t_steps.tolist()
+            coef = samplers.solver_coefficients(sampler, levels, self._churned_levels(levels, n))
         x_next = x.to(torch.float64) * t_steps[0]
         for i, (t_cur, t_next) in enumerate(zip(t_steps[:-1], t_steps[1:])):
             x_cur = x_next
             gamma = min(ec.S_churn / n, np.sqrt(2) - 1) if ec.S_min <= t_cur <= ec.S_max else 0
             t_hat = torch.as_tensor(t_cur + gamma * t_cur)
             x_hat = x_cur + (t_hat ** 2 - t_cur ** 2).sqrt() * ec.S_noise * self.randn_like(x_cur)
-            den = self.model_forward_wrapper(x_hat.to(torch.float32), t_hat.to(torch.float32), y, fwd, mask_ratio=0, **kwargs)["sample"].to(torch.float64)
+            den = denoise(x_hat, t_hat)
+            if sampler != "heun":                   # one evaluation per step: x_next = a x_hat + b (c1 D - c2 D_prev)
+                a, b, c1, c2 = coef[i]
+                x_next = a * x_hat + b * (c1 * den - c2 * hist if c2 != 0 else c1 * den)
+                hist = den
+                continue
             d_cur = (x_hat - den) / t_hat
             x_next = x_hat + (t_next - t_hat) * d_cur
             if i < n - 1:
-                den = self.model_forward_wrapper(x_next.to(torch.float32), t_next.to(torch.float32), y, fwd, mask_ratio=0, **kwargs)["sample"].to(torch.float64)
+                den = denoise(x_next, t_next)
                 d_prime = (x_next - den) / t_next
                 x_next = x_hat + (t_next - t_hat) * (0.5 * d_cur + 0.5 * d_prime)
         return x_next.to(torch.float32)
 
     @torch.no_grad()
-    def _edm_sampler_fused(self, x, y, steps: Optional[int], cfg: float, cond_cache: bool = False):
-        """The same Heun loop (S_churn = 0, the reference's setting: x_hat = x_cur) with everything around the network evaluations in
-        two fused HIP kernels: md_edm_sampler_input (c_in scaling + guidance batch doubling) and md_edm_heun_update (guidance
-        combine + preconditioning + fp64 Euler / Heun update).
+    def _edm_sampler_fused(self, x, y, steps: Optional[int], cfg: float, cond_cache: bool = False, sampler: str = "heun", interval=None):
+        """The same loops with everything around the network evaluations in fused HIP kernels: md_edm_sampler_input (c_in scaling +
+        guidance batch doubling) and md_edm_heun_update (guidance combine + preconditioning + fp64 Euler / Heun update) or, for
+        euler / dpmpp_2m, md_edm_solver_update (the same with the linear-multistep update of samplers.solver_coefficients).
+        S_churn > 0: the noise is drawn once per step as in the tensor-op loop and md_edm_churn adds it to the state in place.
         cond_cache: the captions (doubled under guidance) are encoded once (dit.encode_condition) and every evaluation runs
-        md_edm_sampler_patchify -> engine.forward(patches=, cond=) -> md_edm_heun_update_tok on the token output: no caption-side
-        work per evaluation and no fp32 image between the fp64 state and the network's bf16 rows."""
+        md_edm_sampler_patchify -> engine.forward(patches=, cond=) -> md_edm_heun_update_tok / md_edm_solver_update_tok on the token
+        output: no caption-side work per evaluation and no fp32 image between the fp64 state and the network's bf16 rows.
+        interval: evaluations outside it run the conditional half alone (network batch B) on leading-row views of the same buffers."""
         ec, L, st = self.edm_config, hip.lib(), torch.cuda.current_stream().cuda_stream
         n = ec.num_steps if steps is None else steps
         idx = torch.arange(n, dtype=torch.float64)
         inv_rho = 1 / ec.rho
         t_steps = (ec.sigma_max ** inv_rho + idx / (n - 1) * (ec.sigma_min ** inv_rho - ec.sigma_max ** inv_rho)) ** ec.rho
         t_steps = torch.cat([t_steps, torch.zeros(1, dtype=torch.float64)]).tolist()
-        guided = cfg > 1.0
+        heun, churn = sampler == "heun", ec.S_churn > 0
+        t_hats = self._churned_levels(t_steps, n) if churn else t_steps[:-1]
+        levels = [s for i in range(n) for s in ([t_hats[i]] + ([t_steps[i + 1]] if heun and i < n - 1 else []))]
+        guided = any(samplers.is_guided(s, cfg, interval) for s in levels)      # no guided evaluation at all: the cfg = 1 run
         B, numel = x.shape[0], x.numel()
         x_cur = (x.to(torch.float64) * t_steps[0]).contiguous()
         x_nxt, d_cur = torch.empty_like(x_cur), torch.empty_like(x_cur)
         y2 = torch.cat([y, torch.zeros_like(y)], 0) if guided else y
-        Bn, dup = (2 * B if guided else B), (1 if guided else 0)
+        Bn = 2 * B if guided else B
         if cond_cache:
             dit = self.dit
             C, H, W, p = x.shape[1], x.shape[2], x.shape[3], dit.patch_size
@@ -294,20 +322,27 @@ class LatentDiffusion(nn.Module):
             net_in = torch.empty((Bn,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
 
         def network(xs, sigma):
-            """The network output for state xs at noise level sigma: the fp32 image F, or (cond_cache) the bf16 token rows."""
+            """(network output, dup) for state xs at noise level sigma: the fp32 image F, or (cond_cache) the bf16 token rows; dup = 1
+            when the evaluation is guided: the batch is doubled and the output holds the unconditional half behind the conditional."""
             c_noise = float(np.log(np.float32(sigma)) / 4)
+            dup = 1 if guided and samplers.is_guided(sigma, cfg, interval) else 0
+            Be = 2 * B if dup else B
             if cond_cache:
-                hip.check(L.md_edm_sampler_patchify(xs.data_ptr(), patches.data_ptr(), B, C, H, W, p, float(sigma), ec.sigma_data, dup, st),
+                pt = patches if Be == Bn else patches[:B * (H // p) * (W // p)]
+                hip.check(L.md_edm_sampler_patchify(xs.data_ptr(), pt.data_ptr(), B, C, H, W, p, float(sigma), ec.sigma_data, dup, st),
                           "md_edm_sampler_patchify")
-                t = torch.full((Bn,), c_noise, device=x.device, dtype=torch.float32)
-                return dit._engine.forward(None, t, None, cond=cond, patches=patches).out_tok
+                t = torch.full((Be,), c_noise, device=x.device, dtype=torch.float32)
+                return dit._engine.forward(None, t, None, cond=cond.narrow(Be), patches=pt).out_tok, dup
             hip.check(L.md_edm_sampler_input(xs.data_ptr(), net_in.data_ptr(), numel, float(sigma), ec.sigma_data, dup, st),
                       "md_edm_sampler_input")
             t = torch.full((1,), c_noise, device=x.device, dtype=torch.float32)
-            return self.dit.forward_without_cfg(net_in, t, y2, 0)["sample"].contiguous()
+            if Be == Bn:
+                return self.dit.forward_without_cfg(net_in, t, y2, 0)["sample"].contiguous(), dup
+            return self.dit.forward_without_cfg(net_in[:B], t, y, 0)["sample"].contiguous(), dup
 
-        def update(F, x_in, t_in, t_hat, t_next, second):
+        def update(Fd, x_in, t_in, t_hat, t_next, second):
             """x_nxt (and, on the first half-step, d_cur) from x_cur, the evaluated state x_in and the network output F."""
+            F, dup = Fd
             if cond_cache:
                 hip.check(L.md_edm_heun_update_tok(x_cur.data_ptr(), x_in.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(),
                                                    B, C, H, W, p, float(cfg), dup, t_in, t_hat, t_next, ec.sigma_data, second, st),
@@ -315,18 +350,40 @@ class LatentDiffusion(nn.Module):
             else:
                 hip.check(L.md_edm_heun_update(x_cur.data_ptr(), x_in.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(), numel,
                                                float(cfg), dup, t_in, t_hat, t_next, ec.sigma_data, second, st), "md_edm_heun_update")
+
+        def solver_update(Fd, t_in, coef):
+            """x_nxt = a x_cur + b (c1 D - c2 hist), hist = D; d_cur is the history buffer."""
+            F, dup = Fd
+            if cond_cache:
+                hip.check(L.md_edm_solver_update_tok(x_cur.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(), B, C, H, W, p,
+                                                     float(cfg), dup, t_in, ec.sigma_data, *coef, st), "md_edm_solver_update_tok")
+            else:
+                hip.check(L.md_edm_solver_update(x_cur.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(), numel, float(cfg), dup,
+                                                 t_in, ec.sigma_data, *coef, st), "md_edm_solver_update")
+        coefs = None if heun else samplers.solver_coefficients(sampler, t_steps, t_hats)
         for i, (t_cur, t_next) in enumerate(zip(t_steps[:-1], t_steps[1:])):
-            update(network(x_cur, t_cur), x_cur, t_cur, t_cur, t_next, 0)
-            if i < n - 1:
-                update(network(x_nxt, t_next), x_nxt, t_next, t_cur, t_next, 1)
+            t_hat = t_hats[i]
+            if churn:                               # one draw per step, churned or not: the draws of the tensor-op loop
+                noise = self.randn_like(x_cur)
+                if t_hat != t_cur:                  # x_cur becomes x_hat (x_cur itself is not read again)
+                    noise = noise.to(torch.float64).contiguous()
+                    hip.check(L.md_edm_churn(x_cur.data_ptr(), noise.data_ptr(), x_cur.data_ptr(), numel,
+                                             float(np.sqrt(t_hat ** 2 - t_cur ** 2) * ec.S_noise), st), "md_edm_churn")
+            if heun:
+                update(network(x_cur, t_hat), x_cur, t_hat, t_hat, t_next, 0)
+                if i < n - 1:
+                    update(network(x_nxt, t_next), x_nxt, t_next, t_hat, t_next, 1)
+            else:
+                solver_update(network(x_cur, t_hat), t_hat, coefs[i])
             x_cur, x_nxt = x_nxt, x_cur
         return x_cur.to(torch.float32)
 
     @torch.no_grad()
     def generate(self, prompt: Optional[list] = None, tokenized_prompts=None, attention_mask=None, guidance_scale: float = 5.0,
                  num_inference_steps: int = 30, seed: Optional[int] = None, return_only_latents: bool = False,
-                 cond_cache: Optional[bool] = None, **kwargs):
-        """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache: as in edm_sampler_loop."""
+                 cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, **kwargs):
+        """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache, sampler and
+        guidance_interval: as in edm_sampler_loop."""
         assert prompt or tokenized_prompts is not None, "Must provide either prompt or tokenized prompts"
         device = next(self.dit.parameters()).device
         gen = torch.Generator(device=device)
@@ -339,7 +396,8 @@ class LatentDiffusion(nn.Module):
         emb = self.text_encoder.encode(tokenized_prompts.to(device),
                                        attention_mask=attention_mask.to(device) if attention_mask is not None else None)[0]
         latents = torch.randn((len(emb), self.dit.in_channels, self.latent_res, self.latent_res), device=device, generator=gen)
-        latents = self.edm_sampler_loop(latents, emb, num_inference_steps, cfg=guidance_scale, cond_cache=cond_cache)
+        latents = self.edm_sampler_loop(latents, emb, num_inference_steps, cfg=guidance_scale, cond_cache=cond_cache, sampler=sampler,
+                                        guidance_interval=guidance_interval)
         if return_only_latents:
             return latents
         image = self.vae.decode((latents / self.latent_scale).to(DATA_TYPES[self.dtype])).sample

@@ -1,0 +1,88 @@
+"""Solvers of the EDM sampler, host side: names, the noise schedule and the per-step coefficients of the linear-multistep update
+`x_next = a * x + b * (c1 * D - c2 * hist)` that `md_edm_solver_update(_tok)` applies (D: the denoised value of this step's one
+network evaluation, hist: the previous step's D).  Pure Python in fp64: importable without a GPU and without the native library.
+
+  heun      the reference's 2nd-order loop (model.py:231-297), 2 * steps - 1 evaluations; not of this form, it keeps its own kernels
+  euler     1st order, one evaluation per step
+  dpmpp_2m  DPM-Solver++(2M) (Lu et al. 2022, multistep data-prediction form) in the EDM parameterisation (alpha = 1, lambda = -ln sigma):
+            2nd order, one evaluation per step
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Sequence, Tuple
+
+SAMPLERS = ("heun", "euler", "dpmpp_2m")
+CHURN_SAMPLERS = ("heun", "euler")          # the churn of model.py:254-258 needs a solver without history
+
+
+def check_sampler(sampler: str, S_churn: float = 0.0) -> str:
+    if sampler not in SAMPLERS:
+        raise ValueError(f"unknown sampler {sampler!r}: choose one of {', '.join(SAMPLERS)}")
+    if S_churn > 0 and sampler not in CHURN_SAMPLERS:
+        raise ValueError(f"sampler {sampler!r} is deterministic: S_churn > 0 is defined for {', '.join(CHURN_SAMPLERS)} only")
+    return sampler
+
+
+def edm_schedule(steps: int, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0) -> List[float]:
+    """The EDM noise levels t_0 = sigma_max ... t_{steps-1} = sigma_min and a final 0 (model.py:238-243), fp64."""
+    inv = 1.0 / rho
+    t = [(sigma_max ** inv + i / (steps - 1) * (sigma_min ** inv - sigma_max ** inv)) ** rho for i in range(steps)]
+    return t + [0.0]
+
+
+def guidance_interval_bounds(guidance_interval) -> Optional[Tuple[float, float]]:
+    if guidance_interval is None:
+        return None
+    lo, hi = guidance_interval
+    lo, hi = float(lo), float(hi)
+    if math.isnan(lo) or math.isnan(hi) or lo > hi:
+        raise ValueError(f"guidance_interval must be (sigma_lo, sigma_hi) with sigma_lo <= sigma_hi, got {guidance_interval!r}")
+    return lo, hi
+
+
+def is_guided(sigma: float, cfg: float, interval: Optional[Tuple[float, float]]) -> bool:
+    """Whether the evaluation at noise level sigma runs with classifier-free guidance (network batch 2B)."""
+    return cfg > 1.0 and (interval is None or interval[0] <= sigma <= interval[1])
+
+
+def evaluation_sigmas(sampler: str, t_steps: Sequence[float]) -> List[float]:
+    """The noise level of every network evaluation of a run without churn, in order."""
+    out = []
+    for i, (t_cur, t_next) in enumerate(zip(t_steps[:-1], t_steps[1:])):
+        out.append(t_cur)
+        if sampler == "heun" and t_next > 0:
+            out.append(t_next)
+    return out
+
+
+def solver_coefficients(solver: str, t_steps: Sequence[float], t_hat: Optional[Sequence[float]] = None) -> List[Tuple[float, float, float, float]]:
+    """(a, b, c1, c2) of every step i: t_steps[i] -> t_steps[i + 1] (t_steps ends in 0; the step onto 0 returns D itself).
+    t_hat (euler only): the churned noise level each step is evaluated at, in place of t_steps[i]."""
+    if solver not in ("euler", "dpmpp_2m"):
+        raise ValueError(f"no linear-multistep coefficients for sampler {solver!r}")
+    t = [float(v) for v in t_steps]
+    n = len(t) - 1
+    cur = t[:-1] if t_hat is None else [float(v) for v in t_hat]
+    if len(cur) != n:
+        raise ValueError("t_hat needs one entry per step")
+    if solver == "dpmpp_2m" and cur != t[:-1]:
+        raise ValueError("dpmpp_2m carries history across steps: it cannot start a step from a churned noise level")
+    out = []
+    for i in range(n):
+        t_cur, t_next = cur[i], t[i + 1]
+        if t_next == 0.0:                                     # lambda_next = inf: a = 0, b = -expm1(-inf) = 1, no history
+            out.append((0.0, 1.0, 1.0, 0.0))
+            continue
+        a = t_next / t_cur
+        if solver == "euler":
+            out.append((a, 1.0 - a, 1.0, 0.0))
+            continue
+        h = math.log(t_cur) - math.log(t_next)                # lambda_next - lambda_cur
+        b = -math.expm1(-h)
+        if i == 0:
+            out.append((a, b, 1.0, 0.0))
+            continue
+        r = (math.log(t[i - 1]) - math.log(t_cur)) / h         # (lambda_cur - lambda_prev) / h
+        out.append((a, b, 1.0 + 1.0 / (2.0 * r), 1.0 / (2.0 * r)))
+    return out
