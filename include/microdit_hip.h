@@ -484,6 +484,26 @@ int md_moe_route_stats_ws_floats(int64_t B, int64_t S, int32_t E, int64_t* out);
 int md_moe_route_stats(const int32_t* slot, const float* probs, int64_t ldp, const float* gval, int64_t B, int64_t S, int32_t E,
                        int32_t k, float* ws, int64_t ws_floats, int64_t* cover_hist, double* fstats, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------- post-hoc EMA */
+/* (Added under ABI 6: new symbols only.)  Power-function averages of the fp32 masters (Karras et al. 2024, "Analyzing and Improving
+ * the Training Dynamics of Diffusion Models", section 3 / App. C; no reference counterpart: the reference knows one fixed EMA length,
+ * configs/res_512_*.yaml:4-9).  One pass behind the AdamW pass: every float4 of p is read once and for every profile k < n_profiles
+ *   ema[k][i] = beta[k] * ema[k][i] + (1.f - beta[k]) * p[i]      (fp32; 4 + 8 * n_profiles bytes per parameter)
+ * with beta[k] = (1 - 1/t)^(gamma_k + 1) computed by the caller (t = optimiser steps taken, counted from 1).  beta[k] == 0 (t = 1)
+ * stores p WITHOUT reading ema[k]: whatever the buffer held (NaN included), it comes out as an exact copy of p.
+ * ema and beta are HOST arrays of n_profiles <= MD_EMA_MAX_PROFILES entries, copied into the kernel arguments by value (no device
+ * pointer table); p and every ema[k] are device f32, 16-byte aligned; n % 4 == 0; 0 <= beta[k] < 1.
+ * guard (NULL = none): the go flag of md_step_guard; at *guard == 0 every profile stays untouched bit for bit (the contract of
+ * md_adamw_step_guarded for a live EMA).
+ * The _ranges form walks n_ranges <= MD_ADAMW_MAX_RANGES chunks [flat_off[j], flat_off[j] + count[j]) of the flat buffers (the
+ * convention of md_adamw_step_ranges: host arrays, offsets and counts multiples of 4; p and the profiles are all flat, so only the
+ * flat indices matter) and touches nothing outside them. */
+#define MD_EMA_MAX_PROFILES 4
+int md_ema_power_update(const float* p, float* const* ema, const float* beta, int32_t n_profiles, int64_t n, const int32_t* guard,
+                        hipStream_t stream);
+int md_ema_power_update_ranges(const float* p, float* const* ema, const float* beta, int32_t n_profiles, const int64_t* flat_off,
+                               const int64_t* count, int32_t n_ranges, const int32_t* guard, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

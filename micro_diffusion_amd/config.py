@@ -121,6 +121,40 @@ def diagnostics_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
             "moe_routing": bool(misc.get("moe_routing_monitor", False))}
 
 
+def posthoc_ema_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The post-hoc EMA switches of the `misc` section, off unless the config sets them:
+    misc.posthoc_ema_sigma_rels=[0.05,0.10] (1 .. 4 relative widths, each inside (0, 0.28)) and
+    misc.posthoc_ema_snapshot_interval=<N>ba (0 / absent: the averages are tracked and checkpointed, no snapshot is written).
+    Returns {"sigma_rels": tuple, "snapshot_interval": batches}; raises ValueError on values the optimiser cannot honour."""
+    from .posthoc_ema import MAX_PROFILES, SIGMA_REL_MAX
+    misc = cfg.get("misc") or {}
+    raw = misc.get("posthoc_ema_sigma_rels")
+    if raw is None or raw == [] or raw == "":
+        rels = ()
+    elif isinstance(raw, (int, float)):
+        rels = (float(raw),)
+    elif isinstance(raw, (list, tuple)):
+        rels = tuple(float(v) for v in raw)
+    else:
+        raise ValueError(f"misc.posthoc_ema_sigma_rels must be a list of numbers, got {raw!r}")
+    if len(rels) > MAX_PROFILES:
+        raise ValueError(f"misc.posthoc_ema_sigma_rels: at most {MAX_PROFILES} profiles (MD_EMA_MAX_PROFILES), got {len(rels)}")
+    for s in rels:
+        if not 0.0 < s < SIGMA_REL_MAX:
+            raise ValueError(f"misc.posthoc_ema_sigma_rels: {s} is outside (0, {SIGMA_REL_MAX})")
+    if len(set(rels)) != len(rels):
+        raise ValueError(f"misc.posthoc_ema_sigma_rels: duplicate values in {list(rels)}")
+    iv = misc.get("posthoc_ema_snapshot_interval", 0) or 0
+    if not isinstance(iv, int):
+        from .trainer import parse_batches
+        iv = parse_batches(iv)
+    if iv < 0:
+        raise ValueError("misc.posthoc_ema_snapshot_interval must not be negative")
+    if iv and not rels:
+        raise ValueError("misc.posthoc_ema_snapshot_interval needs misc.posthoc_ema_sigma_rels")
+    return {"sigma_rels": rels, "snapshot_interval": int(iv)}
+
+
 def locate(target: str):
     native = TARGETS.get(target, target)
     if native is None:

@@ -7,6 +7,7 @@
 //                                weights, one pass: 34 B / parameter (p, m, v read + write, g read + zero, shadow write; +8 with EMA)
 //   md_step_guard                go flag of the step from the same device-side sum (finite or not) + running count of skipped steps;
 //   md_adamw_step[_ranges]_guarded  the AdamW pass with that flag: a non-finite step leaves weights and moments untouched (no host sync)
+// (The post-hoc EMA's power-function averages are a pass of their own behind this one: ema.hip, md_ema_power_update.)
 // Gradients may be supplied as bf16 (the data-parallel exchange buffer) instead of the fp32 accumulators.
 // Replaces clip_grad_norm_ (train.py:85-86), torch.optim.AdamW (train.py:39-43; configs/*.yaml optimizer) and the EMA algorithm
 // named by configs/res_512_*.yaml:4-9 (diffusion.algorithms.ema.EMA: ema = s * ema + (1 - s) * p every batch after ema_start).

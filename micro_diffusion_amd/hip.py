@@ -241,6 +241,33 @@ _sig("md_colsum_det", P, I32, I64, P, I64, I64, P, I64, P)
 _sig("md_loss_sigma_hist", P, P, I64, F32, F32, I32, P, P, P, P)
 _sig("md_moe_route_stats_ws_floats", I64, I64, I32, POINTER(c_int64))
 _sig("md_moe_route_stats", P, P, I64, P, I64, I64, I32, I32, P, I64, P, P, P)
+# post-hoc EMA: up to EMA_MAX_PROFILES power-function averages of the masters in one pass (host arrays of pointers / betas)
+_sig("md_ema_power_update", P, P, P, I32, I64, P, P)
+_sig("md_ema_power_update_ranges", P, P, P, I32, P, P, I32, P, P)
+EMA_MAX_PROFILES = 4     # MD_EMA_MAX_PROFILES
+ADAMW_MAX_RANGES = 64    # MD_ADAMW_MAX_RANGES
+
+
+def ema_power_update(p, emas, betas, n, guard=None, flat_off=None, count=None, stream=None, expect=0):
+    """md_ema_power_update (or, with flat_off / count -- ctypes int64 arrays or sequences --, its _ranges form).  p / emas / guard:
+    ints (device addresses) or torch tensors; betas: Python floats.  expect=None returns the code instead of raising."""
+    def ptr(x):
+        if x is None:
+            return None
+        return x if isinstance(x, int) else x.data_ptr()
+    k = len(emas)
+    ev = (c_void_p * max(k, 1))(*[ptr(e) for e in emas])
+    bv = (c_float * max(k, 1))(*[float(b) for b in betas])
+    st = stream if stream is not None else stream_ptr()
+    if flat_off is None:
+        rc = lib().md_ema_power_update(ptr(p), ev, bv, k, n, ptr(guard), st)
+    else:
+        if not isinstance(flat_off, ctypes.Array):
+            flat_off, count = (c_int64 * len(flat_off))(*flat_off), (c_int64 * len(count))(*count)
+        rc = lib().md_ema_power_update_ranges(ptr(p), ev, bv, k, flat_off, count, len(flat_off), ptr(guard), st)
+    if expect is None:
+        return rc
+    check(rc, "md_ema_power_update")
 
 
 def exported_symbols():

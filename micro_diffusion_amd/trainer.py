@@ -22,7 +22,10 @@ configs/*.yaml), re-designed for one process per GPU with RCCL over xGMI:
     the reference's NaNCatcher, but before the update reaches the weights and without a host sync);
   * model diagnostics (opt-in): `Trainer(diagnostics_interval=N, loss_by_sigma_bins=n, moe_routing=True)` keeps the EDM loss split by
     noise level and, on every N-th batch, the token coverage / entropy / marginals of every expert-choice router
-    (diagnostics.py, md_loss_sigma_hist / md_moe_route_stats); `Trainer.diagnostics()` reads them.
+    (diagnostics.py, md_loss_sigma_hist / md_moe_route_stats); `Trainer.diagnostics()` reads them;
+  * post-hoc EMA (opt-in): `FusedAdamW(posthoc_sigma_rels=(0.05, 0.10))` tracks up to four power-function averages of the masters in
+    one extra bandwidth pass behind the AdamW pass (md_ema_power_update[_ranges]); train.py snapshots them and posthoc_ema.py
+    synthesises the average for any EMA length afterwards (Karras et al. 2024, section 3).
 """
 from __future__ import annotations
 
@@ -40,6 +43,7 @@ import torch.distributed as dist
 
 from . import hip
 from . import diagnostics as mddiag
+from . import posthoc_ema
 
 
 def parse_batches(v) -> int:
@@ -178,8 +182,16 @@ class FusedAdamW:
     MAX_BUCKETS = 64      # per-bucket partial sums of the gradient norm (data-parallel exchange), MD_SUMSQ_PARTIALS floats each
 
     def __init__(self, dit, lr: float = 2.4e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.1,
-                 ema_smoothing: Optional[float] = None, ema_start: int = 0, skip_nonfinite: bool = False):
-        """`skip_nonfinite`: guard the step on the device.  The squared gradient norm is then taken on every step (also with
+                 ema_smoothing: Optional[float] = None, ema_start: int = 0, skip_nonfinite: bool = False,
+                 posthoc_sigma_rels=None):
+        """`posthoc_sigma_rels`: a tuple of 1 .. 4 relative widths (e.g. (0.05, 0.10)) switches the post-hoc EMA on: one flat fp32
+        buffer per value, each the size of the masters (4.66 GB per profile at XL/2), holds the power-function average with
+        gamma = posthoc_ema.sigma_rel_to_gamma(value).  After the AdamW launch(es) of every step ONE md_ema_power_update pass reads
+        the masters once and updates every profile with beta = (1 - 1/t)^(gamma + 1), t = step_count (computed on the host in
+        fp64; t = 1 copies the weights).  Independent of `ema_smoothing`: both may be on.  With `skip_nonfinite` the pass takes the
+        guard flag: a skipped step advances t and leaves the averages alone, the same convention as for the fixed-length EMA
+        (ema_live / step_count advance, the average does not move).  None (default): no buffer, no launch, no state entry.
+        `skip_nonfinite`: guard the step on the device.  The squared gradient norm is then taken on every step (also with
         max_norm == 0), md_step_guard derives a go flag from it and the AdamW pass runs in its guarded form: when the norm is not
         finite (a NaN or an Inf anywhere in the gradient) weights, moments and a live EMA stay untouched bit for bit, the
         accumulators are still zeroed and the bf16 weights re-emitted.  No host sync; skipped_steps() reads the device counter.
@@ -200,6 +212,11 @@ class FusedAdamW:
         self.last_grad_scale = 1.0
         self.skip_nonfinite = bool(skip_nonfinite)
         self.guard_state = torch.zeros(4, device=f["p"].device, dtype=torch.int32) if self.skip_nonfinite else None    # md_step_guard
+        self.posthoc_sigma_rels = tuple(float(s) for s in (posthoc_sigma_rels or ()))
+        if len(self.posthoc_sigma_rels) > hip.EMA_MAX_PROFILES:
+            raise ValueError(f"at most {hip.EMA_MAX_PROFILES} post-hoc EMA profiles (MD_EMA_MAX_PROFILES), got {len(self.posthoc_sigma_rels)}")
+        self.posthoc_gammas = tuple(posthoc_ema.sigma_rel_to_gamma(s) for s in self.posthoc_sigma_rels)
+        self.posthoc = [torch.zeros_like(f["p"]) for _ in self.posthoc_sigma_rels]        # empty list: the feature is off
 
     def skipped_steps(self) -> int:
         """Steps the device-side guard turned into a no-op so far (synchronises: the only host read of the guard)."""
@@ -232,6 +249,14 @@ class FusedAdamW:
         else:
             hip.check(L.md_adamw_step(byref(a), st), "md_adamw_step")
 
+    def _posthoc_update(self, off: int, n: int, flat_off=None, count=None) -> None:
+        """md_ema_power_update on elements [off, off + n) of the masters and every profile, or (flat_off / count) its _ranges form
+        over the whole buffers; beta of the step just taken."""
+        betas = [posthoc_ema.power_beta(self.step_count, g) for g in self.posthoc_gammas]
+        p = self.dit.flat_buffers()["p"]
+        hip.ema_power_update(p.data_ptr() + 4 * off, [e.data_ptr() + 4 * off for e in self.posthoc], betas, n,
+                             guard=self.guard_state, flat_off=flat_off, count=count)
+
     def _begin_step(self, grad_scale: float) -> int:
         self.step_count += 1
         self.last_grad_scale = grad_scale
@@ -260,6 +285,8 @@ class FusedAdamW:
                 self._guard(st)
         self._launch(0, f["total"], self.lr if lr is None else lr, max_norm, grad_scale, ss,
                      g_bf16.data_ptr() if g_bf16 is not None else None, f["s"].data_ptr(), 1, ema_mode)
+        if self.posthoc:
+            self._posthoc_update(0, f["total"])
         self.dit.mark_shadow_fresh()
 
     def step_sharded(self, sync: "GradSync", lr: Optional[float] = None, max_norm: float = 0.0, grad_scale: float = 1.0,
@@ -310,6 +337,17 @@ class FusedAdamW:
             lo, hi = sync.small
             self._launch(lo, hi - lo, lr, max_norm, grad_scale, ss, sync.gbf.data_ptr() + 2 * lo, f["s"].data_ptr() + 2 * lo, 0, ema_mode)
         sync.gather_shadows()
+        if self.posthoc:
+            # behind the AdamW launches (and the launch of the weight all-gathers, which only read the bf16 send buffer): the rank's
+            # chunks through the cached range table, the small region flat
+            if len(ranges) <= hip.ADAMW_MAX_RANGES:
+                if ranges:
+                    self._posthoc_update(0, 0, self._range_off, self._range_cnt)
+            else:
+                for off, cnt in ranges:
+                    self._posthoc_update(off, cnt)
+            if sync.small is not None:
+                self._posthoc_update(sync.small[0], sync.small[1] - sync.small[0])
         self.dit.mark_shadow_fresh()
 
     def grad_norm(self) -> torch.Tensor:
@@ -327,6 +365,8 @@ class FusedAdamW:
         sd = {"m": self._by_name(self.m), "v": self._by_name(self.v), "step": self.step_count, "format": "by_name"}
         if self.ema is not None:
             sd["ema"], sd["ema_live"] = self._by_name(self.ema), self.ema_live
+        if self.posthoc:
+            sd["posthoc"] = {"sigma_rels": list(self.posthoc_sigma_rels), "ema": [self._by_name(e) for e in self.posthoc]}
         return sd
 
     def load_state_dict(self, sd):
@@ -357,6 +397,25 @@ class FusedAdamW:
         elif self.ema is None and "ema" in sd:
             import warnings
             warnings.warn("the checkpoint carries EMA weights but this run configures no EMA: they are dropped")
+        ph = sd.get("posthoc")
+        if self.posthoc and ph is not None:
+            if len(ph["ema"]) != len(self.posthoc):
+                raise RuntimeError(f"the checkpoint carries {len(ph['ema'])} post-hoc EMA profiles, this run configures {len(self.posthoc)}")
+            if any(abs(a - b) > 1e-12 for a, b in zip(ph["sigma_rels"], self.posthoc_sigma_rels)):
+                import warnings
+                warnings.warn(f"post-hoc EMA: the checkpoint's sigma_rels {list(ph['sigma_rels'])} differ from this run's "
+                              f"{list(self.posthoc_sigma_rels)}: the loaded averages continue with the new exponents")
+            for dst, src in zip(self.posthoc, ph["ema"]):
+                put(dst, src)
+        elif self.posthoc and self.step_count > 0:
+            # beta(t > 1) would mix the zero-initialised buffers into the averages: start every profile as a copy of the weights
+            import warnings
+            warnings.warn(f"optimizer state at step {self.step_count} carries no post-hoc EMA profiles: they restart from the current weights")
+            for e in self.posthoc:
+                e.copy_(self.dit.flat_buffers()["p"])
+        elif ph is not None:
+            import warnings
+            warnings.warn("the checkpoint carries post-hoc EMA profiles but this run configures none: they are dropped")
 
     # ------------------------------------------------------------------ EMA weights for evaluation / export
     def ema_state_dict(self):
@@ -371,13 +430,28 @@ class FusedAdamW:
             out[name] = self.ema[o:o + view.numel()].view(view.shape)
         return out
 
+    def posthoc_state_dict(self, k: int):
+        """Post-hoc EMA profile k as a model state_dict (views of the profile buffer, keys / shapes of the parameters), or None
+        before the first step.  Under the sharded optimiser call Trainer.consolidate() first."""
+        if not 0 <= k < len(self.posthoc):
+            raise IndexError(f"post-hoc EMA profile {k} of {len(self.posthoc)}")
+        return self._by_name(self.posthoc[k]) if self.step_count > 0 else None
+
     class _EmaSwap:
-        def __init__(self, opt):
-            self.opt = opt
+        def __init__(self, opt, profile=None):
+            self.opt, self.profile = opt, profile
+
+        def _buf(self):
+            return self.opt.ema if self.profile is None else self.opt.posthoc[self.profile]
 
         def __enter__(self):
             o = self.opt
-            self.active = o.ema is not None and o.ema_live
+            if self.profile is None:
+                self.active = o.ema is not None and o.ema_live
+            else:
+                if not 0 <= self.profile < len(o.posthoc):
+                    raise IndexError(f"post-hoc EMA profile {self.profile} of {len(o.posthoc)}")
+                self.active = o.step_count > 0
             if self.active and getattr(o.dit, "shadow_is_authoritative", False):
                 # sharded optimiser: the fp32 masters of the other ranks' chunks are stale and refresh_shadow() would refuse AFTER
                 # the swap, leaving masters and EMA exchanged -- refuse here, before anything is touched
@@ -385,8 +459,8 @@ class FusedAdamW:
             if self.active:                       # off the step path: plain tensor swaps, then re-derive the bf16 shadow
                 f = o.dit.flat_buffers()
                 tmp = f["p"].clone()
-                f["p"].copy_(o.ema)
-                o.ema.copy_(tmp)
+                f["p"].copy_(self._buf())
+                self._buf().copy_(tmp)
                 o.dit.refresh_shadow(force=True)
             return self.active
 
@@ -395,15 +469,15 @@ class FusedAdamW:
                 o = self.opt
                 f = o.dit.flat_buffers()
                 tmp = f["p"].clone()
-                f["p"].copy_(o.ema)
-                o.ema.copy_(tmp)
+                f["p"].copy_(self._buf())
+                self._buf().copy_(tmp)
                 o.dit.refresh_shadow(force=True)
             return False
 
-    def swap_ema(self):
+    def swap_ema(self, profile: Optional[int] = None):
         """Context manager: the model computes with the EMA weights inside (Composer's EMA swaps them in for evaluation);
-        a no-op before the first EMA batch."""
-        return FusedAdamW._EmaSwap(self)
+        a no-op before the first EMA batch.  `profile` = k evaluates on post-hoc EMA profile k instead (a no-op before the first step)."""
+        return FusedAdamW._EmaSwap(self, profile)
 
 
 RCCL_CHANNELS_DEFAULT = 8      # CUs handed to RCCL per rank: 8 channels move the 2 x 2 GB of a step at well over the ~30 GB/s the
@@ -1023,15 +1097,15 @@ class Trainer:
         return sum(a.elapsed_time(b) for a, b in ev) / len(ev)
 
     def consolidate(self) -> None:
-        """Sharded optimiser only: all-gather the fp32 masters, both moments and the EMA so that every rank holds the whole,
-        current state (checkpoints, evaluation on EMA weights, state_dict()).  A collective: every rank must call it.  Not on the
-        step path (3 x 4.66 GB for XL/2, at checkpoint / evaluation intervals)."""
+        """Sharded optimiser only: all-gather the fp32 masters, both moments, the EMA and the post-hoc EMA profiles so that every rank
+        holds the whole, current state (checkpoints, snapshots, evaluation on EMA weights, state_dict()).  A collective: every rank must
+        call it.  Not on the step path (3 x 4.66 GB for XL/2, one more per average; at checkpoint / evaluation / snapshot intervals)."""
         if not self.sharded or not self.stale_foreign_chunks:
             return
         s = self.sync
         s.wait_gather()
         f = self.model.dit.flat_buffers()
-        bufs = [f["p"], self.opt.m, self.opt.v] + ([self.opt.ema] if self.opt.ema is not None else [])
+        bufs = [f["p"], self.opt.m, self.opt.v] + ([self.opt.ema] if self.opt.ema is not None else []) + list(self.opt.posthoc)
         for t in bufs:
             for key, lo, hi, chunk, olo in s.plan:
                 mine = t[lo + s.rank * chunk: lo + (s.rank + 1) * chunk].clone()
@@ -1057,7 +1131,7 @@ class Trainer:
             return
         self.consolidate()          # after a sharded step rank 0's masters of foreign chunks are stale: make them whole first
         f = self.model.dit.flat_buffers()
-        bufs = [f["p"], self.opt.m, self.opt.v] + ([self.opt.ema] if self.opt.ema is not None else [])
+        bufs = [f["p"], self.opt.m, self.opt.v] + ([self.opt.ema] if self.opt.ema is not None else []) + list(self.opt.posthoc)
         for t in bufs:
             if self.sync.torch_bounce:
                 h = t.cpu()

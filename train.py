@@ -23,6 +23,7 @@ from micro_diffusion_amd.trainer import FusedAdamW, LRSchedule, Trainer, parse_b
 
 
 def train(cfg: dict):
+    posthoc = mdcfg.posthoc_ema_options(cfg)     #  checked before anything is allocated: raises on values it cannot honour
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -73,8 +74,11 @@ def train(cfg: dict):
     if not mdcfg.names_target(cfg, "composer.callbacks.OptimizerMonitor"):
         monitor_every = 0
     guard_kw = dict(skip_nonfinite=True) if skip_nonfinite else {}
+    # Post-hoc EMA, off by default: misc.posthoc_ema_sigma_rels, misc.posthoc_ema_snapshot_interval
+    posthoc_kw = dict(posthoc_sigma_rels=posthoc["sigma_rels"]) if posthoc["sigma_rels"] else {}
+    snap_every = posthoc["snapshot_interval"]
     opt = FusedAdamW(model.dit, lr=ocfg["lr"], betas=tuple(ocfg.get("betas", (0.9, 0.999))), eps=ocfg.get("eps", 1e-8),
-                     weight_decay=ocfg.get("weight_decay", 0.0), **ema_kw, **guard_kw)
+                     weight_decay=ocfg.get("weight_decay", 0.0), **ema_kw, **guard_kw, **posthoc_kw)
     if carried_opt is not None:
         opt.load_state_dict(carried_opt)          # keyed by parameter name; raises on a mismatch with this model
     max_ba = parse_batches(cfg["trainer"]["max_duration"])
@@ -167,8 +171,11 @@ def train(cfg: dict):
             if skip_nonfinite:
                 line["skipped_steps"] = skipped_logged
             print(json.dumps(line), flush=True)
-        if folder and save_every and (step + 1) % save_every == 0:
+        snap_now = bool(folder and snap_every and (step + 1) % snap_every == 0)
+        if snap_now or (folder and save_every and (step + 1) % save_every == 0):
             trainer.consolidate()                                  # a collective under the sharded optimiser: every rank calls it
+        if rank == 0 and snap_now:
+            save_posthoc_snapshots(opt, os.path.join(folder, "posthoc"), step + 1)
         if rank == 0 and folder and save_every and (step + 1) % save_every == 0:
             os.makedirs(folder, exist_ok=True)
             tmp = os.path.join(folder, "latest.pt.tmp")
@@ -181,6 +188,26 @@ def train(cfg: dict):
                         "loader": loader.state_dict() if hasattr(loader, "state_dict") else None}, tmp)
             os.replace(tmp, os.path.join(folder, "latest.pt"))      # never leave a truncated latest.pt behind
     return trainer
+
+
+def save_posthoc_snapshots(opt, folder: str, step: int, profiles=None) -> list:
+    """One file per post-hoc EMA profile: <folder>/ema-<step:08d>-<sigma_rel:.3f>.pt = {"state": by-name fp32 state_dict of the
+    averaged parameters, "buffers": what dit.state_dict() holds besides them (pos_embed: copied, never averaged), "step", "sigma_rel",
+    "gamma"} (what posthoc_ema.reconstruct / scripts/posthoc_ema.py read).  Snapshots are never rotated away: the
+    reconstruction needs all of them, so they live outside save_num_checkpoints_to_keep.  `profiles`: indices to write (default: all)."""
+    from micro_diffusion_amd import posthoc_ema
+    os.makedirs(folder, exist_ok=True)
+    torch.cuda.synchronize()
+    written = []
+    buffers = {n: v.detach().cpu().clone() for n, v in opt.dit.state_dict().items() if n not in opt.dit.flat_buffers()["P"]}
+    for k in (range(len(opt.posthoc)) if profiles is None else profiles):
+        s, g = opt.posthoc_sigma_rels[k], opt.posthoc_gammas[k]
+        path = os.path.join(folder, posthoc_ema.snapshot_name(step, s))
+        state = {n: v.detach().cpu().clone() for n, v in opt.posthoc_state_dict(k).items()}
+        torch.save({"state": state, "buffers": buffers, "step": int(step), "sigma_rel": float(s), "gamma": float(g)}, path + ".tmp")
+        os.replace(path + ".tmp", path)
+        written.append(path)
+    return written
 
 
 @torch.no_grad()
