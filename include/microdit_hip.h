@@ -347,6 +347,33 @@ int md_edm_loss_train(const void* tok, const int32_t* keep_rows, const float* xn
                       float accum_weight, int64_t B, int64_t Tk, int32_t C, int32_t H, int32_t W, int32_t p, float sigma_data,
                       hipStream_t stream);
 
+/* Learned per-noise-level loss weighting (added under ABI 6: new symbols only).  Karras et al. 2024, "Analyzing and Improving the
+ * Training Dynamics of Diffusion Models", section 2.2 (uncertainty-based loss weighting); no reference counterpart: models/model.py:199-210
+ * trains with the fixed EDM weight alone.  With C channels (C a multiple of 64, 64 <= C <= 256), cnoise[b] = ln(sigma[b]) / 4 as
+ * md_edm_prepare(_f16) writes it and L[b] the loss_per_sample of md_edm_loss_train(_weighted), all fp32:
+ *   feat[b, c] = sqrt(2) * cosf(cnoise[b] * freq[c] + phase[c])        freq, phase: fixed buffers [C]
+ *   u[b]       = sum_c w[c] * feat[b, c]                               w: the C trainable weights (w = 0: u = 0, inv = 1 exactly)
+ *   inv[b]     = expf(-u[b])
+ *   objective  = (1 / B) sum_b (L[b] * inv[b] + u[b])
+ *   dw[c]     += sum_b gscale / B * (1 - inv[b] * L[b]) * feat[b, c]
+ * md_logvar_fwd writes u [B] and inv [B]: one wave per sample, lane l adds channels l, l + 64, ... in ascending order.
+ * md_edm_loss_train_weighted is md_edm_loss_train with sample_scale [B] (the inv above): the gradient factor of sample b is
+ * (gfac * sample_scale[b]), formed once, then * diff; loss_per_sample, loss_mean and loss_accum stay the RAW loss (sample_scale = 1
+ * gives the bits of md_edm_loss_train).
+ * md_logvar_bwd: one workgroup, no float atomic; for every c the samples are added to dw[c] in index order (two calls from the same
+ * buffers give the same bits); obj_mean = the objective, obj_accum (optional) += accum_weight * obj_mean.  inv is recomputed from u.
+ * A non-finite L[b] propagates into dw (not masked: the step guard handles it).
+ * All three return -1 on a null pointer (obj_accum excepted), B < 1 or a C outside the set above; no allocation, no synchronisation. */
+int md_logvar_fwd(const float* cnoise, const float* freq, const float* phase, const float* w, float* u, float* inv, int64_t B,
+                  int32_t C, hipStream_t stream);
+int md_edm_loss_train_weighted(const void* tok, const int32_t* keep_rows, const float* xn, const float* x0, const float* sigma,
+                               float* loss_per_sample, float* loss_mean, void* dtok_bf16, float grad_scale, float* loss_accum,
+                               float accum_weight, int64_t B, int64_t Tk, int32_t C, int32_t H, int32_t W, int32_t p,
+                               float sigma_data, const float* sample_scale, hipStream_t stream);
+int md_logvar_bwd(const float* cnoise, const float* freq, const float* phase, const float* u, const float* loss_per_sample,
+                  float gscale, float* dw, float* obj_mean, float* obj_accum, float accum_weight, int64_t B, int32_t C,
+                  hipStream_t stream);
+
 /* Sampler (model.py:231-297): the arithmetic around each network evaluation of the Heun loop, fused; fp64 state, fp32
  * preconditioning (model.py:144-179) and classifier-free-guidance combine (dit.py:542-550: F = [cond; uncond] halves). */
 int md_edm_sampler_input(const double* x, float* out, int64_t n, float sigma, float sigma_data, int32_t duplicate, hipStream_t stream);

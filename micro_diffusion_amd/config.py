@@ -155,6 +155,36 @@ def posthoc_ema_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     return {"sigma_rels": rels, "snapshot_interval": int(iv)}
 
 
+def loss_weighting_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The learned loss-weighting switches of the `misc` section, off unless the config sets them:
+    misc.loss_uncertainty_weighting (bool), misc.loss_uncertainty_channels (64 / 128 / 192 / 256, default 128) and
+    misc.loss_uncertainty_lr (default: the optimiser's lr; the schedule factor applies to both).
+    Returns {"enabled": bool, "channels": int, "lr": float or None}; raises ValueError on values the kernels cannot honour and on
+    channels / lr given without the switch."""
+    from .loss_weighting import CHANNEL_CHOICES, check_channels
+    misc = cfg.get("misc") or {}
+    on = misc.get("loss_uncertainty_weighting", False)
+    if on is None:
+        on = False
+    if not isinstance(on, bool):
+        raise ValueError(f"misc.loss_uncertainty_weighting must be true or false, got {on!r}")
+    ch, lr = misc.get("loss_uncertainty_channels"), misc.get("loss_uncertainty_lr")
+    if not on:
+        for key, v in (("loss_uncertainty_channels", ch), ("loss_uncertainty_lr", lr)):
+            if v is not None:
+                raise ValueError(f"misc.{key} needs misc.loss_uncertainty_weighting=true")
+        return {"enabled": False, "channels": 128, "lr": None}
+    try:
+        ch = check_channels(128 if ch is None else ch)
+    except ValueError:
+        raise ValueError(f"misc.loss_uncertainty_channels must be one of {CHANNEL_CHOICES}, got {ch!r}") from None
+    if lr is not None:
+        if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not lr >= 0 or lr == float("inf"):
+            raise ValueError(f"misc.loss_uncertainty_lr must be a non-negative number, got {lr!r}")
+        lr = float(lr)
+    return {"enabled": True, "channels": ch, "lr": lr}
+
+
 def locate(target: str):
     native = TARGETS.get(target, target)
     if native is None:

@@ -88,11 +88,13 @@ __global__ __launch_bounds__(256) void unpatchify_kernel(const bf16* tok, const 
 // dtok = gscale * d(mean_b loss_b)/dF for the kept tokens ([B*Tk, C*p*p], (ph, pw, c) order; f32, or bf16 for the
 // training step, whose backward starts from bf16 anyway).  The batch mean is taken by edm_loss_finish_kernel in sample
 // order (the first version added the per-sample terms with float atomics: the loss depended on the arrival order).
-template <typename DT>
+// WEIGHTED (md_edm_loss_train_weighted): the gradient factor of sample b is (gfac * sample_scale[b]), formed once; the loss outputs
+// stay the raw loss.  The unweighted instantiations never read sample_scale (NULL).
+template <typename DT, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void edm_loss_kernel(const bf16* tok, const int32_t* keep_rows, const float* xn,
                                                        const float* x0, const float* sigma, float* loss_per_sample,
                                                        DT* dtok, float gscale, int64_t B, int64_t Tk, int C, int H,
-                                                       int W, int p, float sd) {
+                                                       int W, int p, float sd, const float* sample_scale) {
     __shared__ float red[4];
     const int gh = H / p, gw = W / p, pv = C * p * p;
     const int64_t T = (int64_t)gh * gw;
@@ -102,7 +104,8 @@ __global__ __launch_bounds__(256) void edm_loss_kernel(const bf16* tok, const in
     const float cskip = sd * sd / (s * s + sd * sd);
     const float cout = s * sd / sqrtf(s * s + sd * sd);
     const float norm = 1.f / ((float)pv * (float)Tk);
-    const float gfac = 2.f * wgt * cout * norm / (float)B * gscale;
+    float gfac = 2.f * wgt * cout * norm / (float)B * gscale;
+    if constexpr (WEIGHTED) gfac = gfac * sample_scale[b];
     float acc = 0.f;
     for (int64_t i = threadIdx.x; i < Tk * pv; i += 256) {
         const int64_t j = i / pv;
@@ -430,7 +433,7 @@ extern "C" int md_edm_loss(const void* tok, const int32_t* keep_rows, const floa
     if (!tok || !xn || !x0 || !sigma || !loss_per_sample || !loss_mean || B <= 0 || Tk <= 0 || H % p || W % p)
         return MD_BAD_ARG;
     hipLaunchKernelGGL(edm_loss_kernel<float>, dim3((unsigned)B), dim3(256), 0, st, (const bf16*)tok, keep_rows, xn, x0, sigma,
-                       loss_per_sample, dtok, 1.f, B, Tk, C, H, W, p, sigma_data);
+                       loss_per_sample, dtok, 1.f, B, Tk, C, H, W, p, sigma_data, (const float*)nullptr);
     hipLaunchKernelGGL(edm_loss_finish_kernel, dim3(1), dim3(64), 0, st, loss_per_sample, loss_mean, (float*)nullptr, 0.f, B);
     MD_LAUNCH_CHECK();
     return 0;
@@ -443,7 +446,21 @@ extern "C" int md_edm_loss_train(const void* tok, const int32_t* keep_rows, cons
     if (!tok || !xn || !x0 || !sigma || !loss_per_sample || !loss_mean || !dtok_bf16 || B <= 0 || Tk <= 0 || H % p || W % p)
         return MD_BAD_ARG;
     hipLaunchKernelGGL(edm_loss_kernel<bf16>, dim3((unsigned)B), dim3(256), 0, st, (const bf16*)tok, keep_rows, xn, x0, sigma,
-                       loss_per_sample, (bf16*)dtok_bf16, grad_scale, B, Tk, C, H, W, p, sigma_data);
+                       loss_per_sample, (bf16*)dtok_bf16, grad_scale, B, Tk, C, H, W, p, sigma_data, (const float*)nullptr);
+    hipLaunchKernelGGL(edm_loss_finish_kernel, dim3(1), dim3(64), 0, st, loss_per_sample, loss_mean, loss_accum, accum_weight, B);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_edm_loss_train_weighted(const void* tok, const int32_t* keep_rows, const float* xn, const float* x0,
+                                          const float* sigma, float* loss_per_sample, float* loss_mean, void* dtok_bf16,
+                                          float grad_scale, float* loss_accum, float accum_weight, int64_t B, int64_t Tk, int32_t C,
+                                          int32_t H, int32_t W, int32_t p, float sigma_data, const float* sample_scale, hipStream_t st) {
+    if (!tok || !xn || !x0 || !sigma || !loss_per_sample || !loss_mean || !dtok_bf16 || !sample_scale || B <= 0 || Tk <= 0 || H % p ||
+        W % p)
+        return MD_BAD_ARG;
+    hipLaunchKernelGGL((edm_loss_kernel<bf16, true>), dim3((unsigned)B), dim3(256), 0, st, (const bf16*)tok, keep_rows, xn, x0, sigma,
+                       loss_per_sample, (bf16*)dtok_bf16, grad_scale, B, Tk, C, H, W, p, sigma_data, sample_scale);
     hipLaunchKernelGGL(edm_loss_finish_kernel, dim3(1), dim3(64), 0, st, loss_per_sample, loss_mean, loss_accum, accum_weight, B);
     MD_LAUNCH_CHECK();
     return 0;

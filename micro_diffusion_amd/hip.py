@@ -211,6 +211,11 @@ _sig("md_timestep_embed", P, P, I64, I32, P)
 _sig("md_unpatchify", P, P, I64, P, P, I64, I32, I32, I32, I32, P)
 _sig("md_edm_loss", P, P, P, P, P, P, P, P, I64, I64, I32, I32, I32, I32, F32, P)
 _sig("md_edm_loss_train", P, P, P, P, P, P, P, P, F32, P, F32, I64, I64, I32, I32, I32, I32, F32, P)
+# learned per-noise-level loss weighting (loss_weighting.py): u / exp(-u) per sample, the EDM loss with a per-sample gradient factor,
+# the gradient of the weighted objective w.r.t. the C feature weights
+_sig("md_logvar_fwd", P, P, P, P, P, P, I64, I32, P)
+_sig("md_edm_loss_train_weighted", P, P, P, P, P, P, P, P, F32, P, F32, I64, I64, I32, I32, I32, I32, F32, P, P)
+_sig("md_logvar_bwd", P, P, P, P, P, F32, P, P, P, F32, I64, I32, P)
 _sig("md_edm_sampler_input", P, P, I64, F32, F32, I32, P)
 _sig("md_edm_heun_update", P, P, P, P, P, I64, F32, I32, ctypes.c_double, ctypes.c_double, ctypes.c_double, F32, I32, P)
 # token-space forms (the cached sampling path): no fp32 image between the fp64 sampler state and the network's bf16 rows

@@ -78,6 +78,10 @@ class LatentDiffusion(nn.Module):
         # Loss by noise level (opt-in): a diagnostics.LossBySigma; every EDM loss evaluation then adds its per-sample
         # losses to the train or eval table (one md_loss_sigma_hist launch).  None: no launch, no buffer.
         self.loss_by_sigma = None
+        # Learned per-noise-level loss weighting (opt-in): a loss_weighting.LossWeighting; the Trainer's microbatch
+        # step then runs md_logvar_fwd -> md_edm_loss_train_weighted -> md_logvar_bwd.  None: the launches of today.  Evaluation and
+        # sampling never read it.
+        self.loss_weighting = None
         assert self.train_mask_ratio >= 0, "Masking ratio must be non-negative!"
         self.randn_like = torch.randn_like
         self.latent_scale = self.vae.config.scaling_factor
@@ -176,6 +180,10 @@ class LatentDiffusion(nn.Module):
         x, y, rnd, eps, mnoise = self._prep(x, y, mask_ratio, _noise)
         dit = self.dit
         need_grad = torch.is_grad_enabled() and dit._plist[0].requires_grad
+        if need_grad and self.loss_weighting is not None:
+            raise RuntimeError("the learned loss weighting is armed (LatentDiffusion.loss_weighting): its gradient exists only on the "
+                               "Trainer's microbatch path (train_microbatch); the autograd surface would train the network on the "
+                               "unweighted loss.  Disarm it or run under torch.no_grad()")
         args = (self, dit._grad_anchor, x, y, rnd, eps, mnoise, float(mask_ratio), _y_rowscale)
         if need_grad:
             return _EDMLossFunction.apply(*args)
@@ -433,9 +441,18 @@ def _edm_forward(model: LatentDiffusion, anchor, x, y, rnd, eps, mnoise, mask_ra
     lps = torch.empty(B, device=dev)
     loss = torch.empty(1, device=dev)
     keep = None if tape.keep_rows is None else tape.keep_rows.data_ptr()
+    lw = model.loss_weighting if train is not None else None
     if train is not None:
         gscale, accum, aw = train
         dtok = torch.empty(B * tape.Tk, dit.config.patch_vec, device=dev, dtype=torch.bfloat16)
+    if lw is not None:
+        inv = lw.forward(cnoise)
+        hip.check(L.md_edm_loss_train_weighted(tape.out_tok.data_ptr(), keep, xn.data_ptr(), x0.data_ptr(), sigma.data_ptr(), lps.data_ptr(),
+                                               loss.data_ptr(), dtok.data_ptr(), gscale, None if accum is None else accum.data_ptr(), aw,
+                                               B, tape.Tk, C, H, W, dit.patch_size, ec.sigma_data, inv.data_ptr(), st),
+                  "md_edm_loss_train_weighted")
+        lw.backward(cnoise, lps, gscale, lw.objective_accum, aw)
+    elif train is not None:
         hip.check(L.md_edm_loss_train(tape.out_tok.data_ptr(), keep, xn.data_ptr(), x0.data_ptr(), sigma.data_ptr(), lps.data_ptr(),
                                       loss.data_ptr(), dtok.data_ptr(), gscale, None if accum is None else accum.data_ptr(), aw, B,
                                       tape.Tk, C, H, W, dit.patch_size, ec.sigma_data, st), "md_edm_loss_train")

@@ -25,7 +25,10 @@ configs/*.yaml), re-designed for one process per GPU with RCCL over xGMI:
     (diagnostics.py, md_loss_sigma_hist / md_moe_route_stats); `Trainer.diagnostics()` reads them;
   * post-hoc EMA (opt-in): `FusedAdamW(posthoc_sigma_rels=(0.05, 0.10))` tracks up to four power-function averages of the masters in
     one extra bandwidth pass behind the AdamW pass (md_ema_power_update[_ranges]); train.py snapshots them and posthoc_ema.py
-    synthesises the average for any EMA length afterwards (Karras et al. 2024, section 3).
+    synthesises the average for any EMA length afterwards (Karras et al. 2024, section 3);
+  * learned loss weighting (opt-in): `Trainer(loss_weighting=LossWeighting())` trains u(sigma) next to the network (loss_weighting.py,
+    Karras et al. 2024, section 2.2): two more tiny launches per microbatch, one fp32 all-reduce of its C gradient values per step and
+    one C-element AdamW launch behind the main optimiser pass.
 """
 from __future__ import annotations
 
@@ -44,6 +47,7 @@ import torch.distributed as dist
 from . import hip
 from . import diagnostics as mddiag
 from . import posthoc_ema
+from .loss_weighting import LossWeighting
 
 
 def parse_batches(v) -> int:
@@ -871,8 +875,13 @@ class Trainer:
     def __init__(self, model, optimizer: FusedAdamW, schedule: Optional[LRSchedule] = None, clip_norm: float = 0.0,
                  microbatch_size: int = 256, process_group=None, log: Optional[Callable[[dict], None]] = None,
                  exchange: str = "auto", single_rank_exchange: bool = False, dp_mode: str = "auto", transport: str = "auto",
-                 monitor_interval: int = 0, diagnostics_interval: int = 0, loss_by_sigma_bins: int = 0, moe_routing: bool = False):
-        """diagnostics_interval / loss_by_sigma_bins / moe_routing (all off by default: no launch, no buffer): see diagnostics().
+                 monitor_interval: int = 0, diagnostics_interval: int = 0, loss_by_sigma_bins: int = 0, moe_routing: bool = False,
+                 loss_weighting: Optional[LossWeighting] = None):
+        """loss_weighting (None: off -- no launch, no buffer, no collective): a LossWeighting armed as model.loss_weighting.  Its C
+        gradient values are all-reduced (fp32 sum) after the main exchange in every exchange mode, its AdamW launch runs behind the
+        main optimiser pass at `loss_weighting.lr` (default: the optimiser's lr) times the schedule factor, outside the clipped norm,
+        under the optimiser's step guard when that is on; weighted_objective() is the rank-mean objective of the last step.
+        diagnostics_interval / loss_by_sigma_bins / moe_routing (all off by default: no launch, no buffer): see diagnostics().
         loss_by_sigma_bins = n > 0 arms model.loss_by_sigma (n bins over P_mean +- 3 P_std in ln sigma): every microbatch of every
         step adds to the histogram.  moe_routing arms the engine's route_stats for the microbatches of the batches whose number is a
         multiple of diagnostics_interval (tables zeroed when armed, accumulated over the step's microbatches).
@@ -924,6 +933,9 @@ class Trainer:
             ec = model.edm_config
             model.loss_by_sigma = mddiag.LossBySigma(int(loss_by_sigma_bins), ec.P_mean, ec.P_std)
         self._route_stats = mddiag.RouteStats(model.dit.engine) if moe_routing else None     # armed by train_step on report batches
+        self.loss_weighting = loss_weighting
+        self._objective = None               # with the loss weighting: rank-mean weighted objective of the last step (device scalar)
+        model.loss_weighting = loss_weighting      # unconditionally: a model armed by an earlier Trainer must not stay armed unstepped
         self.log = log
         self._win: List[tuple] = []
         self.measure_comm = False          # bench.py: event pairs around GradSync.finish() (exposed exchange time)
@@ -941,6 +953,10 @@ class Trainer:
         starts = list(range(0, n, mb))
         total = torch.empty(1, device=model.dit.flat_buffers()["p"].device)       # a fresh scalar per step: callers keep them
         hip.check(hip.lib().md_fill_zero(total.data_ptr(), 4, torch.cuda.current_stream().cuda_stream), "md_fill_zero")
+        lw = self.loss_weighting
+        if lw is not None:                   # a fresh scalar per step, like `total`: the step's rank-mean weighted objective
+            lw.objective_accum = self._objective = torch.empty(1, device=total.device)
+            hip.check(hip.lib().md_fill_zero(self._objective.data_ptr(), 4, torch.cuda.current_stream().cuda_stream), "md_fill_zero")
         if (self._route_stats is not None and self.diagnostics_interval > 0
                 and (self.batches_seen + 1) % self.diagnostics_interval == 0):
             self._route_stats.zero()
@@ -963,6 +979,8 @@ class Trainer:
         if self.measure_comm:
             e1.record()                                  # behind the waits on the collectives / side-stream norms
             self._comm_events.append((e0, e1))
+        if lw is not None and self.world > 1:
+            self._reduce_loss_weighting_grad()
         if self.monitor_interval > 0 and (self.batches_seen + 1) % self.monitor_interval == 0:
             self.collect_tensor_stats()                  # reads the gradients the optimiser pass is about to consume and clear
         fac = self.schedule.factor(self.batches_seen) if self.schedule is not None else 1.0
@@ -977,11 +995,27 @@ class Trainer:
         else:
             self.opt.step(lr=self.opt.lr * fac, max_norm=self.clip_norm, grad_scale=1.0 / self.world,
                           g_bf16=self.sync.gbf, norm_partials=slots * hip.SUMSQ_PARTIALS)
+        if lw is not None:                   # behind the main pass: its guard flag (skip_nonfinite) is set by now
+            lw.step((self.opt.lr if lw.lr is None else lw.lr) * fac, grad_scale=1.0 / self.world, guard_state=self.opt.guard_state)
         if self.measure_comm:
             o1.record()                                  # norm finish + AdamW (+ the launch of the weight all-gathers)
             self._opt_events.append((o0, o1))
         self.batches_seen += 1
         return total.reshape(())
+
+    # ------------------------------------------------------------------ learned loss weighting
+    def _reduce_loss_weighting_grad(self) -> None:
+        """One fp32 all-reduce (sum) of the C gradient values of u(sigma) on the trainer's process group, the same in all three
+        exchange modes; the 1 / world factor goes into the AdamW launch's grad_scale as for the other gradients.  A sum of `world`
+        addends per element: every rank receives the same bits."""
+        w = self.sync._all_reduce(self.loss_weighting.g)
+        if w is not None:
+            w.wait()
+
+    def weighted_objective(self) -> Optional[torch.Tensor]:
+        """The rank-mean weighted objective (1 / B) sum_b (L_b e^{-u_b} + u_b) of the last step (device scalar; None before the first
+        step or without the loss weighting).  train_step's return value stays the raw loss."""
+        return self._objective.reshape(()) if self.loss_weighting is not None and self._objective is not None else None
 
     # ------------------------------------------------------------------ per-tensor statistics (optimizer monitor)
     def _stats_names(self) -> List[str]:
@@ -1085,6 +1119,25 @@ class Trainer:
             c, s = c.view(len(rs.names), -1), s.view(len(rs.names), -1)
             for i, name in enumerate(rs.names):
                 out.update(mddiag.format_route_stats(name, c[i].tolist(), s[i].tolist()))
+        lw = self.loss_weighting
+        if lw is not None:
+            # u(sigma) at the centres of the loss-by-sigma bins when that histogram is armed (the two tables line up), else at 16 points
+            # over P_mean +- 3 P_std; w is identical on every rank, the objective of the last step is averaged over the ranks
+            ec = model.edm_config
+            if lbs is not None:
+                e = [float(x) for x in lbs.edges]
+                pts = [0.5 * (a + b) for a, b in zip(e[:-1], e[1:])]
+            else:
+                lo, hi = ec.P_mean - 3 * ec.P_std, ec.P_mean + 3 * ec.P_std
+                pts = [lo + (hi - lo) * i / 15 for i in range(16)]
+            obj = self.weighted_objective()
+            if obj is not None and self.world > 1:              # the mean over the ranks: every rank reports the same number
+                obj = obj.reshape(1).clone()
+                wk = self.sync._all_reduce(obj)
+                if wk is not None:
+                    wk.wait()
+                obj = obj / self.world
+            out["loss_weighting"] = {"ln_sigma": pts, "u": lw.u_at(pts), "objective": None if obj is None else float(obj)}
         return out
 
     def exposed_comm_ms(self, last: int = 0) -> Optional[float]:
@@ -1132,6 +1185,9 @@ class Trainer:
         self.consolidate()          # after a sharded step rank 0's masters of foreign chunks are stale: make them whole first
         f = self.model.dit.flat_buffers()
         bufs = [f["p"], self.opt.m, self.opt.v] + ([self.opt.ema] if self.opt.ema is not None else []) + list(self.opt.posthoc)
+        if self.loss_weighting is not None:
+            lw = self.loss_weighting
+            bufs += [lw.freq, lw.phase, lw.w, lw.m, lw.v]
         for t in bufs:
             if self.sync.torch_bounce:
                 h = t.cpu()
@@ -1156,6 +1212,9 @@ class Trainer:
         for i, (_, blo, bhi) in enumerate(self.sync.bucket_list):
             n = (bhi - blo) // 8 * 8             # buckets start on 1024-element boundaries; a ragged end (none today) is left to the next check
             hip.check(L.md_checksum_u16(f["s"].data_ptr() + 2 * blo, n, mine.data_ptr() + 16 * i, st), "md_checksum_u16")
+        mine = mine.reshape(-1)
+        if self.loss_weighting is not None:      # the C weights of u(sigma): their fp32 bit patterns ride along in the same comparison
+            mine = torch.cat([mine, self.loss_weighting.w.view(torch.int32).to(torch.int64)])
         lo, hi = mine.clone(), mine.clone()
         if self.sync.torch_bounce:
             lo, hi = lo.cpu(), hi.cpu()

@@ -18,12 +18,14 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from micro_diffusion_amd import config as mdcfg  # noqa: E402
+from micro_diffusion_amd import loss_weighting as mdlw  # noqa: E402
 from micro_diffusion_amd.model import text_encoder_embedding_format  # noqa: E402
 from micro_diffusion_amd.trainer import FusedAdamW, LRSchedule, Trainer, parse_batches  # noqa: E402
 
 
 def train(cfg: dict):
     posthoc = mdcfg.posthoc_ema_options(cfg)     #  checked before anything is allocated: raises on values it cannot honour
+    lwopt = mdcfg.loss_weighting_options(cfg)    #  likewise: channels / lr checked here
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -43,6 +45,9 @@ def train(cfg: dict):
     # sigma / eps / mask noise for their shards of the global batch.
     torch.manual_seed(cfg["seed"] + rank)
     carried_opt = None
+    # Learned loss weighting, off by default: misc.loss_uncertainty_weighting / _channels / _lr.  The feature buffers
+    # are drawn on the CPU from the run's seed: the same on every rank.
+    lw = mdlw.LossWeighting(lwopt["channels"], seed=cfg["seed"], lr=lwopt["lr"], device="cuda") if lwopt["enabled"] else None
     if cfg["trainer"].get("load_path"):
         ckpt = torch.load(cfg["trainer"]["load_path"], map_location="cuda")
         sd = ckpt.get("state", {}).get("model", ckpt)
@@ -54,6 +59,8 @@ def train(cfg: dict):
         ignore = [k.split("/")[-1] for k in cfg["trainer"].get("load_ignore_keys", [])]
         sd = {k: v for k, v in sd.items() if not any(k == i.replace("dit.", "") for i in ignore)}
         model.dit.load_state_dict(sd, strict=bool(cfg["trainer"].get("load_strict_model_weights", True)) and not ignore)
+        # u(sigma) travels with the weights; its moments only when the optimiser state is carried too
+        mdlw.restore(lw, ckpt.get("state", {}), weights_only=carried_opt is None)
     ocfg = dict(cfg["optimizer"])
     ocfg.pop("_target_")
     # EMA of the weights (configs/res_512_*.yaml:4-9, diffusion.algorithms.ema.EMA): folded into the AdamW kernel.  The
@@ -101,7 +108,7 @@ def train(cfg: dict):
     diag_kw = {k: v for k, v in mdcfg.diagnostics_options(cfg).items() if v}
     diag_every = diag_kw.get("diagnostics_interval", 0)
     trainer = Trainer(model, opt, sched, clip_norm=clip, microbatch_size=int(cfg["trainer"]["device_train_microbatch_size"]),
-                      **monitor_kw, **diag_kw)
+                      **monitor_kw, **diag_kw, **(dict(loss_weighting=lw) if lw is not None else {}))
     save_every = parse_batches(cfg["trainer"].get("save_interval", "0ba"))
     folder = cfg["trainer"].get("save_folder")
     log_every = int(cfg.get("misc", {}).get("log_interval", 10))
@@ -113,6 +120,7 @@ def train(cfg: dict):
         ck = torch.load(latest, map_location="cuda")
         model.dit.load_state_dict({k[len("dit."):]: v for k, v in ck["state"]["model"].items()})
         opt.load_state_dict(ck["optimizer"])
+        mdlw.restore(lw, ck["state"])
         start = int(ck["batch"])
         trainer.batches_seen = start
         if ck.get("loader") is not None and hasattr(loader, "load_state_dict"):
@@ -166,11 +174,8 @@ def train(cfg: dict):
         if rank == 0 and (step + 1) % log_every == 0:
             torch.cuda.synchronize()
             dt, t_last = time.time() - t_last, time.time()
-            line = {"batch": step + 1, "loss": float(loss), "lr": opt.lr * sched.factor(step),
-                    "samples_per_sec": ds["train_batch_size"] * log_every / dt}
-            if skip_nonfinite:
-                line["skipped_steps"] = skipped_logged
-            print(json.dumps(line), flush=True)
+            print(json.dumps(log_line(step + 1, loss, opt.lr * sched.factor(step), ds["train_batch_size"] * log_every / dt,
+                                      skipped_logged if skip_nonfinite else None, trainer)), flush=True)
         snap_now = bool(folder and snap_every and (step + 1) % snap_every == 0)
         if snap_now or (folder and save_every and (step + 1) % save_every == 0):
             trainer.consolidate()                                  # a collective under the sharded optimiser: every rank calls it
@@ -179,15 +184,35 @@ def train(cfg: dict):
         if rank == 0 and folder and save_every and (step + 1) % save_every == 0:
             os.makedirs(folder, exist_ok=True)
             tmp = os.path.join(folder, "latest.pt.tmp")
-            ema_sd = opt.ema_state_dict()
-            state = {"model": {"dit." + k: v for k, v in model.dit.state_dict().items()}}
-            if ema_sd is not None:                                  # the EMA weights as a loadable model state (evaluation / export)
-                state["ema_model"] = {"dit." + k: v for k, v in ema_sd.items()}
-            torch.save({"state": state,
+            torch.save({"state": checkpoint_state(model, opt),
                         "optimizer": opt.state_dict(), "batch": step + 1, "rng_cuda": torch.cuda.get_rng_state(),
                         "loader": loader.state_dict() if hasattr(loader, "state_dict") else None}, tmp)
             os.replace(tmp, os.path.join(folder, "latest.pt"))      # never leave a truncated latest.pt behind
     return trainer
+
+
+def log_line(batch: int, loss, lr: float, samples_per_sec: float, skipped=None, trainer=None) -> dict:
+    """The periodic log line.  `loss` is the raw EDM loss with or without the learned loss weighting (the curves stay comparable);
+    `weighted_loss`, the objective the weighting minimises, appears only when the feature is on."""
+    line = {"batch": batch, "loss": float(loss), "lr": lr, "samples_per_sec": samples_per_sec}
+    if skipped is not None:
+        line["skipped_steps"] = skipped
+    obj = trainer.weighted_objective() if trainer is not None and getattr(trainer, "loss_weighting", None) is not None else None
+    if obj is not None:
+        line["weighted_loss"] = float(obj)
+    return line
+
+
+def checkpoint_state(model, opt) -> dict:
+    """The `state` entry of a checkpoint: the weights under Composer's `dit.*` keys, the EMA weights once they exist, and -- only when
+    the learned loss weighting is on -- `loss_weighting` (feature buffers, w, moments; dit.state_dict() itself is unchanged)."""
+    state = {"model": {"dit." + k: v for k, v in model.dit.state_dict().items()}}
+    ema_sd = opt.ema_state_dict()
+    if ema_sd is not None:                                          # the EMA weights as a loadable model state (evaluation / export)
+        state["ema_model"] = {"dit." + k: v for k, v in ema_sd.items()}
+    if getattr(model, "loss_weighting", None) is not None:
+        state["loss_weighting"] = model.loss_weighting.state_dict()
+    return state
 
 
 def save_posthoc_snapshots(opt, folder: str, step: int, profiles=None) -> list:
