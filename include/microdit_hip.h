@@ -404,6 +404,28 @@ int md_edm_solver_update(const double* x_in, const float* F, double* hist, doubl
 int md_edm_solver_update_tok(const double* x_in, const void* tok_bf16, double* hist, double* x_next, int64_t B, int32_t C, int32_t H,
                              int32_t W, int32_t p, float cfg, int32_t has_uncond, double t_in, float sigma_data, double a, double b,
                              double c1, double c2, hipStream_t stream);
+/* Autoguidance (Karras et al. 2024, "Guiding a diffusion model with a bad version of itself"): the two-pointer forms of the four
+ * update entry points above.  The second operand of the guidance combine F = Fg + cfg * (Fm - Fg) is the output of a second, weaker
+ * network in a buffer of its own -- F_guide: n floats; tok_guide_bf16: [B*T, C*p*p] bf16 rows -- in place of the unconditional half
+ * behind the conditional one (`has_uncond`), so two batch-B outputs need no concatenation.
+ *   - Each gives the bits of its counterpart called with has_uncond = 1 on the concatenation [F; F_guide] ([tok; tok_guide]): the same
+ *     kernels run, with the same fp32 combine (one fma), fp32 preconditioning and fp64 state.
+ *   - The token forms take the 16-byte vector path only when C*p*p is a multiple of 8 and BOTH token pointers are 16-byte aligned;
+ *     otherwise the whole launch goes element by element.  A misaligned pointer is never read with a vector load.
+ *   - A null pointer (the guide's included), a non-positive size, H % p or W % p non-zero, or t_in <= 0 returns MD_BAD_ARG and launches
+ *     nothing.
+ *   - Aliasing as above: x_next may alias x_in / x_hat; the two network outputs are only read and may alias each other. */
+int md_edm_heun_update_guide(const double* x_hat, const double* x_in, const float* F, const float* F_guide, double* d_cur, double* x_next,
+                             int64_t n, float cfg, double t_in, double t_hat, double t_next, float sigma_data, int32_t second,
+                             hipStream_t stream);
+int md_edm_solver_update_guide(const double* x_in, const float* F, const float* F_guide, double* hist, double* x_next, int64_t n, float cfg,
+                               double t_in, float sigma_data, double a, double b, double c1, double c2, hipStream_t stream);
+int md_edm_heun_update_guide_tok(const double* x_hat, const double* x_in, const void* tok_bf16, const void* tok_guide_bf16, double* d_cur,
+                                 double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg, double t_in, double t_hat,
+                                 double t_next, float sigma_data, int32_t second, hipStream_t stream);
+int md_edm_solver_update_guide_tok(const double* x_in, const void* tok_bf16, const void* tok_guide_bf16, double* hist, double* x_next,
+                                   int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg, double t_in, float sigma_data, double a,
+                                   double b, double c1, double c2, hipStream_t stream);
 /* Stochastic churn (model.py:254-258): x_hat = x + coef * noise in fp64, one fma per element; coef = sqrt(t_hat^2 - t_cur^2) * S_noise
  * from the host.  x_hat may alias x. */
 int md_edm_churn(const double* x, const double* noise, double* x_hat, int64_t n, double coef, hipStream_t stream);

@@ -206,23 +206,26 @@ __global__ __launch_bounds__(256) void sampler_input_kernel(const double* x, flo
     }
 }
 
-__global__ __launch_bounds__(256) void heun_update_kernel(const double* x_hat, const double* x_in, const float* F, double* d_cur,
-                                                          double* x_next, int64_t n, float cfg, int has_uncond, double t_in, double t_hat,
+// The second operand of the guidance combine is a pointer of its own (Fu / tok_u; NULL: no combine): the unconditional half of a
+// doubled batch (F + n, the has_uncond entry points) or the output of a second, weaker network (the _guide entry points).  One set
+// of kernels serves both, so the two give the same bits by construction.
+__global__ __launch_bounds__(256) void heun_update_kernel(const double* x_hat, const double* x_in, const float* F, const float* Fu,
+                                                          double* d_cur, double* x_next, int64_t n, float cfg, double t_in, double t_hat,
                                                           double t_next, float sigma_data, int second) {
     float c_skip, c_out;
     heun_coef(t_in, sigma_data, c_skip, c_out);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double xi = x_in[i];
         float f = F[i];
-        if (has_uncond) f = cfg_combine(f, F[n + i], cfg);
+        if (Fu) f = cfg_combine(f, Fu[i], cfg);
         double d;
         x_next[i] = heun_element(xi, x_hat[i], f, c_skip, c_out, t_in, t_hat, t_next, second, second ? d_cur[i] : 0.0, d);
         if (!second) d_cur[i] = d;
     }
 }
 
-__global__ __launch_bounds__(256) void solver_update_kernel(const double* x_in, const float* F, double* hist, double* x_next, int64_t n,
-                                                            float cfg, int has_uncond, double t_in, float sigma_data, double a, double b,
+__global__ __launch_bounds__(256) void solver_update_kernel(const double* x_in, const float* F, const float* Fu, double* hist, double* x_next,
+                                                            int64_t n, float cfg, double t_in, float sigma_data, double a, double b,
                                                             double c1, double c2) {
     float c_skip, c_out;
     heun_coef(t_in, sigma_data, c_skip, c_out);
@@ -230,7 +233,7 @@ __global__ __launch_bounds__(256) void solver_update_kernel(const double* x_in, 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double xi = x_in[i];
         float f = F[i];
-        if (has_uncond) f = cfg_combine(f, F[n + i], cfg);
+        if (Fu) f = cfg_combine(f, Fu[i], cfg);
         double den;
         x_next[i] = solver_element(xi, f, c_skip, c_out, a, b, c1, c2, use_hist ? hist[i] : 0.0, den);
         hist[i] = den;
@@ -294,20 +297,22 @@ __global__ __launch_bounds__(256) void sampler_patchify_kernel(const double* x, 
     }
 }
 
-// F[b, c, ti*p+ph, tj*p+pw] = tok[row, (ph*p + pw)*C + c] (the unconditional half: row + B*T), then heun_element on that pixel
+// F[b, c, ti*p+ph, tj*p+pw] = tok[row, (ph*p + pw)*C + c] (the second operand: the same row of tok_u), then heun_element on that pixel
 template <bool VEC>
-__global__ __launch_bounds__(256) void heun_update_tok_kernel(const double* x_hat, const double* x_in, const bf16* tok, double* d_cur,
-                                                              double* x_next, int64_t B, int C, int H, int W, int p, float cfg,
-                                                              int has_uncond, double t_in, double t_hat, double t_next,
-                                                              float sigma_data, int second) {
+__global__ __launch_bounds__(256) void heun_update_tok_kernel(const double* x_hat, const double* x_in, const bf16* tok, const bf16* tok_u,
+                                                              double* d_cur, double* x_next, int64_t B, int C, int H, int W, int p,
+                                                              float cfg, double t_in, double t_hat, double t_next, float sigma_data,
+                                                              int second) {
     float c_skip, c_out;
     heun_coef(t_in, sigma_data, c_skip, c_out);
     const int gh = H / p, gw = W / p, pv = C * p * p, nseg = (pv + 7) / 8;
     const int64_t rows = B * gh * gw, total = rows * nseg;
+    const bool has_uncond = tok_u != nullptr;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const tok_item t = tok_item_of(i, gh, gw, nseg);
-        const bf16* fc = tok + t.row * pv + t.e0;
-        const bf16* fu = fc + rows * pv;
+        const int64_t off = t.row * pv + t.e0;
+        const bf16* fc = tok + off;
+        const bf16* fu = has_uncond ? tok_u + off : fc;
         U128 vc, vu;
         if (VEC) {
             vc.h = ld_bf16x8(fc);
@@ -339,18 +344,20 @@ __global__ __launch_bounds__(256) void heun_update_tok_kernel(const double* x_ha
 
 // The token-space form of solver_update_kernel: F as in heun_update_tok_kernel, then solver_element on that pixel
 template <bool VEC>
-__global__ __launch_bounds__(256) void solver_update_tok_kernel(const double* x_in, const bf16* tok, double* hist, double* x_next, int64_t B,
-                                                                int C, int H, int W, int p, float cfg, int has_uncond, double t_in,
+__global__ __launch_bounds__(256) void solver_update_tok_kernel(const double* x_in, const bf16* tok, const bf16* tok_u, double* hist, double* x_next,
+                                                                int64_t B, int C, int H, int W, int p, float cfg, double t_in,
                                                                 float sigma_data, double a, double b, double c1, double c2) {
     float c_skip, c_out;
     heun_coef(t_in, sigma_data, c_skip, c_out);
     const bool use_hist = c2 != 0.0;
     const int gh = H / p, gw = W / p, pv = C * p * p, nseg = (pv + 7) / 8;
     const int64_t rows = B * gh * gw, total = rows * nseg;
+    const bool has_uncond = tok_u != nullptr;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const tok_item t = tok_item_of(i, gh, gw, nseg);
-        const bf16* fc = tok + t.row * pv + t.e0;
-        const bf16* fu = fc + rows * pv;
+        const int64_t off = t.row * pv + t.e0;
+        const bf16* fc = tok + off;
+        const bf16* fu = has_uncond ? tok_u + off : fc;
         U128 vc, vu;
         if (VEC) {
             vc.h = ld_bf16x8(fc);
@@ -380,6 +387,57 @@ __global__ __launch_bounds__(256) void solver_update_tok_kernel(const double* x_
 }
 
 inline bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
+
+// The launches behind the sampler update entry points (arguments checked by the callers).  Fu / tok_u: the second operand of the
+// guidance combine, NULL for none.  The token forms take the 16-byte path only when the row width is a multiple of 8 and BOTH token
+// pointers are 16-byte aligned: one misaligned pointer sends the whole launch element by element, so it is never read as a vector.
+inline int64_t uncond_offset(int64_t B, int C, int H, int W, int p) { return B * (H / p) * (W / p) * C * p * p; }
+
+inline int launch_heun_update(const double* x_hat, const double* x_in, const float* F, const float* Fu, double* d_cur, double* x_next,
+                              int64_t n, float cfg, double t_in, double t_hat, double t_next, float sigma_data, int second, hipStream_t st) {
+    hipLaunchKernelGGL(heun_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_hat, x_in, F, Fu, d_cur, x_next, n, cfg, t_in, t_hat, t_next,
+                       sigma_data, second);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+inline int launch_solver_update(const double* x_in, const float* F, const float* Fu, double* hist, double* x_next, int64_t n, float cfg,
+                                double t_in, float sigma_data, double a, double b, double c1, double c2, hipStream_t st) {
+    hipLaunchKernelGGL(solver_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_in, F, Fu, hist, x_next, n, cfg, t_in, sigma_data, a, b, c1,
+                       c2);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+inline int launch_heun_update_tok(const double* x_hat, const double* x_in, const bf16* tok, const bf16* tok_u, double* d_cur, double* x_next,
+                                  int64_t B, int C, int H, int W, int p, float cfg, double t_in, double t_hat, double t_next,
+                                  float sigma_data, int second, hipStream_t st) {
+    const int pv = C * p * p;
+    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
+    if (pv % 8 == 0 && aligned16(tok) && aligned16(tok_u))
+        hipLaunchKernelGGL(heun_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, tok, tok_u, d_cur, x_next, B, C,
+                           H, W, p, cfg, t_in, t_hat, t_next, sigma_data, second);
+    else
+        hipLaunchKernelGGL(heun_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, tok, tok_u, d_cur, x_next, B, C,
+                           H, W, p, cfg, t_in, t_hat, t_next, sigma_data, second);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+inline int launch_solver_update_tok(const double* x_in, const bf16* tok, const bf16* tok_u, double* hist, double* x_next, int64_t B, int C,
+                                    int H, int W, int p, float cfg, double t_in, float sigma_data, double a, double b, double c1, double c2,
+                                    hipStream_t st) {
+    const int pv = C * p * p;
+    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
+    if (pv % 8 == 0 && aligned16(tok) && aligned16(tok_u))
+        hipLaunchKernelGGL(solver_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_in, tok, tok_u, hist, x_next, B, C, H, W,
+                           p, cfg, t_in, sigma_data, a, b, c1, c2);
+    else
+        hipLaunchKernelGGL(solver_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_in, tok, tok_u, hist, x_next, B, C, H, W,
+                           p, cfg, t_in, sigma_data, a, b, c1, c2);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
 
 }  // namespace
 
@@ -478,10 +536,15 @@ extern "C" int md_edm_heun_update(const double* x_hat, const double* x_in, const
                                   float cfg, int32_t has_uncond, double t_in, double t_hat, double t_next, float sigma_data,
                                   int32_t second, hipStream_t st) {
     if (!x_hat || !x_in || !F || !d_cur || !x_next || n <= 0 || t_in <= 0) return MD_BAD_ARG;
-    hipLaunchKernelGGL(heun_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_hat, x_in, F, d_cur, x_next, n, cfg, has_uncond, t_in,
-                       t_hat, t_next, sigma_data, second);
-    MD_LAUNCH_CHECK();
-    return 0;
+    return launch_heun_update(x_hat, x_in, F, has_uncond ? F + n : nullptr, d_cur, x_next, n, cfg, t_in, t_hat, t_next, sigma_data, second,
+                              st);
+}
+
+extern "C" int md_edm_heun_update_guide(const double* x_hat, const double* x_in, const float* F, const float* F_guide, double* d_cur,
+                                        double* x_next, int64_t n, float cfg, double t_in, double t_hat, double t_next, float sigma_data,
+                                        int32_t second, hipStream_t st) {
+    if (!x_hat || !x_in || !F || !F_guide || !d_cur || !x_next || n <= 0 || t_in <= 0) return MD_BAD_ARG;
+    return launch_heun_update(x_hat, x_in, F, F_guide, d_cur, x_next, n, cfg, t_in, t_hat, t_next, sigma_data, second, st);
 }
 
 extern "C" int md_edm_sampler_patchify(const double* x, void* patches_bf16, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p,
@@ -505,26 +568,33 @@ extern "C" int md_edm_heun_update_tok(const double* x_hat, const double* x_in, c
     if (!x_hat || !x_in || !tok_bf16 || !d_cur || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
         t_in <= 0)
         return MD_BAD_ARG;
-    const int pv = C * p * p;
-    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
-    if (pv % 8 == 0 && aligned16(tok_bf16))
-        hipLaunchKernelGGL(heun_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, (const bf16*)tok_bf16, d_cur,
-                           x_next, B, C, H, W, p, cfg, has_uncond, t_in, t_hat, t_next, sigma_data, second);
-    else
-        hipLaunchKernelGGL(heun_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, (const bf16*)tok_bf16, d_cur,
-                           x_next, B, C, H, W, p, cfg, has_uncond, t_in, t_hat, t_next, sigma_data, second);
-    MD_LAUNCH_CHECK();
-    return 0;
+    const bf16* tok = (const bf16*)tok_bf16;
+    return launch_heun_update_tok(x_hat, x_in, tok, has_uncond ? tok + uncond_offset(B, C, H, W, p) : nullptr, d_cur, x_next, B, C, H, W, p,
+                                  cfg, t_in, t_hat, t_next, sigma_data, second, st);
+}
+
+extern "C" int md_edm_heun_update_guide_tok(const double* x_hat, const double* x_in, const void* tok_bf16, const void* tok_guide_bf16,
+                                            double* d_cur, double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg,
+                                            double t_in, double t_hat, double t_next, float sigma_data, int32_t second, hipStream_t st) {
+    if (!x_hat || !x_in || !tok_bf16 || !tok_guide_bf16 || !d_cur || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p ||
+        W % p || t_in <= 0)
+        return MD_BAD_ARG;
+    return launch_heun_update_tok(x_hat, x_in, (const bf16*)tok_bf16, (const bf16*)tok_guide_bf16, d_cur, x_next, B, C, H, W, p, cfg, t_in,
+                                  t_hat, t_next, sigma_data, second, st);
 }
 
 extern "C" int md_edm_solver_update(const double* x_in, const float* F, double* hist, double* x_next, int64_t n, float cfg,
                                     int32_t has_uncond, double t_in, float sigma_data, double a, double b, double c1, double c2,
                                     hipStream_t st) {
     if (!x_in || !F || !hist || !x_next || n <= 0 || t_in <= 0) return MD_BAD_ARG;
-    hipLaunchKernelGGL(solver_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_in, F, hist, x_next, n, cfg, has_uncond, t_in, sigma_data,
-                       a, b, c1, c2);
-    MD_LAUNCH_CHECK();
-    return 0;
+    return launch_solver_update(x_in, F, has_uncond ? F + n : nullptr, hist, x_next, n, cfg, t_in, sigma_data, a, b, c1, c2, st);
+}
+
+extern "C" int md_edm_solver_update_guide(const double* x_in, const float* F, const float* F_guide, double* hist, double* x_next, int64_t n,
+                                          float cfg, double t_in, float sigma_data, double a, double b, double c1, double c2,
+                                          hipStream_t st) {
+    if (!x_in || !F || !F_guide || !hist || !x_next || n <= 0 || t_in <= 0) return MD_BAD_ARG;
+    return launch_solver_update(x_in, F, F_guide, hist, x_next, n, cfg, t_in, sigma_data, a, b, c1, c2, st);
 }
 
 extern "C" int md_edm_solver_update_tok(const double* x_in, const void* tok_bf16, double* hist, double* x_next, int64_t B, int32_t C,
@@ -532,16 +602,19 @@ extern "C" int md_edm_solver_update_tok(const double* x_in, const void* tok_bf16
                                         double a, double b, double c1, double c2, hipStream_t st) {
     if (!x_in || !tok_bf16 || !hist || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p || t_in <= 0)
         return MD_BAD_ARG;
-    const int pv = C * p * p;
-    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
-    if (pv % 8 == 0 && aligned16(tok_bf16))
-        hipLaunchKernelGGL(solver_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_in, (const bf16*)tok_bf16, hist, x_next,
-                           B, C, H, W, p, cfg, has_uncond, t_in, sigma_data, a, b, c1, c2);
-    else
-        hipLaunchKernelGGL(solver_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_in, (const bf16*)tok_bf16, hist, x_next,
-                           B, C, H, W, p, cfg, has_uncond, t_in, sigma_data, a, b, c1, c2);
-    MD_LAUNCH_CHECK();
-    return 0;
+    const bf16* tok = (const bf16*)tok_bf16;
+    return launch_solver_update_tok(x_in, tok, has_uncond ? tok + uncond_offset(B, C, H, W, p) : nullptr, hist, x_next, B, C, H, W, p, cfg,
+                                    t_in, sigma_data, a, b, c1, c2, st);
+}
+
+extern "C" int md_edm_solver_update_guide_tok(const double* x_in, const void* tok_bf16, const void* tok_guide_bf16, double* hist,
+                                              double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg, double t_in,
+                                              float sigma_data, double a, double b, double c1, double c2, hipStream_t st) {
+    if (!x_in || !tok_bf16 || !tok_guide_bf16 || !hist || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
+        t_in <= 0)
+        return MD_BAD_ARG;
+    return launch_solver_update_tok(x_in, (const bf16*)tok_bf16, (const bf16*)tok_guide_bf16, hist, x_next, B, C, H, W, p, cfg, t_in,
+                                    sigma_data, a, b, c1, c2, st);
 }
 
 extern "C" int md_edm_churn(const double* x, const double* noise, double* x_hat, int64_t n, double coef, hipStream_t st) {

@@ -226,6 +226,14 @@ _sig("md_edm_solver_update", P, P, P, P, I64, F32, I32, ctypes.c_double, F32, ct
 _sig("md_edm_solver_update_tok", P, P, P, P, I64, I32, I32, I32, I32, F32, I32, ctypes.c_double, F32, ctypes.c_double, ctypes.c_double,
      ctypes.c_double, ctypes.c_double, P)
 _sig("md_edm_churn", P, P, P, I64, ctypes.c_double, P)
+# autoguidance: the two-pointer forms of the four update entry points (the second network's output in a buffer of its own)
+_sig("md_edm_heun_update_guide", P, P, P, P, P, P, I64, F32, ctypes.c_double, ctypes.c_double, ctypes.c_double, F32, I32, P)
+_sig("md_edm_solver_update_guide", P, P, P, P, P, I64, F32, ctypes.c_double, F32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+     ctypes.c_double, P)
+_sig("md_edm_heun_update_guide_tok", P, P, P, P, P, P, I64, I32, I32, I32, I32, F32, ctypes.c_double, ctypes.c_double, ctypes.c_double, F32,
+     I32, P)
+_sig("md_edm_solver_update_guide_tok", P, P, P, P, P, I64, I32, I32, I32, I32, F32, ctypes.c_double, F32, ctypes.c_double, ctypes.c_double,
+     ctypes.c_double, ctypes.c_double, P)
 _sig("md_sumsq", P, I32, I64, P, P)
 _sig("md_sumsq_finish", P, I64, P, P)
 _sig("md_checksum_u16", P, I64, P, P)

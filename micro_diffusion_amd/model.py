@@ -242,7 +242,8 @@ class LatentDiffusion(nn.Module):
 
     @torch.no_grad()
     def edm_sampler_loop(self, x, y, steps: Optional[int] = None, cfg: float = 1.0, fused: Optional[bool] = None,
-                         cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, **kwargs):
+                         cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
+                         guide_captions: str = "same", **kwargs):
         """EDM sampler, fp64 state (model.py:231-297).  `fused` (None = whenever possible) selects the loop whose per-step arithmetic
         runs in fused HIP kernels; False keeps the reference's tensor-op formulation (generic forward functions).
         `cond_cache` (None = the environment variable MD_SAMPLER_CACHE, default off): encode the captions once for the whole run
@@ -250,10 +251,16 @@ class LatentDiffusion(nn.Module):
         `sampler`: "heun" (the reference's 2nd-order loop, 2 * steps - 1 network evaluations), "euler" or "dpmpp_2m" (DPM-Solver++(2M),
         2nd order); the last two take one evaluation per step (samplers.py).  S_churn > 0 is defined for heun and euler.
         `guidance_interval` = (sigma_lo, sigma_hi): an evaluation at noise level sigma is guided (batch doubled) only while
-        sigma_lo <= sigma <= sigma_hi; outside it the conditional half runs alone.  None: every evaluation is guided when cfg > 1."""
+        sigma_lo <= sigma <= sigma_hi; outside it the conditional half runs alone.  None: every evaluation is guided when cfg > 1.
+        `guide`: a second, weaker DiT on the same device (autoguidance, Karras et al. 2024).  cfg is then the autoguidance weight w:
+        a guided evaluation runs this model at batch B, then the guide at batch B on the same network input, and the update combines
+        F = F_guide + w * (F_main - F_guide); no evaluation is batch-doubled.  Unguided evaluations (cfg <= 1, outside the interval)
+        never run the guide.  `guide_captions`: "same" (the guide sees the captions) or "null" (zeroed captions; with guide = this
+        model's own dit that is classifier-free guidance as two batch-B launches)."""
         ec = self.edm_config
         samplers.check_sampler(sampler, ec.S_churn)
         interval = samplers.guidance_interval_bounds(guidance_interval)
+        samplers.check_guide(self.dit, guide, guide_captions)
         can_fuse = not kwargs and x.is_cuda
         cond_cache = sampler_cache_enabled(cond_cache)
         if cond_cache and (fused is False or not can_fuse):
@@ -262,8 +269,11 @@ class LatentDiffusion(nn.Module):
             fused = can_fuse
         if fused:
             assert can_fuse, "the fused sampler needs CUDA tensors and no extra forward arguments"
-            return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval)
-        fwd = partial(self.dit.forward, cfg=cfg) if cfg > 1.0 else self.dit.forward
+            return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, guide, guide_captions == "null")
+        if guide is not None:
+            fwd = self._autoguided_forward(guide, torch.zeros_like(y) if guide_captions == "null" else y, cfg) if cfg > 1.0 else self.dit.forward
+        else:
+            fwd = partial(self.dit.forward, cfg=cfg) if cfg > 1.0 else self.dit.forward
 
         def denoise(xs, sigma):
             f = fwd if interval is None or interval[0] <= float(sigma) <= interval[1] else self.dit.forward
@@ -296,8 +306,18 @@ class LatentDiffusion(nn.Module):
                 x_next = x_hat + (t_next - t_hat) * (0.5 * d_cur + 0.5 * d_prime)
         return x_next.to(torch.float32)
 
+    def _autoguided_forward(self, guide, y_guide, w: float):
+        """The forward function of an autoguided evaluation for model_forward_wrapper: both networks on the same input at batch B, the
+        guide with its own captions, combined in fp32 as the update kernels do (F = F_guide + w * (F_main - F_guide))."""
+        def fwd(x, t, y, **kwargs):
+            fm = self.dit.forward_without_cfg(x, t, y, **kwargs)["sample"].to(torch.float32)
+            fg = guide.forward_without_cfg(x, t, y_guide, **kwargs)["sample"].to(torch.float32)
+            return {"sample": fg + w * (fm - fg)}
+        return fwd
+
     @torch.no_grad()
-    def _edm_sampler_fused(self, x, y, steps: Optional[int], cfg: float, cond_cache: bool = False, sampler: str = "heun", interval=None):
+    def _edm_sampler_fused(self, x, y, steps: Optional[int], cfg: float, cond_cache: bool = False, sampler: str = "heun", interval=None,
+                           guide=None, guide_null: bool = False):
         """The same loops with everything around the network evaluations in fused HIP kernels: md_edm_sampler_input (c_in scaling +
         guidance batch doubling) and md_edm_heun_update (guidance combine + preconditioning + fp64 Euler / Heun update) or, for
         euler / dpmpp_2m, md_edm_solver_update (the same with the linear-multistep update of samplers.solver_coefficients).
@@ -305,7 +325,11 @@ class LatentDiffusion(nn.Module):
         cond_cache: the captions (doubled under guidance) are encoded once (dit.encode_condition) and every evaluation runs
         md_edm_sampler_patchify -> engine.forward(patches=, cond=) -> md_edm_heun_update_tok / md_edm_solver_update_tok on the token
         output: no caption-side work per evaluation and no fp32 image between the fp64 state and the network's bf16 rows.
-        interval: evaluations outside it run the conditional half alone (network batch B) on leading-row views of the same buffers."""
+        interval: evaluations outside it run the conditional half alone (network batch B) on leading-row views of the same buffers.
+        guide: nothing is doubled.  A guided evaluation writes the network input once (dup = 0), runs self.dit and then the guide on it
+        at batch B (the guide with its own captions / its own Conditioning, encoded by the guide) and hands the two outputs to
+        md_edm_*_update_guide(_tok).  Both outputs are fresh allocations that network() returns together, so main's is alive and
+        untouched while the guide runs and until the update has been enqueued."""
         ec, L, st = self.edm_config, hip.lib(), torch.cuda.current_stream().cuda_stream
         n = ec.num_steps if steps is None else steps
         idx = torch.arange(n, dtype=torch.float64)
@@ -319,39 +343,59 @@ class LatentDiffusion(nn.Module):
         B, numel = x.shape[0], x.numel()
         x_cur = (x.to(torch.float64) * t_steps[0]).contiguous()
         x_nxt, d_cur = torch.empty_like(x_cur), torch.empty_like(x_cur)
-        y2 = torch.cat([y, torch.zeros_like(y)], 0) if guided else y
-        Bn = 2 * B if guided else B
+        auto = guide is not None and guided         # with a guide the second operand comes from it: the batch is never doubled
+        y2 = torch.cat([y, torch.zeros_like(y)], 0) if guided and not auto else y
+        Bn = 2 * B if guided and not auto else B
+        if auto:
+            y_g = torch.zeros_like(y) if guide_null else y
         if cond_cache:
             dit = self.dit
             C, H, W, p = x.shape[1], x.shape[2], x.shape[3], dit.patch_size
             cond = dit.encode_condition(y2)
+            if auto:
+                cond_g = guide.encode_condition(y_g)
             patches = torch.empty(Bn * (H // p) * (W // p), dit.config.patch_vec, device=x.device, dtype=torch.bfloat16)
         else:
             net_in = torch.empty((Bn,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
 
         def network(xs, sigma):
-            """(network output, dup) for state xs at noise level sigma: the fp32 image F, or (cond_cache) the bf16 token rows; dup = 1
-            when the evaluation is guided: the batch is doubled and the output holds the unconditional half behind the conditional."""
+            """(network output, dup, guide output) for state xs at noise level sigma: the fp32 image F, or (cond_cache) the bf16 token
+            rows; dup = 1 when the evaluation is guided by batch doubling: the output holds the unconditional half behind the
+            conditional.  With a guide dup is 0 and a guided evaluation returns the guide's output as well (else None)."""
             c_noise = float(np.log(np.float32(sigma)) / 4)
-            dup = 1 if guided and samplers.is_guided(sigma, cfg, interval) else 0
+            g_eval = guided and samplers.is_guided(sigma, cfg, interval)
+            dup = 1 if g_eval and not auto else 0
             Be = 2 * B if dup else B
             if cond_cache:
                 pt = patches if Be == Bn else patches[:B * (H // p) * (W // p)]
                 hip.check(L.md_edm_sampler_patchify(xs.data_ptr(), pt.data_ptr(), B, C, H, W, p, float(sigma), ec.sigma_data, dup, st),
                           "md_edm_sampler_patchify")
                 t = torch.full((Be,), c_noise, device=x.device, dtype=torch.float32)
-                return dit._engine.forward(None, t, None, cond=cond.narrow(Be), patches=pt).out_tok, dup
+                F = dit._engine.forward(None, t, None, cond=cond.narrow(Be), patches=pt).out_tok
+                Fg = guide._engine.forward(None, t, None, cond=cond_g, patches=pt).out_tok if auto and g_eval else None
+                return F, dup, Fg
             hip.check(L.md_edm_sampler_input(xs.data_ptr(), net_in.data_ptr(), numel, float(sigma), ec.sigma_data, dup, st),
                       "md_edm_sampler_input")
             t = torch.full((1,), c_noise, device=x.device, dtype=torch.float32)
             if Be == Bn:
-                return self.dit.forward_without_cfg(net_in, t, y2, 0)["sample"].contiguous(), dup
-            return self.dit.forward_without_cfg(net_in[:B], t, y, 0)["sample"].contiguous(), dup
+                F = self.dit.forward_without_cfg(net_in, t, y2, 0)["sample"].contiguous()
+            else:
+                F = self.dit.forward_without_cfg(net_in[:B], t, y, 0)["sample"].contiguous()
+            Fg = guide.forward_without_cfg(net_in, t, y_g, 0)["sample"].to(torch.float32).contiguous() if auto and g_eval else None
+            return F, dup, Fg
 
         def update(Fd, x_in, t_in, t_hat, t_next, second):
             """x_nxt (and, on the first half-step, d_cur) from x_cur, the evaluated state x_in and the network output F."""
-            F, dup = Fd
-            if cond_cache:
+            F, dup, Fg = Fd
+            if Fg is not None and cond_cache:
+                hip.check(L.md_edm_heun_update_guide_tok(x_cur.data_ptr(), x_in.data_ptr(), F.data_ptr(), Fg.data_ptr(), d_cur.data_ptr(),
+                                                         x_nxt.data_ptr(), B, C, H, W, p, float(cfg), t_in, t_hat, t_next, ec.sigma_data,
+                                                         second, st), "md_edm_heun_update_guide_tok")
+            elif Fg is not None:
+                hip.check(L.md_edm_heun_update_guide(x_cur.data_ptr(), x_in.data_ptr(), F.data_ptr(), Fg.data_ptr(), d_cur.data_ptr(),
+                                                     x_nxt.data_ptr(), numel, float(cfg), t_in, t_hat, t_next, ec.sigma_data, second, st),
+                          "md_edm_heun_update_guide")
+            elif cond_cache:
                 hip.check(L.md_edm_heun_update_tok(x_cur.data_ptr(), x_in.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(),
                                                    B, C, H, W, p, float(cfg), dup, t_in, t_hat, t_next, ec.sigma_data, second, st),
                           "md_edm_heun_update_tok")
@@ -361,8 +405,15 @@ class LatentDiffusion(nn.Module):
 
         def solver_update(Fd, t_in, coef):
             """x_nxt = a x_cur + b (c1 D - c2 hist), hist = D; d_cur is the history buffer."""
-            F, dup = Fd
-            if cond_cache:
+            F, dup, Fg = Fd
+            if Fg is not None and cond_cache:
+                hip.check(L.md_edm_solver_update_guide_tok(x_cur.data_ptr(), F.data_ptr(), Fg.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(),
+                                                           B, C, H, W, p, float(cfg), t_in, ec.sigma_data, *coef, st),
+                          "md_edm_solver_update_guide_tok")
+            elif Fg is not None:
+                hip.check(L.md_edm_solver_update_guide(x_cur.data_ptr(), F.data_ptr(), Fg.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(), numel,
+                                                       float(cfg), t_in, ec.sigma_data, *coef, st), "md_edm_solver_update_guide")
+            elif cond_cache:
                 hip.check(L.md_edm_solver_update_tok(x_cur.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(), B, C, H, W, p,
                                                      float(cfg), dup, t_in, ec.sigma_data, *coef, st), "md_edm_solver_update_tok")
             else:
@@ -389,9 +440,11 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def generate(self, prompt: Optional[list] = None, tokenized_prompts=None, attention_mask=None, guidance_scale: float = 5.0,
                  num_inference_steps: int = 30, seed: Optional[int] = None, return_only_latents: bool = False,
-                 cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, **kwargs):
-        """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache, sampler and
-        guidance_interval: as in edm_sampler_loop."""
+                 cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
+                 guide_captions: str = "same", **kwargs):
+        """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache, sampler,
+        guidance_interval, guide and guide_captions: as in edm_sampler_loop (with a guide, guidance_scale is the autoguidance weight)."""
+        samplers.check_guide(self.dit, guide, guide_captions)
         assert prompt or tokenized_prompts is not None, "Must provide either prompt or tokenized prompts"
         device = next(self.dit.parameters()).device
         gen = torch.Generator(device=device)
@@ -405,7 +458,7 @@ class LatentDiffusion(nn.Module):
                                        attention_mask=attention_mask.to(device) if attention_mask is not None else None)[0]
         latents = torch.randn((len(emb), self.dit.in_channels, self.latent_res, self.latent_res), device=device, generator=gen)
         latents = self.edm_sampler_loop(latents, emb, num_inference_steps, cfg=guidance_scale, cond_cache=cond_cache, sampler=sampler,
-                                        guidance_interval=guidance_interval)
+                                        guidance_interval=guidance_interval, guide=guide, guide_captions=guide_captions)
         if return_only_latents:
             return latents
         image = self.vae.decode((latents / self.latent_scale).to(DATA_TYPES[self.dtype])).sample

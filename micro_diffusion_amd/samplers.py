@@ -42,8 +42,41 @@ def guidance_interval_bounds(guidance_interval) -> Optional[Tuple[float, float]]
 
 
 def is_guided(sigma: float, cfg: float, interval: Optional[Tuple[float, float]]) -> bool:
-    """Whether the evaluation at noise level sigma runs with classifier-free guidance (network batch 2B)."""
+    """Whether the evaluation at noise level sigma is guided: classifier-free guidance (network batch 2B) or, with a guide network,
+    autoguidance (both networks at batch B)."""
     return cfg > 1.0 and (interval is None or interval[0] <= sigma <= interval[1])
+
+
+GUIDE_CAPTIONS = ("same", "null")           # what an autoguidance guide is conditioned on: the captions, or zeroed captions
+GUIDE_GEOMETRY = ("in_channels", "patch_size", "input_size", "caption_channels")
+
+
+def _module_device(module):
+    params = getattr(module, "parameters", None)
+    first = next(iter(params()), None) if params is not None else None
+    return None if first is None else first.device
+
+
+def check_guide(main, guide, guide_captions: str = "same") -> None:
+    """Refuse, before anything is launched or allocated, an autoguidance request the sampler cannot run: an unknown `guide_captions`,
+    "null" without a guide, a guide whose latent / patch / caption geometry (config fields GUIDE_GEOMETRY) differs from main's -- the
+    two networks read the same network input and their outputs are combined element by element --, or a guide on another device.
+    A guide that is main itself is legal (with "same" the combine returns main's output for every weight)."""
+    if guide_captions not in GUIDE_CAPTIONS:
+        raise ValueError(f"unknown guide_captions {guide_captions!r}: choose one of {', '.join(GUIDE_CAPTIONS)}")
+    if guide is None:
+        if guide_captions != "same":
+            raise ValueError(f"guide_captions={guide_captions!r} needs a guide")
+        return
+    if guide is main:
+        return
+    for name in GUIDE_GEOMETRY:
+        a, b = getattr(main.config, name), getattr(guide.config, name)
+        if a != b:
+            raise ValueError(f"the guide's {name} ({b}) differs from the main network's ({a})")
+    da, db = _module_device(main), _module_device(guide)
+    if da != db:
+        raise ValueError(f"the guide is on {db}, the main network on {da}: both must be on the same device")
 
 
 def evaluation_sigmas(sampler: str, t_steps: Sequence[float]) -> List[float]:
