@@ -429,6 +429,21 @@ int md_edm_solver_update_guide_tok(const double* x_in, const void* tok_bf16, con
 /* Stochastic churn (model.py:254-258): x_hat = x + coef * noise in fp64, one fma per element; coef = sqrt(t_hat^2 - t_cur^2) * S_noise
  * from the host.  x_hat may alias x. */
 int md_edm_churn(const double* x, const double* noise, double* x_hat, int64_t n, double coef, hipStream_t stream);
+/* Image-conditioned sampling (SDEdit image-to-image, inpainting, RePaint resampling; opt-in): blend the known latents x0, brought to
+ * the noise level sigma of the state, into the fp64 sampler state x [B, C, HW], in place:
+ *   x[b,c,i] = fma(m, x[b,c,i], (1 - m) * k),  k = noise ? fma(sigma, noise[b,c,i], x0[b,c,i]) : x0[b,c,i],
+ *   m = (double)mask[(mask_B == 1 ? 0 : b), i]   (mask == NULL: m = 0, the whole state is replaced)
+ * mask: f32 [mask_B, HW] with values in [0, 1] (the caller's check), broadcast over the channels; 1 = generated, 0 = known.
+ *   - Explicit fmas, so m = 1 returns x and m = 0 returns k bit for bit.  Without a mask x is written and never read.
+ *   - One entry point for the SDEdit initialisation (mask = NULL, noise = the unit noise, sigma = the first executed level), the blend
+ *     at the start of an inpainting step (noise = a fresh draw, sigma = t_i) and the final paste (noise = NULL, sigma = 0).
+ *   - x may alias noise; x0 and mask are only read.  Two elements per lane (16-byte accesses) when HW is even and x, x0 and noise are
+ *     16-byte aligned, element by element otherwise.
+ *   - MD_BAD_ARG, nothing launched: x or x0 NULL; B, C or HW <= 0; a mask with mask_B not in {1, B}; noise == NULL with sigma != 0;
+ *     sigma negative or not finite.
+ * The RePaint jump back to level t_i is md_edm_churn(x, noise, x, n, sqrt(t_i^2 - t_next^2)). */
+int md_edm_blend_known(double* x, const double* x0, const double* noise, const float* mask, int64_t B, int32_t C, int64_t HW,
+                       int32_t mask_B, double sigma, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------- optimiser */
 /* Sum of squares of a gradient buffer (fp32, or bf16 when g_is_bf16), deterministic: workgroup b of a fixed grid writes

@@ -226,6 +226,8 @@ _sig("md_edm_solver_update", P, P, P, P, I64, F32, I32, ctypes.c_double, F32, ct
 _sig("md_edm_solver_update_tok", P, P, P, P, I64, I32, I32, I32, I32, F32, I32, ctypes.c_double, F32, ctypes.c_double, ctypes.c_double,
      ctypes.c_double, ctypes.c_double, P)
 _sig("md_edm_churn", P, P, P, I64, ctypes.c_double, P)
+# image-conditioned sampling (img2img, inpainting): blend the known latents, at the state's noise level, into the fp64 state (edit.hip)
+_sig("md_edm_blend_known", P, P, P, P, I64, I32, I64, I32, ctypes.c_double, P)
 # autoguidance: the two-pointer forms of the four update entry points (the second network's output in a buffer of its own)
 _sig("md_edm_heun_update_guide", P, P, P, P, P, P, I64, F32, ctypes.c_double, ctypes.c_double, ctypes.c_double, F32, I32, P)
 _sig("md_edm_solver_update_guide", P, P, P, P, P, I64, F32, ctypes.c_double, F32, ctypes.c_double, ctypes.c_double, ctypes.c_double,

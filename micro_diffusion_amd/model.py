@@ -243,7 +243,8 @@ class LatentDiffusion(nn.Module):
     @torch.no_grad()
     def edm_sampler_loop(self, x, y, steps: Optional[int] = None, cfg: float = 1.0, fused: Optional[bool] = None,
                          cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
-                         guide_captions: str = "same", **kwargs):
+                         guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
+                         **kwargs):
         """EDM sampler, fp64 state (model.py:231-297).  `fused` (None = whenever possible) selects the loop whose per-step arithmetic
         runs in fused HIP kernels; False keeps the reference's tensor-op formulation (generic forward functions).
         `cond_cache` (None = the environment variable MD_SAMPLER_CACHE, default off): encode the captions once for the whole run
@@ -256,11 +257,27 @@ class LatentDiffusion(nn.Module):
         a guided evaluation runs this model at batch B, then the guide at batch B on the same network input, and the update combines
         F = F_guide + w * (F_main - F_guide); no evaluation is batch-doubled.  Unguided evaluations (cfg <= 1, outside the interval)
         never run the guide.  `guide_captions`: "same" (the guide sees the captions) or "null" (zeroed captions; with guide = this
-        model's own dit that is classifier-free guidance as two batch-B launches)."""
+        model's own dit that is classifier-free guidance as two batch-B launches).
+        Image-conditioned sampling (this loop with fused=False is the definition, the fused loop follows it):
+        `init_latents` (fp32, the shape of x, in the sampler's space: VAE latents * latent_scale): image-to-image.  With
+        k = max(1, min(n, ceil(strength * n))) and i0 = n - k the state starts as init_latents + t_i0 * x and steps i0 ... n - 1 run;
+        euler / dpmpp_2m take their coefficients from the truncated schedule, so the first executed step has no history.
+        `strength` in (0, 1]: 1 runs every step (the start is then init_latents + sigma_max * x).
+        `inpaint_mask` ([B or 1, 1, H, W], [B or 1, H, W] or [H, W]; bool, or float in [0, 1]; broadcast over the channels): 1 = generate,
+        0 = keep init_latents, values between blend.  At the start of every executed step i, before the churn,
+        x_cur <- m * x_cur + (1 - m) * (init_latents + t_i * randn_like(x_cur)), and after the last step x <- m * x + (1 - m) * init_latents:
+        where m == 0 the result is init_latents bit for bit.  Heun's second evaluation is not re-blended: it sees the first half-step's
+        state as it is.  With a mask the churn draw is made only when S_churn > 0 (without one the loop keeps the reference's draw).
+        `resample` = r >= 1 (RePaint, Lugmayr et al. 2022; needs a mask; heun and euler): every step with t_next > 0 runs r times, and
+        after each repetition but the last x <- x + sqrt(t_i^2 - t_next^2) * randn_like(x) takes the state back to level t_i.  Draws of one
+        repetition, in order: blend, churn (S_churn > 0), the step, re-noise.  samplers.edit_evaluations counts the evaluations."""
         ec = self.edm_config
         samplers.check_sampler(sampler, ec.S_churn)
         interval = samplers.guidance_interval_bounds(guidance_interval)
         samplers.check_guide(self.dit, guide, guide_captions)
+        samplers.check_edit(sampler, init_latents is not None, strength, inpaint_mask is not None, resample)
+        n = ec.num_steps if steps is None else steps
+        edit = None if init_latents is None else self._edit_operands(x, init_latents, strength, inpaint_mask, resample, n)
         can_fuse = not kwargs and x.is_cuda
         cond_cache = sampler_cache_enabled(cond_cache)
         if cond_cache and (fused is False or not can_fuse):
@@ -269,7 +286,7 @@ class LatentDiffusion(nn.Module):
             fused = can_fuse
         if fused:
             assert can_fuse, "the fused sampler needs CUDA tensors and no extra forward arguments"
-            return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, guide, guide_captions == "null")
+            return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, guide, guide_captions == "null", edit)
         if guide is not None:
             fwd = self._autoguided_forward(guide, torch.zeros_like(y) if guide_captions == "null" else y, cfg) if cfg > 1.0 else self.dit.forward
         else:
@@ -278,33 +295,64 @@ class LatentDiffusion(nn.Module):
         def denoise(xs, sigma):
             f = fwd if interval is None or interval[0] <= float(sigma) <= interval[1] else self.dit.forward
             return self.model_forward_wrapper(xs.to(torch.float32), sigma.to(torch.float32), y, f, mask_ratio=0, **kwargs)["sample"].to(torch.float64)
-        n = ec.num_steps if steps is None else steps
         idx = torch.arange(n, dtype=torch.float64, device=x.device)
         inv_rho = 1 / ec.rho
         t_steps = (ec.sigma_max ** inv_rho + idx / (n - 1) * (ec.sigma_min ** inv_rho - ec.sigma_max ** inv_rho)) ** ec.rho
         t_steps = torch.cat([t_steps, torch.zeros_like(t_steps[:1])])
+        x0, m, i0, resample = (None, None, 0, 1) if edit is None else edit
+        if m is not None:                           # [mask_B, H * W] fp32 -> broadcast over the channels of the fp64 state
+            m = m.view(m.shape[0], 1, x.shape[-2], x.shape[-1]).to(torch.float64)
         if sampler != "heun":
             levels = t_steps.tolist()
-            coef = samplers.solver_coefficients(sampler, levels, self._churned_levels(levels, n))
-        x_next = x.to(torch.float64) * t_steps[0]
-        for i, (t_cur, t_next) in enumerate(zip(t_steps[:-1], t_steps[1:])):
-            x_cur = x_next
-            gamma = min(ec.S_churn / n, np.sqrt(2) - 1) if ec.S_min <= t_cur <= ec.S_max else 0
-            t_hat = torch.as_tensor(t_cur + gamma * t_cur)
-            x_hat = x_cur + (t_hat ** 2 - t_cur ** 2).sqrt() * ec.S_noise * self.randn_like(x_cur)
-            den = denoise(x_hat, t_hat)
-            if sampler != "heun":                   # one evaluation per step: x_next = a x_hat + b (c1 D - c2 D_prev)
-                a, b, c1, c2 = coef[i]
-                x_next = a * x_hat + b * (c1 * den - c2 * hist if c2 != 0 else c1 * den)
-                hist = den
-                continue
-            d_cur = (x_hat - den) / t_hat
-            x_next = x_hat + (t_next - t_hat) * d_cur
-            if i < n - 1:
-                den = denoise(x_next, t_next)
-                d_prime = (x_next - den) / t_next
-                x_next = x_hat + (t_next - t_hat) * (0.5 * d_cur + 0.5 * d_prime)
+            coef = samplers.solver_coefficients(sampler, levels[i0:], self._churned_levels(levels, n)[i0:])
+        reps = samplers.edit_repetitions(t_steps.tolist(), i0, resample) if resample > 1 else [1] * (n - i0)
+        draw_churn = m is None or ec.S_churn > 0
+        x_next = x.to(torch.float64) * t_steps[0] if edit is None else x0 + t_steps[i0] * x.to(torch.float64)
+        for i in range(i0, n):
+            t_cur, t_next = t_steps[i], t_steps[i + 1]
+            for rep in range(reps[i - i0]):
+                x_cur = x_next
+                if m is not None:
+                    x_cur = m * x_cur + (1 - m) * (x0 + t_cur * self.randn_like(x_cur))
+                gamma = min(ec.S_churn / n, np.sqrt(2) - 1) if ec.S_min <= t_cur <= ec.S_max else 0
+                t_hat = torch.as_tensor(t_cur + gamma * t_cur)
+                x_hat = x_cur + (t_hat ** 2 - t_cur ** 2).sqrt() * ec.S_noise * self.randn_like(x_cur) if draw_churn else x_cur
+                den = denoise(x_hat, t_hat)
+                if sampler != "heun":               # one evaluation per step: x_next = a x_hat + b (c1 D - c2 D_prev)
+                    a, b, c1, c2 = coef[i - i0]
+                    x_next = a * x_hat + b * (c1 * den - c2 * hist if c2 != 0 else c1 * den)
+                    hist = den
+                else:
+                    d_cur = (x_hat - den) / t_hat
+                    x_next = x_hat + (t_next - t_hat) * d_cur
+                    if i < n - 1:
+                        den = denoise(x_next, t_next)
+                        d_prime = (x_next - den) / t_next
+                        x_next = x_hat + (t_next - t_hat) * (0.5 * d_cur + 0.5 * d_prime)
+                if rep < reps[i - i0] - 1:          # RePaint: back to level t_cur for the next repetition
+                    x_next = x_next + (t_cur ** 2 - t_next ** 2).sqrt() * self.randn_like(x_next)
+        if m is not None:
+            x_next = m * x_next + (1 - m) * x0
         return x_next.to(torch.float32)
+
+    def _edit_operands(self, x, init_latents, strength, inpaint_mask, resample, n):
+        """(init_latents as fp64, the mask as contiguous fp32 [mask_B, H * W] or None, i0, resample) on x's device, each converted once;
+        ValueError for latents of another shape, a mask that does not broadcast over [B, 1, H, W] or a float mask outside [0, 1]."""
+        if tuple(init_latents.shape) != tuple(x.shape):
+            raise ValueError(f"init_latents has shape {tuple(init_latents.shape)}, the noise {tuple(x.shape)}: they must agree")
+        x0 = init_latents.detach().to(device=x.device, dtype=torch.float64).contiguous()
+        m = None
+        if inpaint_mask is not None:
+            B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+            shape = tuple(inpaint_mask.shape)
+            ok = (shape == (H, W) or (len(shape) == 3 and shape[0] in (1, B) and shape[1:] == (H, W))
+                  or (len(shape) == 4 and shape[0] in (1, B) and shape[1] == 1 and shape[2:] == (H, W)))
+            if not ok:
+                raise ValueError(f"inpaint_mask has shape {shape}: expected [{B} or 1, 1, {H}, {W}], [{B} or 1, {H}, {W}] or [{H}, {W}]")
+            m = inpaint_mask.detach().to(device=x.device, dtype=torch.float32).reshape(-1, H * W).contiguous()
+            if inpaint_mask.dtype != torch.bool and not bool(((m >= 0) & (m <= 1)).all()):
+                raise ValueError("inpaint_mask must be bool or hold values in [0, 1] (1 = generate, 0 = keep init_latents)")
+        return x0, m, samplers.edit_start_index(n, strength), resample
 
     def _autoguided_forward(self, guide, y_guide, w: float):
         """The forward function of an autoguided evaluation for model_forward_wrapper: both networks on the same input at batch B, the
@@ -317,7 +365,7 @@ class LatentDiffusion(nn.Module):
 
     @torch.no_grad()
     def _edm_sampler_fused(self, x, y, steps: Optional[int], cfg: float, cond_cache: bool = False, sampler: str = "heun", interval=None,
-                           guide=None, guide_null: bool = False):
+                           guide=None, guide_null: bool = False, edit=None):
         """The same loops with everything around the network evaluations in fused HIP kernels: md_edm_sampler_input (c_in scaling +
         guidance batch doubling) and md_edm_heun_update (guidance combine + preconditioning + fp64 Euler / Heun update) or, for
         euler / dpmpp_2m, md_edm_solver_update (the same with the linear-multistep update of samplers.solver_coefficients).
@@ -329,7 +377,11 @@ class LatentDiffusion(nn.Module):
         guide: nothing is doubled.  A guided evaluation writes the network input once (dup = 0), runs self.dit and then the guide on it
         at batch B (the guide with its own captions / its own Conditioning, encoded by the guide) and hands the two outputs to
         md_edm_*_update_guide(_tok).  Both outputs are fresh allocations that network() returns together, so main's is alive and
-        untouched while the guide runs and until the update has been enqueued."""
+        untouched while the guide runs and until the update has been enqueued.
+        edit = (init_latents fp64, mask fp32 [mask_B, H * W] or None, i0, resample) from _edit_operands: md_edm_blend_known writes the
+        SDEdit start into the state (in place on the fp64 copy of x, which is its noise operand), blends the known latents at level t_i
+        into x_cur at the start of every repetition (one draw, one launch) and pastes them after the last step; a repetition that is
+        not the last ends with one draw and md_edm_churn in place on the state it produced (x_cur after the swap).  None: none of it."""
         ec, L, st = self.edm_config, hip.lib(), torch.cuda.current_stream().cuda_stream
         n = ec.num_steps if steps is None else steps
         idx = torch.arange(n, dtype=torch.float64)
@@ -338,10 +390,22 @@ class LatentDiffusion(nn.Module):
         t_steps = torch.cat([t_steps, torch.zeros(1, dtype=torch.float64)]).tolist()
         heun, churn = sampler == "heun", ec.S_churn > 0
         t_hats = self._churned_levels(t_steps, n) if churn else t_steps[:-1]
-        levels = [s for i in range(n) for s in ([t_hats[i]] + ([t_steps[i + 1]] if heun and i < n - 1 else []))]
+        x0, mask, i0, resample = (None, None, 0, 1) if edit is None else edit
+        levels = [s for i in range(i0, n) for s in ([t_hats[i]] + ([t_steps[i + 1]] if heun and i < n - 1 else []))]
         guided = any(samplers.is_guided(s, cfg, interval) for s in levels)      # no guided evaluation at all: the cfg = 1 run
         B, numel = x.shape[0], x.numel()
-        x_cur = (x.to(torch.float64) * t_steps[0]).contiguous()
+
+        def blend_known(noise, m, sigma):
+            """x_cur <- m * x_cur + (1 - m) * (x0 + sigma * noise); m None: the whole state, noise None: x0 itself."""
+            hip.check(L.md_edm_blend_known(x_cur.data_ptr(), x0.data_ptr(), None if noise is None else noise.data_ptr(),
+                                           None if m is None else m.data_ptr(), B, x.shape[1], x.shape[2] * x.shape[3],
+                                           1 if m is None else m.shape[0], float(sigma), st), "md_edm_blend_known")
+        if edit is None:
+            x_cur = (x.to(torch.float64) * t_steps[0]).contiguous()
+        else:
+            # always a copy: the kernel writes the start into it in place, and an fp64 contiguous x would otherwise be the caller's tensor
+            x_cur = x.to(torch.float64, copy=True, memory_format=torch.contiguous_format)
+            blend_known(x_cur, None, t_steps[i0])
         x_nxt, d_cur = torch.empty_like(x_cur), torch.empty_like(x_cur)
         auto = guide is not None and guided         # with a guide the second operand comes from it: the batch is never doubled
         y2 = torch.cat([y, torch.zeros_like(y)], 0) if guided and not auto else y
@@ -419,32 +483,48 @@ class LatentDiffusion(nn.Module):
             else:
                 hip.check(L.md_edm_solver_update(x_cur.data_ptr(), F.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(), numel, float(cfg), dup,
                                                  t_in, ec.sigma_data, *coef, st), "md_edm_solver_update")
-        coefs = None if heun else samplers.solver_coefficients(sampler, t_steps, t_hats)
-        for i, (t_cur, t_next) in enumerate(zip(t_steps[:-1], t_steps[1:])):
-            t_hat = t_hats[i]
-            if churn:                               # one draw per step, churned or not: the draws of the tensor-op loop
-                noise = self.randn_like(x_cur)
-                if t_hat != t_cur:                  # x_cur becomes x_hat (x_cur itself is not read again)
-                    noise = noise.to(torch.float64).contiguous()
+        coefs = None if heun else samplers.solver_coefficients(sampler, t_steps[i0:], t_hats[i0:])
+        reps = samplers.edit_repetitions(t_steps, i0, resample) if resample > 1 else [1] * (n - i0)
+        for i in range(i0, n):
+            t_cur, t_next, t_hat = t_steps[i], t_steps[i + 1], t_hats[i]
+            for rep in range(reps[i - i0]):
+                # .to(float64).contiguous() on a draw, here and below, does nothing for torch.randn_like on the fp64 state: it is there for
+                # a replaced self.randn_like (a recorded or fp32 generator), whose result the kernels must still read as contiguous fp64
+                if mask is not None:                # the known region at this step's noise level, one fresh draw
+                    blend_known(self.randn_like(x_cur).to(torch.float64).contiguous(), mask, t_cur)
+                if churn:                           # one draw per step, churned or not: the draws of the tensor-op loop
+                    noise = self.randn_like(x_cur)
+                    if t_hat != t_cur:              # x_cur becomes x_hat (x_cur itself is not read again)
+                        noise = noise.to(torch.float64).contiguous()
+                        hip.check(L.md_edm_churn(x_cur.data_ptr(), noise.data_ptr(), x_cur.data_ptr(), numel,
+                                                 float(np.sqrt(t_hat ** 2 - t_cur ** 2) * ec.S_noise), st), "md_edm_churn")
+                if heun:
+                    update(network(x_cur, t_hat), x_cur, t_hat, t_hat, t_next, 0)
+                    if i < n - 1:
+                        update(network(x_nxt, t_next), x_nxt, t_next, t_hat, t_next, 1)
+                else:
+                    solver_update(network(x_cur, t_hat), t_hat, coefs[i - i0])
+                x_cur, x_nxt = x_nxt, x_cur
+                if rep < reps[i - i0] - 1:          # RePaint: the state this repetition produced goes back to level t_cur
+                    noise = self.randn_like(x_cur).to(torch.float64).contiguous()
                     hip.check(L.md_edm_churn(x_cur.data_ptr(), noise.data_ptr(), x_cur.data_ptr(), numel,
-                                             float(np.sqrt(t_hat ** 2 - t_cur ** 2) * ec.S_noise), st), "md_edm_churn")
-            if heun:
-                update(network(x_cur, t_hat), x_cur, t_hat, t_hat, t_next, 0)
-                if i < n - 1:
-                    update(network(x_nxt, t_next), x_nxt, t_next, t_hat, t_next, 1)
-            else:
-                solver_update(network(x_cur, t_hat), t_hat, coefs[i])
-            x_cur, x_nxt = x_nxt, x_cur
+                                             float(np.sqrt(t_cur ** 2 - t_next ** 2)), st), "md_edm_churn")
+        if mask is not None:
+            blend_known(None, mask, 0.0)
         return x_cur.to(torch.float32)
 
     @torch.no_grad()
     def generate(self, prompt: Optional[list] = None, tokenized_prompts=None, attention_mask=None, guidance_scale: float = 5.0,
                  num_inference_steps: int = 30, seed: Optional[int] = None, return_only_latents: bool = False,
                  cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
-                 guide_captions: str = "same", **kwargs):
+                 guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1, **kwargs):
         """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache, sampler,
-        guidance_interval, guide and guide_captions: as in edm_sampler_loop (with a guide, guidance_scale is the autoguidance weight)."""
+        guidance_interval, guide and guide_captions: as in edm_sampler_loop (with a guide, guidance_scale is the autoguidance weight).
+        init_latents, strength, inpaint_mask and resample: image-to-image and inpainting as in edm_sampler_loop; the seeded draw below is
+        then the unit noise added to init_latents.  init_latents are latents already (VAE latents * latent_scale, the space of the
+        trainer's image_latents): encoding an image into them stays the caller's vae.encode, a frozen third-party model."""
         samplers.check_guide(self.dit, guide, guide_captions)
+        samplers.check_edit(sampler, init_latents is not None, strength, inpaint_mask is not None, resample)
         assert prompt or tokenized_prompts is not None, "Must provide either prompt or tokenized prompts"
         device = next(self.dit.parameters()).device
         gen = torch.Generator(device=device)
@@ -458,7 +538,8 @@ class LatentDiffusion(nn.Module):
                                        attention_mask=attention_mask.to(device) if attention_mask is not None else None)[0]
         latents = torch.randn((len(emb), self.dit.in_channels, self.latent_res, self.latent_res), device=device, generator=gen)
         latents = self.edm_sampler_loop(latents, emb, num_inference_steps, cfg=guidance_scale, cond_cache=cond_cache, sampler=sampler,
-                                        guidance_interval=guidance_interval, guide=guide, guide_captions=guide_captions)
+                                        guidance_interval=guidance_interval, guide=guide, guide_captions=guide_captions,
+                                        init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, resample=resample)
         if return_only_latents:
             return latents
         image = self.vae.decode((latents / self.latent_scale).to(DATA_TYPES[self.dtype])).sample

@@ -24,6 +24,57 @@ def check_sampler(sampler: str, S_churn: float = 0.0) -> str:
     return sampler
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Image-conditioned sampling: image-to-image (SDEdit) starts the schedule late from known latents, inpainting holds the
+# region where the mask is 0 at those latents, RePaint resampling repeats every step.  Both sampler loops take their step counts from
+# the three helpers below.
+# ---------------------------------------------------------------------------------------------------------------------
+RESAMPLE_SAMPLERS = ("heun", "euler")       # the jump back to the step's own noise level needs a solver without history
+
+
+def check_edit(sampler: str, has_init: bool, strength: float = 1.0, has_mask: bool = False, resample: int = 1) -> None:
+    """Refuse, before anything is launched, allocated or drawn, an image-conditioned request that is not defined."""
+    try:                                    # any real number: a Python or numpy scalar, a 0-dim tensor
+        in_range = not isinstance(strength, (bool, str)) and 0.0 < float(strength) <= 1.0
+    except (TypeError, ValueError, RuntimeError):     # not a number; a tensor of several elements
+        in_range = False
+    if not in_range:
+        raise ValueError(f"strength must be a number in (0, 1], got {strength!r}")
+    strength = float(strength)
+    if strength < 1.0 and not has_init:
+        raise ValueError(f"strength={strength!r} needs init_latents: without them the sampler starts from pure noise")
+    if has_mask and not has_init:
+        raise ValueError("inpaint_mask needs init_latents: the region where the mask is 0 is held at them")
+    if isinstance(resample, bool) or not isinstance(resample, int) or resample < 1:
+        raise ValueError(f"resample must be an integer >= 1, got {resample!r}")
+    if resample > 1 and not has_mask:
+        raise ValueError("resample > 1 harmonises the generated region with the kept one: it needs inpaint_mask")
+    if resample > 1 and sampler not in RESAMPLE_SAMPLERS:
+        raise ValueError(f"sampler {sampler!r} carries history across steps, which does not survive the jump back to the step's noise "
+                         f"level: resample > 1 is defined for {', '.join(RESAMPLE_SAMPLERS)} only")
+
+
+def edit_start_index(n: int, strength: float = 1.0) -> int:
+    """i0, the first executed step of an n-step schedule: the last k = max(1, min(n, ceil(strength * n))) steps run."""
+    strength = float(strength)
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f"strength must be in (0, 1], got {strength!r}")
+    return n - max(1, min(n, math.ceil(strength * n)))
+
+
+def edit_repetitions(t_steps: Sequence[float], i0: int = 0, resample: int = 1) -> List[int]:
+    """How often each executed step i0 ... n - 1 runs (t_steps ends in 0): `resample` times, the step onto sigma = 0 once."""
+    return [resample if t_steps[i + 1] > 0 else 1 for i in range(i0, len(t_steps) - 1)]
+
+
+def edit_evaluations(sampler: str, n: int, strength: float = 1.0, resample: int = 1) -> int:
+    """Network evaluations of a run: heun takes two per repetition (one for the step onto sigma = 0), the others one."""
+    check_sampler(sampler)
+    check_edit(sampler, True, strength, True, resample)
+    reps = edit_repetitions(edm_schedule(n), edit_start_index(n, strength), resample)
+    return sum(r * (2 if sampler == "heun" else 1) for r in reps[:-1]) + reps[-1]
+
+
 def edm_schedule(steps: int, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0) -> List[float]:
     """The EDM noise levels t_0 = sigma_max ... t_{steps-1} = sigma_min and a final 0 (model.py:238-243), fp64."""
     inv = 1.0 / rho
