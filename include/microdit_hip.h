@@ -568,6 +568,43 @@ int md_ema_power_update(const float* p, float* const* ema, const float* beta, in
 int md_ema_power_update_ranges(const float* p, float* const* ema, const float* beta, int32_t n_profiles, const int64_t* flat_off,
                                const int64_t* count, int32_t n_ranges, const int32_t* guard, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------- LoRA */
+/* (Added under ABI 6: new symbols only.)  Low-rank adapters on a frozen base (Hu et al. 2021, "LoRA: Low-Rank Adaptation of Large
+ * Language Models"; no reference counterpart: the reference fine-tunes every weight).  For a targeted matrix W [rows, cols] of the
+ * flat buffers with adapter A [rank, cols], B [rows, rank] (row-major, inside the adapter's own flat fp32 buffer) and scale = alpha / rank:
+ *   md_lora_merge   v = p_W + scale * (B A) in fp32 for every item: acc = fma(B[n,j], A[j,k], acc) for j ascending from 0, then
+ *                   v = fma(scale, acc, p).  out_is_f32 = 0 stores bf16(v) (round to nearest even) at the tensor's offset of a bf16
+ *                   buffer -- the shadow the engine reads --, out_is_f32 = 1 stores v itself (out == p allowed: the adapter fused into
+ *                   the masters).  Both forms run the same instructions up to the store, so the bf16 form holds exactly the rounding of
+ *                   what the fp32 form stores.  Nothing outside the items' [w_off, w_off + rows * cols) is written.
+ *   md_lora_grad    from the accumulated fp32 gradient G = g_W, with c = scale * grad_scale:
+ *                     d_adapter[B][n, j] += c * sum_k G[n, k] A[j, k]        d_adapter[A][j, k] += c * sum_n B[n, j] G[n, k]
+ *                   (d_adapter has the adapter's layout).  fp32, no atomics, one writer per address, every sum in an order that is a
+ *                   function of the table alone: two calls on the same data give identical bits.  A workgroup owns a strip of 64 rows
+ *                   over all columns: dB rows are complete inside it (k ascending); the strip's share of dA (n ascending) goes to the
+ *                   workspace slice [strip][rank][cols] of the item, and a finish launch issued by the same call adds the slices in
+ *                   ascending strip order.  G is read once.  ws needs no initialisation (written before it is read).
+ * ONE launch over all items (two for md_lora_grad), driven by a work table in the manner of md_tensor_stats_partial.  `items` is the
+ * DEVICE copy the kernels read; `items_host` is the caller's HOST copy of the same n_items entries: shapes, alignment and the
+ * workspace size are checked on it and the grids are sized from it (an error code has to come from the host, and a launch path does
+ * not synchronise to read a device table).  md_lora_grad_ws_floats checks the host table, writes every item's ws_off into it (upload
+ * the table afterwards) and returns the workspace size in floats.
+ * Supported: rank in {4, 8, 16, 32, 64}; rows >= 1 (no tile size is assumed to divide it); cols a multiple of 8; w_off a multiple of
+ * 8, a_off / b_off multiples of 4 (16-byte accesses); p, g, out, adapter, d_adapter, ws 16-byte aligned.  Anything else, a NULL
+ * pointer, a ws_off that is not what md_lora_grad_ws_floats wrote, or ws_floats below its result: MD_BAD_ARG, nothing launched. */
+typedef struct md_lora_item {
+    int64_t w_off;  /* first element of W inside p / g / out */
+    int64_t a_off;  /* first element of A [rank, cols] inside adapter / d_adapter */
+    int64_t b_off;  /* first element of B [rows, rank] inside adapter / d_adapter */
+    int64_t ws_off; /* first float of the item's dA slices inside ws: written by md_lora_grad_ws_floats, not read by md_lora_merge */
+    int32_t rows, cols;
+} md_lora_item;
+int md_lora_merge(const float* p, const float* adapter, const md_lora_item* items, const md_lora_item* items_host, int32_t n_items,
+                  int32_t rank, float scale, void* out, int32_t out_is_f32, hipStream_t stream);
+int md_lora_grad_ws_floats(md_lora_item* items_host, int32_t n_items, int32_t rank, int64_t* out);
+int md_lora_grad(const float* g, const float* adapter, const md_lora_item* items, const md_lora_item* items_host, int32_t n_items,
+                 int32_t rank, float scale, float grad_scale, float* d_adapter, float* ws, int64_t ws_floats, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

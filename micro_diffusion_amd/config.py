@@ -185,6 +185,67 @@ def loss_weighting_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     return {"enabled": True, "channels": ch, "lr": lr}
 
 
+def lora_options(cfg: Dict[str, Any], world: Any = None) -> Dict[str, Any]:
+    """The LoRA switches of the `misc` section, off unless the config sets them: misc.lora_rank (0 / absent: off; one of
+    4, 8, 16, 32, 64), misc.lora_alpha (default: the rank), misc.lora_targets (regular expressions on parameter names; default: the five
+    attention projections of every block), misc.lora_weight_decay (default 0) and misc.lora_load_path (an adapter file to start from).
+    Returns {"enabled", "rank", "alpha", "targets", "weight_decay", "load_path"}.  Raises ValueError on values the kernels cannot
+    honour, on the other keys given without a rank, and on what LoRA training does not cover: more than one rank (`world`, default the
+    WORLD_SIZE environment variable), algorithms.ema, misc.posthoc_ema_* and misc.optimizer_monitor_interval > 0."""
+    import os
+    from .lora import DEFAULT_TARGETS, RANKS
+    misc = cfg.get("misc") or {}
+    rank = misc.get("lora_rank", 0)
+    if rank is None:
+        rank = 0
+    if isinstance(rank, bool) or not isinstance(rank, int) or (rank != 0 and rank not in RANKS):
+        raise ValueError(f"misc.lora_rank must be 0 (off) or one of {RANKS}, got {rank!r}")
+    keys = ("lora_alpha", "lora_targets", "lora_weight_decay", "lora_load_path")
+    if rank == 0:
+        for k in keys:
+            if misc.get(k) is not None:
+                raise ValueError(f"misc.{k} needs misc.lora_rank")
+        return {"enabled": False, "rank": 0, "alpha": None, "targets": list(DEFAULT_TARGETS), "weight_decay": 0.0, "load_path": None}
+    alpha = misc.get("lora_alpha")
+    if alpha is not None:
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or alpha != alpha or alpha in (float("inf"), float("-inf")):
+            raise ValueError(f"misc.lora_alpha must be a finite number, got {alpha!r}")
+        alpha = float(alpha)
+    targets = misc.get("lora_targets")
+    if targets is None:
+        targets = list(DEFAULT_TARGETS)
+    elif isinstance(targets, str):
+        targets = [targets]
+    elif isinstance(targets, (list, tuple)) and targets and all(isinstance(t, str) for t in targets):
+        targets = list(targets)
+    else:
+        raise ValueError(f"misc.lora_targets must be a non-empty list of regular expressions, got {targets!r}")
+    import re
+    for t in targets:
+        try:
+            re.compile(t)
+        except re.error as e:
+            raise ValueError(f"misc.lora_targets: {t!r} is not a regular expression ({e})") from None
+    wd = misc.get("lora_weight_decay", 0.0)
+    wd = 0.0 if wd is None else wd
+    if isinstance(wd, bool) or not isinstance(wd, (int, float)) or not wd >= 0 or wd == float("inf"):
+        raise ValueError(f"misc.lora_weight_decay must be a non-negative number, got {wd!r}")
+    path = misc.get("lora_load_path")
+    if path is not None and not isinstance(path, str):
+        raise ValueError(f"misc.lora_load_path must be a path, got {path!r}")
+    world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else int(world)
+    if world > 1:
+        raise ValueError(f"misc.lora_rank: LoRA training is single-GPU for now (WORLD_SIZE = {world}); data parallelism is a follow-up")
+    if (cfg.get("algorithms") or {}).get("ema"):
+        raise ValueError("misc.lora_rank with algorithms.ema: the adapter is a few MB, an average of the frozen base is not kept")
+    for k in ("posthoc_ema_sigma_rels", "posthoc_ema_snapshot_interval"):
+        if misc.get(k):
+            raise ValueError(f"misc.lora_rank with misc.{k}: the post-hoc averages cover the base's masters, which LoRA leaves frozen")
+    if int(misc.get("optimizer_monitor_interval", 0) or 0) > 0:
+        raise ValueError("misc.lora_rank with misc.optimizer_monitor_interval > 0: the monitor's tables cover the base's optimiser pass")
+    return {"enabled": True, "rank": rank, "alpha": alpha, "targets": targets, "weight_decay": float(wd), "load_path": path}
+
+
 def locate(target: str):
     native = TARGETS.get(target, target)
     if native is None:

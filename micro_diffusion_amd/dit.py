@@ -107,6 +107,7 @@ class DiT(nn.Module):
         self._shadow_version = -1
         self._shadow_epoch = 0       # times the bf16 shadow was rewritten (never reset): what a cached Conditioning is valid for
         self._grad_anchor = None
+        self._lora = None            # an attached lora.LoRA: every writer of the shadow re-applies it (refresh_shadow)
         self._build_and_init()
 
     # ------------------------------------------------------------------------------------------ construction
@@ -244,6 +245,8 @@ class DiT(nn.Module):
         if force or ver != self._shadow_version:
             hip.check(hip.lib().md_cast_f32_bf16(f["p"].data_ptr(), f["s"].data_ptr(), f["total"], None,
                                                  torch.cuda.current_stream().cuda_stream), "md_cast_f32_bf16")
+            if self._lora is not None:
+                self._lora.apply_to_shadow()       # md_lora_merge: the targeted matrices := bf16(p + scale B A)
             self._shadow_written(ver)
 
     def mark_shadow_fresh(self) -> None:

@@ -173,6 +173,12 @@ class StatsItem(Structure):
     _fields_ = [("src_off", c_int64), ("count", c_int32), ("tensor", c_int32)]
 
 
+class LoraItem(Structure):
+    """md_lora_item: one targeted matrix W [rows, cols] of the flat buffers and its A [rank, cols] / B [rows, rank] inside the adapter's
+    flat buffer (offsets in elements); ws_off is written by md_lora_grad_ws_floats."""
+    _fields_ = [("w_off", c_int64), ("a_off", c_int64), ("b_off", c_int64), ("ws_off", c_int64), ("rows", c_int32), ("cols", c_int32)]
+
+
 _sig("md_gemm_bf16", POINTER(GemmArgs), P)
 _sig("md_splitk_reduce_flat", P, P, I64, I64, I32, I32, P)
 _sig("md_splitk_reduce", P, P, I64, I64, I64, I64, I32, I32, I32, P)
@@ -259,6 +265,11 @@ _sig("md_moe_route_stats", P, P, I64, P, I64, I64, I32, I32, P, I64, P, P, P)
 # post-hoc EMA: up to EMA_MAX_PROFILES power-function averages of the masters in one pass (host arrays of pointers / betas)
 _sig("md_ema_power_update", P, P, P, I32, I64, P, P)
 _sig("md_ema_power_update_ranges", P, P, P, I32, P, P, I32, P, P)
+# LoRA: merge the adapters into the bf16 shadow (or the fp32 masters), project the accumulated gradient onto them (lora.py)
+_sig("md_lora_merge", P, P, P, P, I32, I32, F32, P, I32, P)
+_sig("md_lora_grad_ws_floats", P, I32, I32, POINTER(c_int64))
+_sig("md_lora_grad", P, P, P, P, I32, I32, F32, F32, P, P, I64, P)
+LORA_RANKS = (4, 8, 16, 32, 64)
 EMA_MAX_PROFILES = 4     # MD_EMA_MAX_PROFILES
 ADAMW_MAX_RANGES = 64    # MD_ADAMW_MAX_RANGES
 

@@ -202,6 +202,7 @@ class FusedAdamW:
         A skipped step is a consumed batch with a zero update: the host-side step_count (bias corrections), the LR-schedule
         position (Trainer.batches_seen) and ema_live advance as on any other step."""
         self.dit = dit
+        self._refuse_adapter()
         f = dit.flat_buffers()
         self.lr, self.betas, self.eps, self.weight_decay = lr, tuple(betas), eps, weight_decay
         self.m = torch.zeros_like(f["p"])
@@ -221,6 +222,12 @@ class FusedAdamW:
             raise ValueError(f"at most {hip.EMA_MAX_PROFILES} post-hoc EMA profiles (MD_EMA_MAX_PROFILES), got {len(self.posthoc_sigma_rels)}")
         self.posthoc_gammas = tuple(posthoc_ema.sigma_rel_to_gamma(s) for s in self.posthoc_sigma_rels)
         self.posthoc = [torch.zeros_like(f["p"]) for _ in self.posthoc_sigma_rels]        # empty list: the feature is off
+
+    def _refuse_adapter(self) -> None:
+        """This pass emits the bf16 shadow itself and would overwrite a LoRA merge (and train the base the adapter assumes frozen)."""
+        if getattr(self.dit, "_lora", None) is not None:
+            raise RuntimeError("FusedAdamW on a DiT with a LoRA adapter attached: step the adapter with lora.LoRAAdamW, or fuse() / "
+                               "detach() it first")
 
     def skipped_steps(self) -> int:
         """Steps the device-side guard turned into a no-op so far (synchronises: the only host read of the guard)."""
@@ -274,6 +281,7 @@ class FusedAdamW:
              norm_partials: int = 0) -> None:
         """`g_bf16`: take the gradients from this bf16 flat buffer (data-parallel exchange buffer) instead of the fp32
         accumulators.  `norm_partials` > 0: that many per-bucket partial sums of squares are already in self.partials."""
+        self._refuse_adapter()
         f = self.dit.flat_buffers()
         L, st = hip.lib(), torch.cuda.current_stream().cuda_stream
         ema_mode = self._begin_step(grad_scale)
@@ -301,6 +309,7 @@ class FusedAdamW:
         all-gather of the bf16 weights.  The fp32 accumulators were cleared by the staging cast.
         `chunk_of` (measurement aid, single rank): pretend to be one of `chunk_of` ranks — update only the first 1 / chunk_of of
         every bucket — to time the per-rank optimiser pass of an N-GPU run on one GPU; the model is NOT valid afterwards."""
+        self._refuse_adapter()
         f = self.dit.flat_buffers()
         ema_mode = self._begin_step(grad_scale)
         lr = self.lr if lr is None else lr
@@ -907,6 +916,9 @@ class Trainer:
         if getattr(model.dit.engine, "deterministic", False):
             self.sync.deterministic = True
         self.world = self.sync.world
+        if getattr(optimizer, "adapter", None) is not None and self.world > 1:
+            raise NotImplementedError("LoRA training is single-GPU for now: data parallelism (project locally, then all-reduce the "
+                                      "adapter gradient) is not implemented")
         self.sharded = self.sync.enabled and self.sync.mode == "sharded"
         self.stale_foreign_chunks = False    # sharded: fp32 masters / moments of the other ranks' chunks are out of date
         self.shard_chunk_of = None           # measurement aid, see FusedAdamW.step_sharded

@@ -19,6 +19,7 @@ sys.path.insert(0, ROOT)
 
 from micro_diffusion_amd import config as mdcfg  # noqa: E402
 from micro_diffusion_amd import loss_weighting as mdlw  # noqa: E402
+from micro_diffusion_amd.lora import LoRA, LoRAAdamW  # noqa: E402
 from micro_diffusion_amd.model import text_encoder_embedding_format  # noqa: E402
 from micro_diffusion_amd.trainer import FusedAdamW, LRSchedule, Trainer, parse_batches  # noqa: E402
 
@@ -26,6 +27,9 @@ from micro_diffusion_amd.trainer import FusedAdamW, LRSchedule, Trainer, parse_b
 def train(cfg: dict):
     posthoc = mdcfg.posthoc_ema_options(cfg)     #  checked before anything is allocated: raises on values it cannot honour
     lwopt = mdcfg.loss_weighting_options(cfg)    #  likewise: channels / lr checked here
+    lora = mdcfg.lora_options(cfg)               #  likewise: rank / targets checked, unsupported combinations refused
+    if lora["enabled"] and not cfg["trainer"].get("load_path"):
+        raise ValueError("misc.lora_rank needs trainer.load_path: the adapter is trained on a frozen, trained base")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -61,6 +65,8 @@ def train(cfg: dict):
         model.dit.load_state_dict(sd, strict=bool(cfg["trainer"].get("load_strict_model_weights", True)) and not ignore)
         # u(sigma) travels with the weights; its moments only when the optimiser state is carried too
         mdlw.restore(lw, ckpt.get("state", {}), weights_only=carried_opt is None)
+    if lora["enabled"]:
+        carried_opt = None                       # the base's AdamW moments have no use: the base is frozen
     ocfg = dict(cfg["optimizer"])
     ocfg.pop("_target_")
     # EMA of the weights (configs/res_512_*.yaml:4-9, diffusion.algorithms.ema.EMA): folded into the AdamW kernel.  The
@@ -84,8 +90,20 @@ def train(cfg: dict):
     # Post-hoc EMA, off by default: misc.posthoc_ema_sigma_rels, misc.posthoc_ema_snapshot_interval
     posthoc_kw = dict(posthoc_sigma_rels=posthoc["sigma_rels"]) if posthoc["sigma_rels"] else {}
     snap_every = posthoc["snapshot_interval"]
-    opt = FusedAdamW(model.dit, lr=ocfg["lr"], betas=tuple(ocfg.get("betas", (0.9, 0.999))), eps=ocfg.get("eps", 1e-8),
-                     weight_decay=ocfg.get("weight_decay", 0.0), **ema_kw, **guard_kw, **posthoc_kw)
+    adapter = None
+    if lora["enabled"]:
+        # LoRA: the optimiser block's lr / betas / eps drive AdamW on the adapter alone; A is drawn on the CPU from
+        # the run's seed, B = 0 (or both come from misc.lora_load_path)
+        adapter = LoRA(model.dit, rank=lora["rank"], alpha=lora["alpha"], targets=lora["targets"], seed=cfg["seed"])
+        if lora["load_path"]:
+            asd = torch.load(lora["load_path"], map_location="cuda")
+            adapter.load_state_dict(asd.get("lora", asd))
+        adapter.attach()
+        opt = LoRAAdamW(adapter, lr=ocfg["lr"], betas=tuple(ocfg.get("betas", (0.9, 0.999))), eps=ocfg.get("eps", 1e-8),
+                        weight_decay=lora["weight_decay"], **guard_kw)
+    else:
+        opt = FusedAdamW(model.dit, lr=ocfg["lr"], betas=tuple(ocfg.get("betas", (0.9, 0.999))), eps=ocfg.get("eps", 1e-8),
+                         weight_decay=ocfg.get("weight_decay", 0.0), **ema_kw, **guard_kw, **posthoc_kw)
     if carried_opt is not None:
         opt.load_state_dict(carried_opt)          # keyed by parameter name; raises on a mismatch with this model
     max_ba = parse_batches(cfg["trainer"]["max_duration"])
@@ -118,7 +136,12 @@ def train(cfg: dict):
         # Composer's autoresume: continue the run whose checkpoints live in save_folder (weights, AdamW moments, batch
         # counter = LR-schedule position, and the data position: the loader's order is a function of (seed, epoch)).
         ck = torch.load(latest, map_location="cuda")
-        model.dit.load_state_dict({k[len("dit."):]: v for k, v in ck["state"]["model"].items()})
+        if adapter is not None:
+            if "lora" not in ck:
+                raise RuntimeError(f"{latest} is a full checkpoint, this run trains a LoRA adapter (misc.lora_rank)")
+            adapter.load_state_dict(ck["lora"])                    # the base stays what trainer.load_path holds
+        else:
+            model.dit.load_state_dict({k[len("dit."):]: v for k, v in ck["state"]["model"].items()})
         opt.load_state_dict(ck["optimizer"])
         mdlw.restore(lw, ck["state"])
         start = int(ck["batch"])
@@ -184,9 +207,15 @@ def train(cfg: dict):
         if rank == 0 and folder and save_every and (step + 1) % save_every == 0:
             os.makedirs(folder, exist_ok=True)
             tmp = os.path.join(folder, "latest.pt.tmp")
-            torch.save({"state": checkpoint_state(model, opt),
-                        "optimizer": opt.state_dict(), "batch": step + 1, "rng_cuda": torch.cuda.get_rng_state(),
-                        "loader": loader.state_dict() if hasattr(loader, "state_dict") else None}, tmp)
+            extra = {"batch": step + 1, "rng_cuda": torch.cuda.get_rng_state(),
+                     "loader": loader.state_dict() if hasattr(loader, "state_dict") else None}
+            if adapter is not None:
+                # adapter checkpoints instead of full ones: a few MB each, kept per save (lora-<batch>.pt) next to latest.pt
+                torch.save({**lora_checkpoint(model, adapter, opt, cfg["trainer"]["load_path"]), **extra}, tmp)
+                import shutil
+                shutil.copyfile(tmp, os.path.join(folder, f"lora-{step + 1}.pt"))
+            else:
+                torch.save({"state": checkpoint_state(model, opt), "optimizer": opt.state_dict(), **extra}, tmp)
             os.replace(tmp, os.path.join(folder, "latest.pt"))      # never leave a truncated latest.pt behind
     return trainer
 
@@ -213,6 +242,15 @@ def checkpoint_state(model, opt) -> dict:
     if getattr(model, "loss_weighting", None) is not None:
         state["loss_weighting"] = model.loss_weighting.state_dict()
     return state
+
+
+def lora_checkpoint(model, adapter, opt, base_path) -> dict:
+    """What a LoRA run saves in place of a full checkpoint: the adapter (LoRA.state_dict(): loadable with LoRA.from_state_dict), its
+    AdamW moments, the path of the frozen base, and `state` with the learned loss weighting when that is on."""
+    state = {}
+    if getattr(model, "loss_weighting", None) is not None:
+        state["loss_weighting"] = model.loss_weighting.state_dict()
+    return {"lora": adapter.state_dict(), "optimizer": opt.state_dict(), "base_path": base_path, "state": state}
 
 
 def save_posthoc_snapshots(opt, folder: str, step: int, profiles=None) -> list:
