@@ -184,7 +184,9 @@ def test_attention(hip, B, H, Sq, Skv, hd, packed, bwd_split, layout):
     a forced form that does not cover the problem must refuse it (-1) and launch nothing.
     layout "head_major_qk": q, k, dq, dk as [B, H, S, hd] (md_attn_args.hsq / hsk / hsdq / hsdk -- what md_qkln_fwd_hm writes and
     md_qkln_bwd_hm reads), v / o / dO / dv in the packed rows.  All against torch fp32 autograd of the same bf16 inputs
-    (utils.py:116-132,177-193)."""
+    (utils.py:116-132,177-193).
+    What this test does not reach -- B >= 8 (the XCD batch remap), the dispatch boundaries of Sq / Skv, inputs with a hard softmax, lse and
+    delta as outputs, guard rows, per-row limits -- is in tests/test_attention_edges_gpu.py."""
     torch.manual_seed(B * H + Sq + Skv + hd)
     L, st = hip.lib(), hip.stream_ptr()
     hid = H * hd
