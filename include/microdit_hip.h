@@ -445,6 +445,55 @@ int md_edm_churn(const double* x, const double* noise, double* x_hat, int64_t n,
 int md_edm_blend_known(double* x, const double* x0, const double* noise, const float* mask, int64_t B, int32_t C, int64_t HW,
                        int32_t mask_B, double sigma, hipStream_t stream);
 
+/* Guidance modes (opt-in; the default stays the cfg combine of the entry points above): CFG rescale (Lin et al. 2024, "Common Diffusion
+ * Noise Schedules and Sample Steps are Flawed", 3.4) and adaptive projected guidance, APG (Sadat et al. 2024, "Eliminating Oversaturation
+ * and Artifacts of High Guidance Scales").  Both act on the denoised prediction D = c_skip * (float)x_in + c_out * F (fp32, as
+ * md_edm_heun_update forms it) and need reductions per sample over its n = per_sample = C*H*W elements, so a guided evaluation is
+ * md_guidance_prepare(_tok) followed by one of the four _coef update entry points.
+ *   D_c, D_u: D of the conditional output and of the second operand (the unconditional half of a doubled batch, or a guide network's
+ *             output; two pointers, as in the _guide entry points).
+ *   M = (D_c - D_u) + beta * M_prev   fp32, [B, n] in the layout of the state, in place; beta = apg_momentum (APG only, |beta| < 1;
+ *             0 in rescale mode).  M_prev is not read when `first` is set, in rescale mode or when beta == 0.  D_c - D_u is evaluated
+ *             as c_out * (F_c - F_u) in fp32: the c_skip * x term is common to both and cancels, so its rounding stays out of M.
+ *   moments[b] = (S_c, S_m, Q_cc, Q_mm, Q_cm) = (sum D_c, sum M, sum D_c^2, sum M^2, sum D_c * M) over sample b, accumulated in fp64.
+ *   coef[b] = (alpha, gamma), formed in fp64 with w1 = w - 1 and stored as fp32:
+ *     MD_GUIDANCE_APG      s = has_norm_threshold && Q_mm > 0 ? min(1, r / sqrt(Q_mm)) : 1;   p = Q_cc > 0 ? s * Q_cm / Q_cc : 0;
+ *                          alpha = 1 - w1 * (1 - eta) * p;   gamma = w1 * s
+ *                          (= D_c + w1 * (orth + eta * par) for s * M split into its projection on D_c and the rest)
+ *     MD_GUIDANCE_RESCALE  var_c = max(Q_cc / n - (S_c / n)^2, 0);   S_g = S_c + w1 * S_m;
+ *                          var_g = (Q_cc + 2 w1 Q_cm + w1^2 Q_mm) / n - (S_g / n)^2;
+ *                          k = var_g > 0 ? phi * sqrt(var_c / var_g) + 1 - phi : 1;   alpha = k;   gamma = k * w1
+ *   The guided prediction is D = alpha_b * D_c + gamma_b * M: the _coef entry points are md_edm_heun_update(_tok) and
+ *   md_edm_solver_update(_tok) with D = fmaf(alpha_b, D_c, gamma_b * M) (fp32, widened to fp64) in place of the cfg combine, followed
+ *   by the same fp64 update.  F_c / tok_bf16 there is the conditional output alone ([B, n] floats / [B*T, C*p*p] bf16 rows).
+ *   - One workgroup per sample, fixed-order reduction, no atomics: two calls give the same bits, and the token form gives the bits of
+ *     md_unpatchify followed by the image form (the order of the sums depends on the image-layout element index alone).
+ *   - Nothing is copied to the host and nothing synchronises.  M must not alias another operand; in the _coef entry points x_next may
+ *     alias x_in / x_hat as above, and F_c, M and coef are only read.
+ *   - MD_BAD_ARG, nothing launched: a null pointer, a non-positive size, H % p or W % p non-zero, t_in <= 0, a mode other than the two
+ *     below, phi outside [0, 1], has_norm_threshold with r <= 0, |beta| >= 1, or a parameter that is not finite. */
+#define MD_GUIDANCE_RESCALE 1
+#define MD_GUIDANCE_APG 2
+int md_guidance_prepare(const double* x_in, const float* F_c, const float* F_u, float* M, float* coef, double* moments, int64_t B,
+                        int64_t per_sample, double t_in, float sigma_data, int32_t mode, double w, double rescale_phi, double apg_eta,
+                        int32_t has_norm_threshold, double apg_norm_threshold, double apg_momentum, int32_t first, hipStream_t stream);
+int md_guidance_prepare_tok(const double* x_in, const void* tok_bf16, const void* tok_u_bf16, float* M, float* coef, double* moments,
+                            int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, double t_in, float sigma_data, int32_t mode, double w,
+                            double rescale_phi, double apg_eta, int32_t has_norm_threshold, double apg_norm_threshold, double apg_momentum,
+                            int32_t first, hipStream_t stream);
+int md_edm_heun_update_coef(const double* x_hat, const double* x_in, const float* F_c, const float* M, const float* coef, double* d_cur,
+                            double* x_next, int64_t B, int64_t per_sample, double t_in, double t_hat, double t_next, float sigma_data,
+                            int32_t second, hipStream_t stream);
+int md_edm_solver_update_coef(const double* x_in, const float* F_c, const float* M, const float* coef, double* hist, double* x_next,
+                              int64_t B, int64_t per_sample, double t_in, float sigma_data, double a, double b, double c1, double c2,
+                              hipStream_t stream);
+int md_edm_heun_update_coef_tok(const double* x_hat, const double* x_in, const void* tok_bf16, const float* M, const float* coef,
+                                double* d_cur, double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, double t_in,
+                                double t_hat, double t_next, float sigma_data, int32_t second, hipStream_t stream);
+int md_edm_solver_update_coef_tok(const double* x_in, const void* tok_bf16, const float* M, const float* coef, double* hist, double* x_next,
+                                  int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, double t_in, float sigma_data, double a, double b,
+                                  double c1, double c2, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------- optimiser */
 /* Sum of squares of a gradient buffer (fp32, or bf16 when g_is_bf16), deterministic: workgroup b of a fixed grid writes
  * partials[b] (MD_SUMSQ_PARTIALS floats per call); md_sumsq_finish adds `count` partials (several calls' worth, e.g. one per

@@ -9,6 +9,7 @@
 //                       mean (model.py:177,199-210) and its gradient w.r.t. the kept-token network output.
 #include "md_common.h"
 #include "../../include/microdit_hip.h"
+#include <cmath>
 
 namespace {
 
@@ -175,26 +176,42 @@ __device__ __forceinline__ void heun_coef(double t_in, float sigma_data, float& 
 }
 __device__ __forceinline__ float cfg_combine(float fc, float fu, float cfg) { return fmaf(cfg, fc - fu, fu); }
 // D = c_skip * float(x_in) + c_out * F in fp32 (model.py:177), widened to the fp64 of the state.
-__device__ __forceinline__ double sampler_denoised(double xi, float f, float c_skip, float c_out) {
-    return (double)fmaf(c_skip, (float)xi, c_out * f);
+__device__ __forceinline__ float sampler_denoised_f32(double xi, float f, float c_skip, float c_out) {
+    return fmaf(c_skip, (float)xi, c_out * f);
 }
-// Returns x_next of one element; d receives the slope of this evaluation (the first half-step stores it as d_cur), d_prev is the
-// d_cur the second half-step reads.  Values in, values out: the callers load before they store, so x_next may alias x_in or x_hat.
-__device__ __forceinline__ double heun_element(double xi, double xh, float f, float c_skip, float c_out, double t_in, double t_hat,
-                                               double t_next, int second, double d_prev, double& d) {
-    const double D = sampler_denoised(xi, f, c_skip, c_out);
+__device__ __forceinline__ double sampler_denoised(double xi, float f, float c_skip, float c_out) {
+    return (double)sampler_denoised_f32(xi, f, c_skip, c_out);
+}
+// The combine of the guidance modes, in the space of the denoised value: D = alpha_b * D_c + gamma_b * M with D_c the
+// conditional prediction, M the running difference md_guidance_prepare left in the layout of the state and (alpha_b, gamma_b) the
+// per-sample coefficients it formed.  fp32 like the preconditioning, widened to the fp64 of the state.
+__device__ __forceinline__ double sampler_guided(double xi, float fc, float m, float c_skip, float c_out, float alpha, float gamma) {
+    return (double)fmaf(alpha, sampler_denoised_f32(xi, fc, c_skip, c_out), gamma * m);
+}
+// Returns x_next of one element from its denoised value D; d receives the slope of this evaluation (the first half-step stores it as
+// d_cur), d_prev is the d_cur the second half-step reads.  Values in, values out: the callers load before they store, so x_next may
+// alias x_in or x_hat.
+__device__ __forceinline__ double heun_from_denoised(double xi, double xh, double D, double t_in, double t_hat, double t_next, int second,
+                                                     double d_prev, double& d) {
     d = (xi - D) / t_in;
     if (!second) return fma(t_next - t_hat, d, xh);
     return fma(t_next - t_hat, fma(0.5, d, 0.5 * d_prev), xh);
+}
+__device__ __forceinline__ double heun_element(double xi, double xh, float f, float c_skip, float c_out, double t_in, double t_hat,
+                                               double t_next, int second, double d_prev, double& d) {
+    return heun_from_denoised(xi, xh, sampler_denoised(xi, f, c_skip, c_out), t_in, t_hat, t_next, second, d_prev, d);
 }
 
 // One step of a linear multistep solver on the denoised value (Euler, DPM-Solver++(2M)): x_next = a * x_in + b * (c1 * den - c2 * hist);
 // den goes back to the caller, which stores it as the next step's hist.  hist is 0.0 when c2 == 0 (the callers do not load it then),
 // so c1 * den - c2 * hist is c1 * den exactly and a stale or non-finite history buffer never reaches x_next.
+__device__ __forceinline__ double solver_from_denoised(double xi, double den, double a, double b, double c1, double c2, double hist) {
+    return fma(a, xi, b * fma(c1, den, -(c2 * hist)));
+}
 __device__ __forceinline__ double solver_element(double xi, float f, float c_skip, float c_out, double a, double b, double c1, double c2,
                                                  double hist, double& den) {
     den = sampler_denoised(xi, f, c_skip, c_out);
-    return fma(a, xi, b * fma(c1, den, -(c2 * hist)));
+    return solver_from_denoised(xi, den, a, b, c1, c2, hist);
 }
 
 __global__ __launch_bounds__(256) void sampler_input_kernel(const double* x, float* out, int64_t n, float sigma, float sigma_data, int dup) {
@@ -439,6 +456,219 @@ inline int launch_solver_update_tok(const double* x_in, const bf16* tok, const b
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Guidance modes: CFG rescale and adaptive projected guidance need per-sample reductions over the denoised prediction,
+// so a guided evaluation is two launches: guidance_prepare_kernel (M, the five moments, alpha_b and gamma_b) and one of the _coef update
+// kernels, which are the update kernels above with D = alpha_b * D_c + gamma_b * M in place of the cfg combine.
+// ---------------------------------------------------------------------------------------------------------------------
+struct guidance_args {
+    int mode, first, has_r;             // MD_GUIDANCE_*; first: M holds nothing yet (not read); has_r: the norm threshold r is set
+    double w, phi, eta, r;
+    float beta;
+};
+
+// One workgroup per sample.  Thread t takes the image-layout elements t, t + 256, ... of its sample in that order, five fp64 partial
+// sums each, then a fixed tree over the 256 partials in LDS; thread 0 forms the coefficients.  The order of every addition depends
+// on the image-layout element index alone: the token form (TOK) differs only in where it finds F of that element, so the two forms
+// give the same bits, and so do two calls.  The fp64 products of two fp32 values are exact.  M_prev is read and M written by the
+// same work item.  D_c - D_u is formed as c_out * (F_c - F_u): c_skip * x is the same in both and cancels, and the difference of the two
+// fp32 D would carry the rounding of that term, which is of the size of D, not of M, and comes back (w - 1) times in the result.  n per sample is 4,096 ... 16,384 here (16 ... 64 rounds): a grid-wide reduction would need a second launch or
+// atomics for less than a microsecond of arithmetic.
+template <bool TOK>
+__global__ __launch_bounds__(256) void guidance_prepare_kernel(const double* x_in, const void* Fc, const void* Fu, float* M, float* coef,
+                                                               double* moments, int64_t per, int C, int H, int W, int p, double t_in,
+                                                               float sigma_data, guidance_args g) {
+    __shared__ double red[5][256];
+    float c_skip, c_out;
+    heun_coef(t_in, sigma_data, c_skip, c_out);
+    const int64_t b = blockIdx.x;
+    const bool read_m = g.mode == MD_GUIDANCE_APG && !g.first && g.beta != 0.f;
+    double sc = 0.0, sm = 0.0, qcc = 0.0, qmm = 0.0, qcm = 0.0;
+    for (int64_t i = threadIdx.x; i < per; i += 256) {
+        const int64_t pix = b * per + i;
+        float fc, fu;
+        if (TOK) {
+            const int gw = W / p, w = (int)(i % W), hrow = (int)((i / W) % H), c = (int)(i / ((int64_t)W * H));
+            const int64_t row = (b * (H / p) + hrow / p) * gw + w / p;
+            const int64_t off = row * ((int64_t)C * p * p) + ((hrow % p) * p + w % p) * C + c;
+            fc = bf2f(((const bf16*)Fc)[off]);
+            fu = bf2f(((const bf16*)Fu)[off]);
+        } else {
+            fc = ((const float*)Fc)[pix];
+            fu = ((const float*)Fu)[pix];
+        }
+        const double xi = x_in[pix];
+        const float dc = sampler_denoised_f32(xi, fc, c_skip, c_out);
+        float m = c_out * (fc - fu);            // D_c - D_u without its cancelling c_skip * x (see above)
+        if (read_m) m = fmaf(g.beta, M[pix], m);
+        M[pix] = m;
+        const double dcd = (double)dc, md = (double)m;
+        sc += dcd;
+        sm += md;
+        qcc = fma(dcd, dcd, qcc);
+        qmm = fma(md, md, qmm);
+        qcm = fma(dcd, md, qcm);
+    }
+    const int t = threadIdx.x;
+    red[0][t] = sc, red[1][t] = sm, red[2][t] = qcc, red[3][t] = qmm, red[4][t] = qcm;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) red[k][t] += red[k][t + s];
+        }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    const double S_c = red[0][0], S_m = red[1][0], Q_cc = red[2][0], Q_mm = red[3][0], Q_cm = red[4][0];
+    double* mo = moments + b * 5;
+    mo[0] = S_c, mo[1] = S_m, mo[2] = Q_cc, mo[3] = Q_mm, mo[4] = Q_cm;
+    const double w1 = g.w - 1.0;
+    double alpha, gamma;
+    if (g.mode == MD_GUIDANCE_APG) {
+        const double s = g.has_r && Q_mm > 0.0 ? fmin(1.0, g.r / sqrt(Q_mm)) : 1.0;
+        const double pr = Q_cc > 0.0 ? s * Q_cm / Q_cc : 0.0;
+        alpha = 1.0 - w1 * (1.0 - g.eta) * pr;
+        gamma = w1 * s;
+    } else {
+        const double n = (double)per;
+        const double var_c = fmax(Q_cc / n - (S_c / n) * (S_c / n), 0.0);     // a constant D_c can round below zero
+        const double S_g = S_c + w1 * S_m;
+        const double var_g = (Q_cc + 2.0 * w1 * Q_cm + w1 * w1 * Q_mm) / n - (S_g / n) * (S_g / n);
+        const double k = var_g > 0.0 ? g.phi * sqrt(var_c / var_g) + 1.0 - g.phi : 1.0;
+        alpha = k;
+        gamma = k * w1;
+    }
+    coef[b * 2] = (float)alpha;
+    coef[b * 2 + 1] = (float)gamma;
+}
+
+__global__ __launch_bounds__(256) void heun_coef_update_kernel(const double* x_hat, const double* x_in, const float* Fc, const float* M,
+                                                               const float* coef, double* d_cur, double* x_next, int64_t n, int64_t per,
+                                                               double t_in, double t_hat, double t_next, float sigma_data, int second) {
+    float c_skip, c_out;
+    heun_coef(t_in, sigma_data, c_skip, c_out);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / per;
+        const double xi = x_in[i];
+        const double D = sampler_guided(xi, Fc[i], M[i], c_skip, c_out, coef[b * 2], coef[b * 2 + 1]);
+        double d;
+        x_next[i] = heun_from_denoised(xi, x_hat[i], D, t_in, t_hat, t_next, second, second ? d_cur[i] : 0.0, d);
+        if (!second) d_cur[i] = d;
+    }
+}
+
+__global__ __launch_bounds__(256) void solver_coef_update_kernel(const double* x_in, const float* Fc, const float* M, const float* coef,
+                                                                 double* hist, double* x_next, int64_t n, int64_t per, double t_in,
+                                                                 float sigma_data, double a, double b, double c1, double c2) {
+    float c_skip, c_out;
+    heun_coef(t_in, sigma_data, c_skip, c_out);
+    const bool use_hist = c2 != 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t s = i / per;
+        const double xi = x_in[i];
+        const double den = sampler_guided(xi, Fc[i], M[i], c_skip, c_out, coef[s * 2], coef[s * 2 + 1]);
+        x_next[i] = solver_from_denoised(xi, den, a, b, c1, c2, use_hist ? hist[i] : 0.0);
+        hist[i] = den;
+    }
+}
+
+// The token-space forms: F_c as in heun_update_tok_kernel, M and the coefficients of the item's sample from the image-layout buffers.
+template <bool VEC>
+__global__ __launch_bounds__(256) void heun_coef_update_tok_kernel(const double* x_hat, const double* x_in, const bf16* tok, const float* M,
+                                                                   const float* coef, double* d_cur, double* x_next, int64_t B, int C, int H,
+                                                                   int W, int p, double t_in, double t_hat, double t_next, float sigma_data,
+                                                                   int second) {
+    float c_skip, c_out;
+    heun_coef(t_in, sigma_data, c_skip, c_out);
+    const int gh = H / p, gw = W / p, pv = C * p * p, nseg = (pv + 7) / 8;
+    const int64_t rows = B * gh * gw, total = rows * nseg;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const tok_item t = tok_item_of(i, gh, gw, nseg);
+        const bf16* fc = tok + t.row * pv + t.e0;
+        const float alpha = coef[t.b * 2], gamma = coef[t.b * 2 + 1];
+        U128 vc;
+        if (VEC) vc.h = ld_bf16x8(fc);
+        int64_t pix[8];
+        double xi[8], xh[8], dp[8];
+        float m[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {          // every load of the item before its first store (x_next may alias x_in / x_hat)
+            const int e = t.e0 + j;
+            if (!VEC && e >= pv) break;
+            const int c = e % C, pw = (e / C) % p, ph = e / (C * p);
+            pix[j] = ((t.b * C + c) * H + t.ti * p + ph) * W + t.tj * p + pw;
+            xi[j] = x_in[pix[j]];
+            xh[j] = x_hat[pix[j]];
+            dp[j] = second ? d_cur[pix[j]] : 0.0;
+            m[j] = M[pix[j]];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (!VEC && t.e0 + j >= pv) break;
+            const double D = sampler_guided(xi[j], bf2f(VEC ? vc.e[j] : fc[j]), m[j], c_skip, c_out, alpha, gamma);
+            double d;
+            x_next[pix[j]] = heun_from_denoised(xi[j], xh[j], D, t_in, t_hat, t_next, second, dp[j], d);
+            if (!second) d_cur[pix[j]] = d;
+        }
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void solver_coef_update_tok_kernel(const double* x_in, const bf16* tok, const float* M, const float* coef,
+                                                                     double* hist, double* x_next, int64_t B, int C, int H, int W, int p,
+                                                                     double t_in, float sigma_data, double a, double b, double c1, double c2) {
+    float c_skip, c_out;
+    heun_coef(t_in, sigma_data, c_skip, c_out);
+    const bool use_hist = c2 != 0.0;
+    const int gh = H / p, gw = W / p, pv = C * p * p, nseg = (pv + 7) / 8;
+    const int64_t rows = B * gh * gw, total = rows * nseg;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const tok_item t = tok_item_of(i, gh, gw, nseg);
+        const bf16* fc = tok + t.row * pv + t.e0;
+        const float alpha = coef[t.b * 2], gamma = coef[t.b * 2 + 1];
+        U128 vc;
+        if (VEC) vc.h = ld_bf16x8(fc);
+        int64_t pix[8];
+        double xi[8], hp[8];
+        float m[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {          // every load of the item before its first store (x_next may alias x_in)
+            const int e = t.e0 + j;
+            if (!VEC && e >= pv) break;
+            const int c = e % C, pw = (e / C) % p, ph = e / (C * p);
+            pix[j] = ((t.b * C + c) * H + t.ti * p + ph) * W + t.tj * p + pw;
+            xi[j] = x_in[pix[j]];
+            hp[j] = use_hist ? hist[pix[j]] : 0.0;
+            m[j] = M[pix[j]];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (!VEC && t.e0 + j >= pv) break;
+            const double den = sampler_guided(xi[j], bf2f(VEC ? vc.e[j] : fc[j]), m[j], c_skip, c_out, alpha, gamma);
+            x_next[pix[j]] = solver_from_denoised(xi[j], den, a, b, c1, c2, hp[j]);
+            hist[pix[j]] = den;
+        }
+    }
+}
+
+// Everything md_guidance_prepare(_tok) refuses about the mode and its parameters; the comparisons are written so that a NaN fails them.
+inline bool guidance_args_ok(int mode, double w, double phi, double eta, int has_r, double r, double beta) {
+    if (mode != MD_GUIDANCE_RESCALE && mode != MD_GUIDANCE_APG) return false;
+    if (!std::isfinite(w) || !std::isfinite(phi) || !std::isfinite(eta) || !std::isfinite(r) || !std::isfinite(beta)) return false;
+    if (!(phi >= 0.0 && phi <= 1.0)) return false;
+    if (has_r && !(r > 0.0)) return false;
+    return std::fabs(beta) < 1.0;
+}
+
+inline guidance_args make_guidance_args(int mode, double w, double phi, double eta, int has_r, double r, double beta, int first) {
+    guidance_args g;
+    g.mode = mode, g.first = first, g.has_r = has_r;
+    g.w = w, g.phi = phi, g.eta = eta, g.r = r;
+    g.beta = mode == MD_GUIDANCE_APG ? (float)beta : 0.f;      // rescale keeps no momentum
+    return g;
+}
+
 }  // namespace
 
 extern "C" int md_edm_prepare(const float* x0, const float* eps, const float* rnd, float* xn, float* sigma, float* cin,
@@ -620,6 +850,92 @@ extern "C" int md_edm_solver_update_guide_tok(const double* x_in, const void* to
 extern "C" int md_edm_churn(const double* x, const double* noise, double* x_hat, int64_t n, double coef, hipStream_t st) {
     if (!x || !noise || !x_hat || n <= 0) return MD_BAD_ARG;
     hipLaunchKernelGGL(churn_kernel, dim3(egrid(n)), dim3(256), 0, st, x, noise, x_hat, n, coef);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_guidance_prepare(const double* x_in, const float* F_c, const float* F_u, float* M, float* coef, double* moments, int64_t B,
+                                   int64_t per_sample, double t_in, float sigma_data, int32_t mode, double w, double rescale_phi,
+                                   double apg_eta, int32_t has_norm_threshold, double apg_norm_threshold, double apg_momentum, int32_t first,
+                                   hipStream_t st) {
+    if (!x_in || !F_c || !F_u || !M || !coef || !moments || B <= 0 || per_sample <= 0 || !(t_in > 0) ||
+        !guidance_args_ok(mode, w, rescale_phi, apg_eta, has_norm_threshold, apg_norm_threshold, apg_momentum))
+        return MD_BAD_ARG;
+    hipLaunchKernelGGL(guidance_prepare_kernel<false>, dim3((unsigned)B), dim3(256), 0, st, x_in, (const void*)F_c, (const void*)F_u, M, coef,
+                       moments, per_sample, 0, 0, 0, 0, t_in, sigma_data,
+                       make_guidance_args(mode, w, rescale_phi, apg_eta, has_norm_threshold, apg_norm_threshold, apg_momentum, first));
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_guidance_prepare_tok(const double* x_in, const void* tok_bf16, const void* tok_u_bf16, float* M, float* coef,
+                                       double* moments, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, double t_in, float sigma_data,
+                                       int32_t mode, double w, double rescale_phi, double apg_eta, int32_t has_norm_threshold,
+                                       double apg_norm_threshold, double apg_momentum, int32_t first, hipStream_t st) {
+    if (!x_in || !tok_bf16 || !tok_u_bf16 || !M || !coef || !moments || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
+        !(t_in > 0) || !guidance_args_ok(mode, w, rescale_phi, apg_eta, has_norm_threshold, apg_norm_threshold, apg_momentum))
+        return MD_BAD_ARG;
+    hipLaunchKernelGGL(guidance_prepare_kernel<true>, dim3((unsigned)B), dim3(256), 0, st, x_in, tok_bf16, tok_u_bf16, M, coef, moments,
+                       (int64_t)C * H * W, C, H, W, p, t_in, sigma_data,
+                       make_guidance_args(mode, w, rescale_phi, apg_eta, has_norm_threshold, apg_norm_threshold, apg_momentum, first));
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_edm_heun_update_coef(const double* x_hat, const double* x_in, const float* F_c, const float* M, const float* coef,
+                                       double* d_cur, double* x_next, int64_t B, int64_t per_sample, double t_in, double t_hat, double t_next,
+                                       float sigma_data, int32_t second, hipStream_t st) {
+    if (!x_hat || !x_in || !F_c || !M || !coef || !d_cur || !x_next || B <= 0 || per_sample <= 0 || !(t_in > 0)) return MD_BAD_ARG;
+    const int64_t n = B * per_sample;
+    hipLaunchKernelGGL(heun_coef_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_hat, x_in, F_c, M, coef, d_cur, x_next, n, per_sample, t_in,
+                       t_hat, t_next, sigma_data, second);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_edm_solver_update_coef(const double* x_in, const float* F_c, const float* M, const float* coef, double* hist, double* x_next,
+                                         int64_t B, int64_t per_sample, double t_in, float sigma_data, double a, double b, double c1, double c2,
+                                         hipStream_t st) {
+    if (!x_in || !F_c || !M || !coef || !hist || !x_next || B <= 0 || per_sample <= 0 || !(t_in > 0)) return MD_BAD_ARG;
+    const int64_t n = B * per_sample;
+    hipLaunchKernelGGL(solver_coef_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_in, F_c, M, coef, hist, x_next, n, per_sample, t_in,
+                       sigma_data, a, b, c1, c2);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_edm_heun_update_coef_tok(const double* x_hat, const double* x_in, const void* tok_bf16, const float* M, const float* coef,
+                                           double* d_cur, double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, double t_in,
+                                           double t_hat, double t_next, float sigma_data, int32_t second, hipStream_t st) {
+    if (!x_hat || !x_in || !tok_bf16 || !M || !coef || !d_cur || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
+        !(t_in > 0))
+        return MD_BAD_ARG;
+    const int pv = C * p * p;
+    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
+    if (pv % 8 == 0 && aligned16(tok_bf16))
+        hipLaunchKernelGGL(heun_coef_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, (const bf16*)tok_bf16, M, coef,
+                           d_cur, x_next, B, C, H, W, p, t_in, t_hat, t_next, sigma_data, second);
+    else
+        hipLaunchKernelGGL(heun_coef_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, (const bf16*)tok_bf16, M, coef,
+                           d_cur, x_next, B, C, H, W, p, t_in, t_hat, t_next, sigma_data, second);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_edm_solver_update_coef_tok(const double* x_in, const void* tok_bf16, const float* M, const float* coef, double* hist,
+                                             double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, double t_in,
+                                             float sigma_data, double a, double b, double c1, double c2, hipStream_t st) {
+    if (!x_in || !tok_bf16 || !M || !coef || !hist || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
+        !(t_in > 0))
+        return MD_BAD_ARG;
+    const int pv = C * p * p;
+    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
+    if (pv % 8 == 0 && aligned16(tok_bf16))
+        hipLaunchKernelGGL(solver_coef_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_in, (const bf16*)tok_bf16, M, coef, hist,
+                           x_next, B, C, H, W, p, t_in, sigma_data, a, b, c1, c2);
+    else
+        hipLaunchKernelGGL(solver_coef_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_in, (const bf16*)tok_bf16, M, coef, hist,
+                           x_next, B, C, H, W, p, t_in, sigma_data, a, b, c1, c2);
     MD_LAUNCH_CHECK();
     return 0;
 }

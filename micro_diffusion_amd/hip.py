@@ -242,6 +242,15 @@ _sig("md_edm_heun_update_guide_tok", P, P, P, P, P, P, I64, I32, I32, I32, I32, 
      I32, P)
 _sig("md_edm_solver_update_guide_tok", P, P, P, P, P, I64, I32, I32, I32, I32, F32, ctypes.c_double, F32, ctypes.c_double, ctypes.c_double,
      ctypes.c_double, ctypes.c_double, P)
+# guidance modes (CFG rescale, APG): per-sample moments and coefficients, then the update kernels with D = alpha_b * D_c + gamma_b * M
+GUIDANCE_RESCALE, GUIDANCE_APG = 1, 2       # MD_GUIDANCE_*
+F64 = ctypes.c_double
+_sig("md_guidance_prepare", P, P, P, P, P, P, I64, I64, F64, F32, I32, F64, F64, F64, I32, F64, F64, I32, P)
+_sig("md_guidance_prepare_tok", P, P, P, P, P, P, I64, I32, I32, I32, I32, F64, F32, I32, F64, F64, F64, I32, F64, F64, I32, P)
+_sig("md_edm_heun_update_coef", P, P, P, P, P, P, P, I64, I64, F64, F64, F64, F32, I32, P)
+_sig("md_edm_solver_update_coef", P, P, P, P, P, P, I64, I64, F64, F32, F64, F64, F64, F64, P)
+_sig("md_edm_heun_update_coef_tok", P, P, P, P, P, P, P, I64, I32, I32, I32, I32, F64, F64, F64, F32, I32, P)
+_sig("md_edm_solver_update_coef_tok", P, P, P, P, P, P, I64, I32, I32, I32, I32, F64, F32, F64, F64, F64, F64, P)
 _sig("md_sumsq", P, I32, I64, P, P)
 _sig("md_sumsq_finish", P, I64, P, P)
 _sig("md_checksum_u16", P, I64, P, P)

@@ -244,7 +244,8 @@ class LatentDiffusion(nn.Module):
     def edm_sampler_loop(self, x, y, steps: Optional[int] = None, cfg: float = 1.0, fused: Optional[bool] = None,
                          cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
                          guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
-                         **kwargs):
+                         guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
+                         apg_momentum: float = 0.0, **kwargs):
         """EDM sampler, fp64 state (model.py:231-297).  `fused` (None = whenever possible) selects the loop whose per-step arithmetic
         runs in fused HIP kernels; False keeps the reference's tensor-op formulation (generic forward functions).
         `cond_cache` (None = the environment variable MD_SAMPLER_CACHE, default off): encode the captions once for the whole run
@@ -270,11 +271,23 @@ class LatentDiffusion(nn.Module):
         state as it is.  With a mask the churn draw is made only when S_churn > 0 (without one the loop keeps the reference's draw).
         `resample` = r >= 1 (RePaint, Lugmayr et al. 2022; needs a mask; heun and euler): every step with t_next > 0 runs r times, and
         after each repetition but the last x <- x + sqrt(t_i^2 - t_next^2) * randn_like(x) takes the state back to level t_i.  Draws of one
-        repetition, in order: blend, churn (S_churn > 0), the step, re-noise.  samplers.edit_evaluations counts the evaluations."""
+        repetition, in order: blend, churn (S_churn > 0), the step, re-noise.  samplers.edit_evaluations counts the evaluations.
+        `guidance_mode`: how a guided evaluation combines the conditional denoised prediction D_c with the second operand
+        D_u (the unconditional half, or the guide's).  "cfg": D_u + cfg * (D_c - D_u) inside the update kernel, the default (its
+        launches and bits are untouched).  "rescale" (`guidance_rescale` = phi in [0, 1]): the cfg result scaled by phi * std(D_c) / std(result) + 1 - phi per
+        sample.  "apg" (`apg_eta`, `apg_norm_threshold` = r or None, `apg_momentum` = beta in (-1, 1)): the update M = (D_c - D_u) +
+        beta * M_prev of the previous guided evaluation, clipped to norm r per sample, its component parallel to D_c weighted by eta.
+        Both are alpha_b * D_c + gamma_b * M with per-sample coefficients (samplers.guidance_coefficients); they compose with every
+        argument above, and cfg <= 1 or an evaluation outside the interval runs unguided as in "cfg"."""
         ec = self.edm_config
         samplers.check_sampler(sampler, ec.S_churn)
         interval = samplers.guidance_interval_bounds(guidance_interval)
         samplers.check_guide(self.dit, guide, guide_captions)
+        samplers.check_guidance(guidance_mode, cfg, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum)
+        gmode = None                                # (mode, phi, eta, r or None, beta) of a run that is guided in a mode other than "cfg"
+        if guidance_mode != "cfg" and cfg > 1.0:
+            gmode = (guidance_mode, float(guidance_rescale), float(apg_eta), None if apg_norm_threshold is None else float(apg_norm_threshold),
+                     float(apg_momentum))
         samplers.check_edit(sampler, init_latents is not None, strength, inpaint_mask is not None, resample)
         n = ec.num_steps if steps is None else steps
         edit = None if init_latents is None else self._edit_operands(x, init_latents, strength, inpaint_mask, resample, n)
@@ -286,7 +299,7 @@ class LatentDiffusion(nn.Module):
             fused = can_fuse
         if fused:
             assert can_fuse, "the fused sampler needs CUDA tensors and no extra forward arguments"
-            return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, guide, guide_captions == "null", edit)
+            return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, guide, guide_captions == "null", edit, gmode)
         if guide is not None:
             fwd = self._autoguided_forward(guide, torch.zeros_like(y) if guide_captions == "null" else y, cfg) if cfg > 1.0 else self.dit.forward
         else:
@@ -295,6 +308,8 @@ class LatentDiffusion(nn.Module):
         def denoise(xs, sigma):
             f = fwd if interval is None or interval[0] <= float(sigma) <= interval[1] else self.dit.forward
             return self.model_forward_wrapper(xs.to(torch.float32), sigma.to(torch.float32), y, f, mask_ratio=0, **kwargs)["sample"].to(torch.float64)
+        if gmode is not None:
+            denoise = self._mode_guided_denoise(denoise, y, cfg, interval, guide, guide_captions == "null", gmode, kwargs)
         idx = torch.arange(n, dtype=torch.float64, device=x.device)
         inv_rho = 1 / ec.rho
         t_steps = (ec.sigma_max ** inv_rho + idx / (n - 1) * (ec.sigma_min ** inv_rho - ec.sigma_max ** inv_rho)) ** ec.rho
@@ -354,6 +369,38 @@ class LatentDiffusion(nn.Module):
                 raise ValueError("inpaint_mask must be bool or hold values in [0, 1] (1 = generate, 0 = keep init_latents)")
         return x0, m, samplers.edit_start_index(n, strength), resample
 
+    def _mode_guided_denoise(self, unguided, y, w: float, interval, guide, guide_null: bool, gmode, kwargs):
+        """denoise(xs, sigma) of the tensor-op loop in guidance mode "rescale" or "apg" (DESIGN.md 4.14), in plain torch: the
+        preconditioning of model_forward_wrapper (fp32) around one doubled-batch forward without cfg=, or with a guide around two
+        forwards; D_c = c_skip x + c_out F_c as everywhere, D_c - D_u = c_out (F_c - F_u) (c_skip x cancels), and the running difference,
+        the moments and the combine in fp64.  Outside the interval `unguided` runs and M stays."""
+        mode, phi, eta, r, beta = gmode
+        sd = self.edm_config.sigma_data
+        state = {"M": None}                         # the M of the previous guided evaluation of this run
+        y_u = y if guide is not None and not guide_null else torch.zeros_like(y)
+
+        def denoise(xs, sigma):
+            if not (interval is None or interval[0] <= float(sigma) <= interval[1]):
+                return unguided(xs, sigma)
+            xs, sigma = xs.to(torch.float32), sigma.to(torch.float32).reshape(-1, 1, 1, 1)
+            c_skip = sd ** 2 / (sigma ** 2 + sd ** 2)
+            c_out = sigma * sd / (sigma ** 2 + sd ** 2).sqrt()
+            net_in, c_noise = (1 / (sd ** 2 + sigma ** 2).sqrt()) * xs, (sigma.log() / 4).flatten()
+            if guide is None:
+                F = self.dit.forward(torch.cat([net_in, net_in], 0), c_noise, torch.cat([y, y_u], 0), mask_ratio=0, **kwargs)["sample"]
+                F_c, F_u = torch.split(F.to(torch.float32), len(F) // 2, dim=0)
+            else:
+                F_c = self.dit.forward_without_cfg(net_in, c_noise, y, mask_ratio=0, **kwargs)["sample"].to(torch.float32)
+                F_u = guide.forward_without_cfg(net_in, c_noise, y_u, mask_ratio=0, **kwargs)["sample"].to(torch.float32)
+            D_c = (c_skip * xs + c_out * F_c).to(torch.float64)
+            M = c_out.to(torch.float64) * (F_c.to(torch.float64) - F_u.to(torch.float64))
+            if mode == "apg" and beta != 0.0 and state["M"] is not None:
+                M = M + beta * state["M"]
+            state["M"] = M
+            alpha, gamma = samplers.guidance_coefficients(mode, samplers.guidance_moments(D_c, M), D_c[0].numel(), w, phi, eta, r)
+            return alpha.view(-1, 1, 1, 1) * D_c + gamma.view(-1, 1, 1, 1) * M
+        return denoise
+
     def _autoguided_forward(self, guide, y_guide, w: float):
         """The forward function of an autoguided evaluation for model_forward_wrapper: both networks on the same input at batch B, the
         guide with its own captions, combined in fp32 as the update kernels do (F = F_guide + w * (F_main - F_guide))."""
@@ -365,7 +412,7 @@ class LatentDiffusion(nn.Module):
 
     @torch.no_grad()
     def _edm_sampler_fused(self, x, y, steps: Optional[int], cfg: float, cond_cache: bool = False, sampler: str = "heun", interval=None,
-                           guide=None, guide_null: bool = False, edit=None):
+                           guide=None, guide_null: bool = False, edit=None, gmode=None):
         """The same loops with everything around the network evaluations in fused HIP kernels: md_edm_sampler_input (c_in scaling +
         guidance batch doubling) and md_edm_heun_update (guidance combine + preconditioning + fp64 Euler / Heun update) or, for
         euler / dpmpp_2m, md_edm_solver_update (the same with the linear-multistep update of samplers.solver_coefficients).
@@ -381,7 +428,11 @@ class LatentDiffusion(nn.Module):
         edit = (init_latents fp64, mask fp32 [mask_B, H * W] or None, i0, resample) from _edit_operands: md_edm_blend_known writes the
         SDEdit start into the state (in place on the fp64 copy of x, which is its noise operand), blends the known latents at level t_i
         into x_cur at the start of every repetition (one draw, one launch) and pastes them after the last step; a repetition that is
-        not the last ends with one draw and md_edm_churn in place on the state it produced (x_cur after the swap).  None: none of it."""
+        not the last ends with one draw and md_edm_churn in place on the state it produced (x_cur after the swap).  None: none of it.
+        gmode = (mode, phi, eta, r or None, beta) of guidance mode "rescale" / "apg" (DESIGN.md 4.14): M (fp32, the state's layout), coef
+        [B, 2] and moments [B, 5] are allocated once; every guided evaluation runs md_guidance_prepare(_tok) on the two outputs -- the
+        halves of the doubled batch, or main's and the guide's -- and then the _coef form of its update kernel, which reads the
+        conditional output, M and coef.  Nothing comes back to the host.  None ("cfg"): none of it."""
         ec, L, st = self.edm_config, hip.lib(), torch.cuda.current_stream().cuda_stream
         n = ec.num_steps if steps is None else steps
         idx = torch.arange(n, dtype=torch.float64)
@@ -394,6 +445,15 @@ class LatentDiffusion(nn.Module):
         levels = [s for i in range(i0, n) for s in ([t_hats[i]] + ([t_steps[i + 1]] if heun and i < n - 1 else []))]
         guided = any(samplers.is_guided(s, cfg, interval) for s in levels)      # no guided evaluation at all: the cfg = 1 run
         B, numel = x.shape[0], x.numel()
+        if not guided:
+            gmode = None
+        if gmode is not None:
+            g_kind = {"rescale": hip.GUIDANCE_RESCALE, "apg": hip.GUIDANCE_APG}[gmode[0]]
+            g_par = (g_kind, float(cfg), gmode[1], gmode[2], 0 if gmode[3] is None else 1, 1.0 if gmode[3] is None else gmode[3], gmode[4])
+            g_M = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
+            g_coef = torch.empty(B, 2, device=x.device, dtype=torch.float32)
+            g_moments = torch.empty(B, 5, device=x.device, dtype=torch.float64)
+            g_evals = [0]                           # guided evaluations so far: the first one does not read M
 
         def blend_known(noise, m, sigma):
             """x_cur <- m * x_cur + (1 - m) * (x0 + sigma * noise); m None: the whole state, noise None: x0 itself."""
@@ -448,10 +508,35 @@ class LatentDiffusion(nn.Module):
             Fg = guide.forward_without_cfg(net_in, t, y_g, 0)["sample"].to(torch.float32).contiguous() if auto and g_eval else None
             return F, dup, Fg
 
+        def prepare(Fd, x_in, t_in):
+            """In a guidance mode, for a guided evaluation: M, the moments and the coefficients from the two outputs; True when it ran."""
+            F, dup, Fg = Fd
+            if gmode is None or not (dup or Fg is not None):
+                return False
+            Fu = Fg.data_ptr() if Fg is not None else F.data_ptr() + (F.numel() // 2) * F.element_size()
+            first = 1 if g_evals[0] == 0 else 0
+            g_evals[0] += 1
+            if cond_cache:
+                hip.check(L.md_guidance_prepare_tok(x_in.data_ptr(), F.data_ptr(), Fu, g_M.data_ptr(), g_coef.data_ptr(), g_moments.data_ptr(),
+                                                    B, C, H, W, p, t_in, ec.sigma_data, *g_par, first, st), "md_guidance_prepare_tok")
+            else:
+                hip.check(L.md_guidance_prepare(x_in.data_ptr(), F.data_ptr(), Fu, g_M.data_ptr(), g_coef.data_ptr(), g_moments.data_ptr(),
+                                                B, numel // B, t_in, ec.sigma_data, *g_par, first, st), "md_guidance_prepare")
+            return True
+
         def update(Fd, x_in, t_in, t_hat, t_next, second):
             """x_nxt (and, on the first half-step, d_cur) from x_cur, the evaluated state x_in and the network output F."""
             F, dup, Fg = Fd
-            if Fg is not None and cond_cache:
+            if prepare(Fd, x_in, t_in):
+                if cond_cache:
+                    hip.check(L.md_edm_heun_update_coef_tok(x_cur.data_ptr(), x_in.data_ptr(), F.data_ptr(), g_M.data_ptr(), g_coef.data_ptr(),
+                                                            d_cur.data_ptr(), x_nxt.data_ptr(), B, C, H, W, p, t_in, t_hat, t_next,
+                                                            ec.sigma_data, second, st), "md_edm_heun_update_coef_tok")
+                else:
+                    hip.check(L.md_edm_heun_update_coef(x_cur.data_ptr(), x_in.data_ptr(), F.data_ptr(), g_M.data_ptr(), g_coef.data_ptr(),
+                                                        d_cur.data_ptr(), x_nxt.data_ptr(), B, numel // B, t_in, t_hat, t_next, ec.sigma_data,
+                                                        second, st), "md_edm_heun_update_coef")
+            elif Fg is not None and cond_cache:
                 hip.check(L.md_edm_heun_update_guide_tok(x_cur.data_ptr(), x_in.data_ptr(), F.data_ptr(), Fg.data_ptr(), d_cur.data_ptr(),
                                                          x_nxt.data_ptr(), B, C, H, W, p, float(cfg), t_in, t_hat, t_next, ec.sigma_data,
                                                          second, st), "md_edm_heun_update_guide_tok")
@@ -470,7 +555,16 @@ class LatentDiffusion(nn.Module):
         def solver_update(Fd, t_in, coef):
             """x_nxt = a x_cur + b (c1 D - c2 hist), hist = D; d_cur is the history buffer."""
             F, dup, Fg = Fd
-            if Fg is not None and cond_cache:
+            if prepare(Fd, x_cur, t_in):
+                if cond_cache:
+                    hip.check(L.md_edm_solver_update_coef_tok(x_cur.data_ptr(), F.data_ptr(), g_M.data_ptr(), g_coef.data_ptr(), d_cur.data_ptr(),
+                                                              x_nxt.data_ptr(), B, C, H, W, p, t_in, ec.sigma_data, *coef, st),
+                              "md_edm_solver_update_coef_tok")
+                else:
+                    hip.check(L.md_edm_solver_update_coef(x_cur.data_ptr(), F.data_ptr(), g_M.data_ptr(), g_coef.data_ptr(), d_cur.data_ptr(),
+                                                          x_nxt.data_ptr(), B, numel // B, t_in, ec.sigma_data, *coef, st),
+                              "md_edm_solver_update_coef")
+            elif Fg is not None and cond_cache:
                 hip.check(L.md_edm_solver_update_guide_tok(x_cur.data_ptr(), F.data_ptr(), Fg.data_ptr(), d_cur.data_ptr(), x_nxt.data_ptr(),
                                                            B, C, H, W, p, float(cfg), t_in, ec.sigma_data, *coef, st),
                           "md_edm_solver_update_guide_tok")
@@ -517,13 +611,18 @@ class LatentDiffusion(nn.Module):
     def generate(self, prompt: Optional[list] = None, tokenized_prompts=None, attention_mask=None, guidance_scale: float = 5.0,
                  num_inference_steps: int = 30, seed: Optional[int] = None, return_only_latents: bool = False,
                  cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
-                 guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1, **kwargs):
+                 guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
+                 guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
+                 apg_momentum: float = 0.0, **kwargs):
         """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache, sampler,
         guidance_interval, guide and guide_captions: as in edm_sampler_loop (with a guide, guidance_scale is the autoguidance weight).
         init_latents, strength, inpaint_mask and resample: image-to-image and inpainting as in edm_sampler_loop; the seeded draw below is
         then the unit noise added to init_latents.  init_latents are latents already (VAE latents * latent_scale, the space of the
-        trainer's image_latents): encoding an image into them stays the caller's vae.encode, a frozen third-party model."""
+        trainer's image_latents): encoding an image into them stays the caller's vae.encode, a frozen third-party model.
+        guidance_mode, guidance_rescale, apg_eta, apg_norm_threshold and apg_momentum: CFG rescale and adaptive projected guidance as in
+        edm_sampler_loop; they tame the over-saturation of plain guidance at this default guidance_scale."""
         samplers.check_guide(self.dit, guide, guide_captions)
+        samplers.check_guidance(guidance_mode, guidance_scale, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum)
         samplers.check_edit(sampler, init_latents is not None, strength, inpaint_mask is not None, resample)
         assert prompt or tokenized_prompts is not None, "Must provide either prompt or tokenized prompts"
         device = next(self.dit.parameters()).device
@@ -539,7 +638,9 @@ class LatentDiffusion(nn.Module):
         latents = torch.randn((len(emb), self.dit.in_channels, self.latent_res, self.latent_res), device=device, generator=gen)
         latents = self.edm_sampler_loop(latents, emb, num_inference_steps, cfg=guidance_scale, cond_cache=cond_cache, sampler=sampler,
                                         guidance_interval=guidance_interval, guide=guide, guide_captions=guide_captions,
-                                        init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, resample=resample)
+                                        init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, resample=resample,
+                                        guidance_mode=guidance_mode, guidance_rescale=guidance_rescale, apg_eta=apg_eta,
+                                        apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum)
         if return_only_latents:
             return latents
         image = self.vae.decode((latents / self.latent_scale).to(DATA_TYPES[self.dtype])).sample

@@ -98,6 +98,85 @@ def is_guided(sigma: float, cfg: float, interval: Optional[Tuple[float, float]])
     return cfg > 1.0 and (interval is None or interval[0] <= sigma <= interval[1])
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Guidance modes.  A guided evaluation has the conditional denoised prediction D_c and a second operand D_u (the
+# unconditional half of a doubled batch, or a guide network's).  "cfg" combines them as D_u + w (D_c - D_u).  "rescale" (Lin et al. 2024)
+# and "apg" (Sadat et al. 2024) return alpha_b D_c + gamma_b M with M = (D_c - D_u) + beta M_prev the running difference and per-sample
+# coefficients from five moments over [C, H, W]; guidance_coefficients is that table, shared by the tensor-op loop and the tests
+# (md_guidance_prepare is its device form).
+# ---------------------------------------------------------------------------------------------------------------------
+GUIDANCE_MODES = ("cfg", "rescale", "apg")
+
+
+def _finite_number(v) -> bool:
+    try:
+        return not isinstance(v, (bool, str)) and math.isfinite(float(v))
+    except (TypeError, ValueError, RuntimeError):
+        return False
+
+
+def check_guidance(mode: str = "cfg", cfg: float = 1.0, guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
+                   apg_momentum: float = 0.0) -> str:
+    """Refuse, before anything is launched or allocated, a guidance request that is not defined: an unknown mode, a parameter of a
+    mode that is not selected (a non-default guidance_rescale outside "rescale", a non-default apg_* outside "apg"), guidance_rescale
+    outside [0, 1], apg_norm_threshold <= 0, |apg_momentum| >= 1, or anything that is not a finite number."""
+    if mode not in GUIDANCE_MODES:
+        raise ValueError(f"unknown guidance_mode {mode!r}: choose one of {', '.join(GUIDANCE_MODES)}")
+    for name, v in (("cfg", cfg), ("guidance_rescale", guidance_rescale), ("apg_eta", apg_eta), ("apg_momentum", apg_momentum)):
+        if not _finite_number(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    if apg_norm_threshold is not None and not _finite_number(apg_norm_threshold):
+        raise ValueError(f"apg_norm_threshold must be None or a finite number, got {apg_norm_threshold!r}")
+    if mode != "rescale" and float(guidance_rescale) != 0.0:
+        raise ValueError(f"guidance_rescale={guidance_rescale!r} needs guidance_mode='rescale' (got {mode!r})")
+    if mode != "apg" and (float(apg_eta) != 0.0 or apg_norm_threshold is not None or float(apg_momentum) != 0.0):
+        raise ValueError(f"apg_eta, apg_norm_threshold and apg_momentum need guidance_mode='apg' (got {mode!r})")
+    if not 0.0 <= float(guidance_rescale) <= 1.0:
+        raise ValueError(f"guidance_rescale must be in [0, 1], got {guidance_rescale!r}")
+    if apg_norm_threshold is not None and float(apg_norm_threshold) <= 0.0:
+        raise ValueError(f"apg_norm_threshold must be None or > 0, got {apg_norm_threshold!r}")
+    if abs(float(apg_momentum)) >= 1.0:
+        raise ValueError(f"apg_momentum must be in (-1, 1), got {apg_momentum!r}")
+    return mode
+
+
+def guidance_moments(d_c, m):
+    """[B, 5] fp64: (S_c, S_m, Q_cc, Q_mm, Q_cm) of every sample of two torch tensors [B, ...]."""
+    import torch
+    d_c, m = d_c.to(torch.float64).flatten(1), m.to(torch.float64).flatten(1)
+    return torch.stack([d_c.sum(1), m.sum(1), (d_c * d_c).sum(1), (m * m).sum(1), (d_c * m).sum(1)], 1)
+
+
+def guidance_coefficients(mode: str, moments, n: int, w: float, guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None):
+    """(alpha, gamma), two fp64 tensors [B], of the guided prediction alpha_b D_c + gamma_b M from moments [B, 5] = (S_c, S_m, Q_cc,
+    Q_mm, Q_cm) over the n elements of each sample.  The momentum is part of M, not of this table.
+      apg      s = min(1, r / sqrt(Q_mm)) (1 without r or when Q_mm = 0);  p = s Q_cm / Q_cc (0 when Q_cc = 0);
+               alpha = 1 - (w - 1)(1 - eta) p;  gamma = (w - 1) s
+      rescale  var_c = max(Q_cc / n - (S_c / n)^2, 0);  var_g the same of D_c + (w - 1) M;  k = phi sqrt(var_c / var_g) + 1 - phi
+               (1 when var_g <= 0);  alpha = k;  gamma = k (w - 1)"""
+    import torch
+    if mode not in ("rescale", "apg"):
+        raise ValueError(f"no coefficients for guidance_mode {mode!r}: choose 'rescale' or 'apg'")
+    mo = torch.as_tensor(moments, dtype=torch.float64)
+    S_c, S_m, Q_cc, Q_mm, Q_cm = mo.unbind(-1)
+    w1, one = float(w) - 1.0, torch.ones_like(S_c)
+    if mode == "apg":
+        s = one
+        if apg_norm_threshold is not None:
+            pos = Q_mm > 0
+            s = torch.where(pos, torch.clamp(float(apg_norm_threshold) / torch.where(pos, Q_mm, one).sqrt(), max=1.0), one)
+        pos = Q_cc > 0
+        p = torch.where(pos, s * Q_cm / torch.where(pos, Q_cc, one), torch.zeros_like(S_c))
+        return 1.0 - w1 * (1.0 - float(apg_eta)) * p, w1 * s
+    phi = float(guidance_rescale)
+    var_c = (Q_cc / n - (S_c / n) ** 2).clamp(min=0.0)
+    S_g = S_c + w1 * S_m
+    var_g = (Q_cc + 2.0 * w1 * Q_cm + w1 * w1 * Q_mm) / n - (S_g / n) ** 2
+    pos = var_g > 0
+    k = torch.where(pos, phi * (var_c / torch.where(pos, var_g, one)).sqrt() + 1.0 - phi, one)
+    return k, k * w1
+
+
 GUIDE_CAPTIONS = ("same", "null")           # what an autoguidance guide is conditioned on: the captions, or zeroed captions
 GUIDE_GEOMETRY = ("in_channels", "patch_size", "input_size", "caption_channels")
 
