@@ -321,6 +321,34 @@ int md_moe_combine_bwd(const void* dbr, const void* h2, const int32_t* rowidx, c
 int md_moe_dispatch_bwd(const void* dxin, const int32_t* slot, void* dx, const float* probs, int64_t ldp, const float* dgval,
                         void* dlogits, int64_t ldo, int64_t B, int64_t S, int32_t E, int32_t k, int64_t C, hipStream_t stream);
 
+/* Masked-expert pruning (added under ABI 6: new symbols only).  A MoE block whose output is masked right behind it (the last
+ * patch-mixer block: dit.py:495-504 keeps len_keep of the S tokens of a sample) needs its expert MLPs only on routed rows whose
+ * token survives.  md_moe_compact_kept reads what md_moe_route left (after any override) and ids_restore of md_get_mask (a token
+ * is kept iff ids_restore < len_keep) and writes, per expert e, with stride = B*k:
+ *   rowidx_c[e*stride + p], gval_c[e*stride + p]   the kept routed rows in list order (sample-major, then rank), p < count[e];
+ *                                                  p in [count[e], stride): pad rows -- the expert's first routed row, gate value 0
+ *   count[e]                                       int32
+ *   slot_c[token*E + e]                            p, or -1 (every dropped token: -1 for every expert)
+ * The order comes from prefix sums (per-chunk counts in ws, then a scan inside each workgroup): no atomics.  ws: int32 workspace of
+ * ws_ints >= E * ceil(B*k / 1024) elements, dead when the call's kernels have run.  B*S < 2^31, B*k <= 65535 * 1024.
+ * md_moe_gather_compact / md_moe_combine_bwd_compact are md_gather_rows / md_moe_combine_bwd over rows e*stride + j, j < cap, of
+ * every expert (dst / h2 / dh2 are [E, stride, C], dgval [E, stride]).  md_moe_combine_abs / md_moe_dispatch_bwd_abs are
+ * md_moe_combine / md_moe_dispatch_bwd with slot_c holding the absolute position in the expert's list: they index (e, slot_c)
+ * where the originals index (e, n*k + slot), same kernels, same arithmetic in expert order, and still write every token row (a
+ * token without an expert: br = 0, out = res, dx = 0, dlogits = 0). */
+int md_moe_compact_kept(const int32_t* rowidx, const float* gval, const int32_t* ids_restore, int64_t len_keep, int64_t B, int64_t S,
+                        int32_t E, int32_t k, int32_t* rowidx_c, float* gval_c, int32_t* count, int32_t* slot_c, int32_t* ws,
+                        int64_t ws_ints, hipStream_t stream);
+int md_moe_gather_compact(const void* src, int64_t ld_src, const int32_t* rowidx_c, void* dst, int32_t E, int64_t cap, int64_t stride,
+                          int64_t C, hipStream_t stream);
+int md_moe_combine_abs(const void* h2, const float* gval_c, const int32_t* slot_c, const void* res, const void* gate, int64_t ldgate,
+                       void* br, void* out, int64_t B, int64_t S, int32_t E, int64_t stride, int64_t C, hipStream_t stream);
+int md_moe_combine_bwd_compact(const void* dbr, const void* h2, const int32_t* rowidx_c, const float* gval_c, void* dh2, float* dgval,
+                               int32_t E, int64_t cap, int64_t stride, int64_t C, hipStream_t stream);
+int md_moe_dispatch_bwd_abs(const void* dxin, const int32_t* slot_c, void* dx, const float* probs, int64_t ldp, const float* dgval,
+                            void* dlogits, int64_t ldo, int64_t B, int64_t S, int32_t E, int64_t stride, int64_t C,
+                            hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------- EDM front / back end */
 int md_edm_prepare(const float* x0, const float* eps, const float* rnd, float* xn, float* sigma, float* cin, float* cnoise,
                    int64_t B, int64_t per_sample, float p_mean, float p_std, float sigma_data, hipStream_t stream);

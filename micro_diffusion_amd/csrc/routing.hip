@@ -224,6 +224,137 @@ __global__ __launch_bounds__(256) void moe_softmax_bwd_kernel(const float* probs
     for (int e = 0; e < ldo; ++e) dlogits[m * ldo + e] = f2bf(e < E ? p[e] * (dp[e] - dot) : 0.f);
 }
 
+// ---------------------------------------------------------------------------------------------- masked-expert pruning
+// The last patch-mixer block runs on all S tokens of a sample, and the masking right behind it keeps len_keep of them: a routed
+// row whose token is dropped feeds no result, forward or backward.  md_moe_compact_kept lists, per expert, the routed rows whose
+// token survives; the expert GEMMs then run on the first `cap` rows of each list.  The combine / dispatch-backward kernels above
+// serve the compact lists unchanged: with k = 0 their index (e, n*k + slot) IS the absolute position (e, slot).
+__global__ __launch_bounds__(256) void fill_i32_kernel(int32_t* p, int64_t n, int32_t v) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = v;
+}
+
+// Stream compaction in two launches, grid = (chunks of 1024 list entries, expert).  The count kernel leaves the number of kept
+// entries of every chunk in ws[e, chunk]; the write kernel adds up the chunks in front of its own (its base), ranks its own kept
+// entries with a prefix sum over the workgroup (thread t owns the 4 consecutive entries 4 t .. 4 t + 3), and writes them at base +
+// rank: list order (sample-major, then rank) without any atomic.  Positions [count, Bk) become pad rows -- the expert's first
+// routed row (a valid token) with gate value 0 -- written by the workgroup whose chunk holds that position.
+constexpr int CK = 1024;
+
+__device__ __forceinline__ int block_sum_256(int v, int* s_red) {   // all 256 threads get the sum; s_red: 256 ints
+    const int tid = threadIdx.x;
+    __syncthreads();
+    s_red[tid] = v;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) s_red[tid] += s_red[tid + off];
+        __syncthreads();
+    }
+    return s_red[0];
+}
+
+__global__ __launch_bounds__(256) void moe_compact_count_kernel(const int32_t* rowidx, const int32_t* ids_restore, int32_t len_keep,
+                                                                int64_t Bk, int nchunk, int32_t* ws) {
+    __shared__ int s_red[256];
+    const int e = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
+    int cnt = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = (int64_t)c * CK + tid * 4 + j;
+        if (i < Bk) cnt += ids_restore[rowidx[(int64_t)e * Bk + i]] < len_keep;
+    }
+    cnt = block_sum_256(cnt, s_red);
+    if (tid == 0) ws[(int64_t)e * nchunk + c] = cnt;
+}
+
+__global__ __launch_bounds__(256) void moe_compact_write_kernel(const int32_t* rowidx, const float* gval, const int32_t* ids_restore,
+                                                                int32_t len_keep, int64_t Bk, int E, int nchunk, const int32_t* ws,
+                                                                int32_t* rowidx_c, float* gval_c, int32_t* count, int32_t* slot_c) {
+    __shared__ int s_red[256];
+    __shared__ int s_scan[256];
+    const int e = blockIdx.y, c = blockIdx.x, tid = threadIdx.x;
+    int before = 0, all = 0;
+    for (int j = tid; j < nchunk; j += 256) {
+        const int v = ws[(int64_t)e * nchunk + j];
+        all += v;
+        if (j < c) before += v;
+    }
+    const int base = block_sum_256(before, s_red);
+    const int total = block_sum_256(all, s_red);
+    int32_t tok[4];
+    bool kp[4];
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = (int64_t)c * CK + tid * 4 + j;
+        tok[j] = i < Bk ? rowidx[(int64_t)e * Bk + i] : 0;
+        kp[j] = i < Bk && ids_restore[tok[j]] < len_keep;
+        mine += kp[j];
+    }
+    s_scan[tid] = mine;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int v = tid >= off ? s_scan[tid - off] : 0;
+        __syncthreads();
+        s_scan[tid] += v;
+        __syncthreads();
+    }
+    int64_t pos = base + s_scan[tid] - mine;
+    const int32_t padtok = rowidx[(int64_t)e * Bk];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = (int64_t)c * CK + tid * 4 + j;
+        if (kp[j]) {
+            rowidx_c[(int64_t)e * Bk + pos] = tok[j];
+            gval_c[(int64_t)e * Bk + pos] = gval[(int64_t)e * Bk + i];
+            slot_c[(int64_t)tok[j] * E + e] = (int32_t)pos;
+            ++pos;
+        }
+        if (i < Bk && i >= total) {
+            rowidx_c[(int64_t)e * Bk + i] = padtok;
+            gval_c[(int64_t)e * Bk + i] = 0.f;
+        }
+    }
+    if (c == 0 && tid == 0) count[e] = total;
+}
+
+// dst[e*stride + j, :] = src[idx[e*stride + j], :] for j < cap   (grid.y = expert)
+__global__ __launch_bounds__(256) void gather_rows_compact_kernel(const bf16* src, int64_t lds_, const int32_t* idx, bf16* dst,
+                                                                  int64_t cap, int64_t stride, int64_t C) {
+    const int64_t cpr = C / 8, total = cap * cpr, base = (int64_t)blockIdx.y * stride;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = base + i / cpr, c = (i % cpr) * 8;
+        *reinterpret_cast<uint4*>(dst + r * C + c) = *reinterpret_cast<const uint4*>(src + (int64_t)idx[r] * lds_ + c);
+    }
+}
+
+// moe_combine_bwd_kernel over the first cap rows of every expert's compact list (grid.y = expert, rows e*stride + j)
+__global__ __launch_bounds__(256) void moe_combine_bwd_compact_kernel(const bf16* dbr, const bf16* h2, const int32_t* rowidx,
+                                                                      const float* gval, bf16* dh2, float* dgval, int64_t cap,
+                                                                      int64_t stride, int64_t C) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    const int64_t base = (int64_t)blockIdx.y * stride;
+    for (int64_t j = wave; j < cap; j += nwaves) {
+        const int64_t r = base + j;
+        const int64_t tok = rowidx[r];
+        const float g = gval[r];
+        float dot = 0.f;
+        for (int c = lane * 8; c < C; c += 512) {
+            const bf16x8 d = ld_bf16x8(dbr + tok * C + c), h = ld_bf16x8(h2 + r * C + c);
+            bf16x8 o;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float dv = bf2f(d[i]);
+                dot += dv * bf2f(h[i]);
+                o[i] = f2bf(g * dv);
+            }
+            st_bf16x8(dh2 + r * C + c, o);
+        }
+        dot = wave_sum(dot);
+        if (lane == 0) dgval[r] = dot;
+    }
+}
+
 inline int rgrid(int64_t work) {
     int64_t g = (work + 255) / 256;
     if (g > 8192) g = 8192;
@@ -321,6 +452,78 @@ extern "C" int md_moe_dispatch_bwd(const void* dxin, const int32_t* slot, void* 
                            E, k, B * k, C);
     hipLaunchKernelGGL(moe_softmax_bwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, probs, ldp, dgval, slot,
                        (bf16*)dlogits, ldo, M, S, E, k, B * k);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- masked-expert pruning
+extern "C" int md_moe_compact_kept(const int32_t* rowidx, const float* gval, const int32_t* ids_restore, int64_t len_keep, int64_t B,
+                                   int64_t S, int32_t E, int32_t k, int32_t* rowidx_c, float* gval_c, int32_t* count,
+                                   int32_t* slot_c, int32_t* ws, int64_t ws_ints, hipStream_t st) {
+    if (!rowidx || !gval || !ids_restore || !rowidx_c || !gval_c || !count || !slot_c || !ws || B <= 0 || S <= 0 || E <= 0 ||
+        E > 16 || k <= 0 || k > S || len_keep <= 0 || len_keep > S || B * S >= ((int64_t)1 << 31))
+        return MD_BAD_ARG;
+    const int64_t Bk = B * k, nchunk = (Bk + CK - 1) / CK;
+    if (nchunk > 65535 || ws_ints < E * nchunk) return MD_BAD_ARG;
+    hipLaunchKernelGGL(fill_i32_kernel, dim3(rgrid(B * S * E)), dim3(256), 0, st, slot_c, B * S * E, (int32_t)-1);
+    hipLaunchKernelGGL(moe_compact_count_kernel, dim3((unsigned)nchunk, (unsigned)E), dim3(256), 0, st, rowidx, ids_restore,
+                       (int32_t)len_keep, Bk, (int)nchunk, ws);
+    hipLaunchKernelGGL(moe_compact_write_kernel, dim3((unsigned)nchunk, (unsigned)E), dim3(256), 0, st, rowidx, gval, ids_restore,
+                       (int32_t)len_keep, Bk, (int)E, (int)nchunk, (const int32_t*)ws, rowidx_c, gval_c, count, slot_c);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_moe_gather_compact(const void* src, int64_t ld_src, const int32_t* rowidx_c, void* dst, int32_t E, int64_t cap,
+                                     int64_t stride, int64_t C, hipStream_t st) {
+    if (!src || !rowidx_c || !dst || E <= 0 || E > 16 || cap <= 0 || cap > stride || C <= 0 || C % 8 || ld_src % 8) return MD_BAD_ARG;
+    hipLaunchKernelGGL(gather_rows_compact_kernel, dim3(rgrid(cap * C / 8), (unsigned)E), dim3(256), 0, st, (const bf16*)src, ld_src,
+                       rowidx_c, (bf16*)dst, cap, stride, C);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_moe_combine_abs(const void* h2, const float* gval_c, const int32_t* slot_c, const void* res, const void* gate,
+                                  int64_t ldgate, void* br, void* out, int64_t B, int64_t S, int32_t E, int64_t stride, int64_t C,
+                                  hipStream_t st) {
+    if (!h2 || !gval_c || !slot_c || !res || !gate || !br || !out || B <= 0 || S <= 0 || E <= 0 || E > 16 || stride <= 0 || C <= 0 ||
+        C % 8 || ldgate % 8)
+        return MD_BAD_ARG;
+    if (E <= 8)
+        hipLaunchKernelGGL(moe_combine_kernel<8>, dim3(wgrid(B * S)), dim3(256), 0, st, (const bf16*)h2, gval_c, slot_c,
+                           (const bf16*)res, (const bf16*)gate, ldgate, (bf16*)br, (bf16*)out, B * S, S, E, 0, stride, C);
+    else
+        hipLaunchKernelGGL(moe_combine_kernel<16>, dim3(wgrid(B * S)), dim3(256), 0, st, (const bf16*)h2, gval_c, slot_c,
+                           (const bf16*)res, (const bf16*)gate, ldgate, (bf16*)br, (bf16*)out, B * S, S, E, 0, stride, C);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_moe_combine_bwd_compact(const void* dbr, const void* h2, const int32_t* rowidx_c, const float* gval_c, void* dh2,
+                                          float* dgval, int32_t E, int64_t cap, int64_t stride, int64_t C, hipStream_t st) {
+    if (!dbr || !h2 || !rowidx_c || !gval_c || !dh2 || !dgval || E <= 0 || E > 16 || cap <= 0 || cap > stride || C <= 0 || C % 8)
+        return MD_BAD_ARG;
+    hipLaunchKernelGGL(moe_combine_bwd_compact_kernel, dim3(wgrid(cap), (unsigned)E), dim3(256), 0, st, (const bf16*)dbr,
+                       (const bf16*)h2, rowidx_c, gval_c, (bf16*)dh2, dgval, cap, stride, C);
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int md_moe_dispatch_bwd_abs(const void* dxin, const int32_t* slot_c, void* dx, const float* probs, int64_t ldp,
+                                       const float* dgval, void* dlogits, int64_t ldo, int64_t B, int64_t S, int32_t E,
+                                       int64_t stride, int64_t C, hipStream_t st) {
+    if (!dxin || !slot_c || !dx || !probs || !dgval || !dlogits || B <= 0 || S <= 0 || E <= 0 || E > 16 || stride <= 0 || C <= 0 ||
+        C % 8 || ldo < E || ldo > 16)
+        return MD_BAD_ARG;
+    const int64_t M = B * S;
+    if (E <= 8)
+        hipLaunchKernelGGL(moe_scatter_sum_kernel<8>, dim3(wgrid(M)), dim3(256), 0, st, (const bf16*)dxin, slot_c, (bf16*)dx, M, S, E,
+                           0, stride, C);
+    else
+        hipLaunchKernelGGL(moe_scatter_sum_kernel<16>, dim3(wgrid(M)), dim3(256), 0, st, (const bf16*)dxin, slot_c, (bf16*)dx, M, S, E,
+                           0, stride, C);
+    hipLaunchKernelGGL(moe_softmax_bwd_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, probs, ldp, dgval, slot_c,
+                       (bf16*)dlogits, ldo, M, S, E, 0, stride);
     MD_LAUNCH_CHECK();
     return 0;
 }

@@ -21,6 +21,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import time
 from ctypes import byref
 from typing import Dict, List, Optional
 
@@ -161,6 +162,17 @@ class DiTEngine:
         # marginals to its row right behind md_moe_route (one md_moe_route_stats call).  None: no launch, no buffer.  Its tables and
         # workspace are its own allocations: arena sizes, addresses and the tape are those of an unarmed pass.
         self.route_stats = None
+        # Masked-expert pruning: the masking right behind the last patch-mixer block keeps Tk of T tokens, so when that block
+        # is MoE its expert MLPs (forward, both data gradients, both weight gradients) run only on the routed rows whose token survives --
+        # about (1 - mask_ratio) of them.  Routing stays dense and the tape's probs / rowidx / gval / slot are those of the dense pass.
+        # Costs ONE host wait per microbatch (the per-expert counts, 4 E bytes): a microbatch is then not capturable as a hipGraph.
+        # Off (MD_PRUNE_MASKED_EXPERTS=0 or this attribute): the launch sequence is that of the dense pass.
+        self.prune_masked_experts = os.environ.get("MD_PRUNE_MASKED_EXPERTS", "1") != "0"
+        self.prune_granule = 256           # the pruned GEMMs run on ceil(max count / granule) * granule rows per expert: whole 256-row tiles keep
+        #                                    every launch on its dense counterpart's kernel family (w4), contraction a multiple of 128 for _ksplit
+        self.prune_wait_us = None          # tests / profiling: list that receives the host time of every count readback, in microseconds
+        self._prune_host = None            # pinned int32[16] the counts land in
+        self.route_log = None              # tests: list that receives the name of every routing-family entry point a MoE block calls
         self.ws = torch.empty(128 << 20, device=self.dev, dtype=F32)  # 512 MiB split-K workspace
         # Fixed-address activation memory (opt-in: the caller must run forward -> backward strictly in turn, as the Trainer
         # does; two forwards in flight would share the tape arena).
@@ -681,9 +693,11 @@ class DiTEngine:
         self._qkln_fwd(kv.data_ptr(), Mc, 2 * hx, 0, hx, rk.data_ptr())
         return rk, None
 
-    def _block_fwd(self, bp: BlockPlan, x, ycond, B, S, Lc, gc, mod_all=None, kv=None):
+    def _block_fwd(self, bp: BlockPlan, x, ycond, B, S, Lc, gc, mod_all=None, kv=None, keep=None):
         """kv: this block's entry of Conditioning.kv -- the caption-side projection and its K-LayerNorm are then skipped (ycond is not
-        read; inference only: the tape holds no K rstd for a backward)."""
+        read; inference only: the tape holds no K rstd for a backward).
+        keep: (ids_restore [B, S] int32, Tk) when only the tokens with ids_restore < Tk of this block's output are ever read (the
+        last patch-mixer block under masking): a MoE block then runs its experts on the routed rows of those tokens alone."""
         L, st, cfg = self.L, self._st(), self.cfg
         d, h, hx, f = bp.dim, bp.attn_hidden, bp.xattn_hidden, bp.ffn_hidden
         M, Mc, D = B * S, B * Lc, cfg.dim
@@ -780,22 +794,64 @@ class DiTEngine:
                 self._override_routing(t, self.route_override[n], B, S, E, k)
             if self.route_stats is not None:    # after the injection: the statistics describe the routing the layer runs with
                 self.route_stats.record(n, t.slot, t.probs, ldl, t.gval, B, S, k)
+            # rows per expert the expert GEMMs run on: Bk, or -- pruned -- the first `cap` rows of the compact lists.  Buffer sizes do
+            # not depend on cap (the arenas are sized on the first pass); only the launch extents do.
+            t.cap = self._compact_kept(t, keep, B, S, E, k) if keep is not None else None
+            rows = t.cap or Bk
             t.xin = self.empty(E, Bk, d)
-            hip.check(L.md_gather_rows(t.xm3.data_ptr(), d, t.rowidx.data_ptr(), t.xin.data_ptr(), d, E * Bk, d, st), "gather")
+            if t.cap is None:
+                hip.check(L.md_gather_rows(t.xm3.data_ptr(), d, t.rowidx.data_ptr(), t.xin.data_ptr(), d, E * Bk, d, st), "gather")
+            else:
+                hip.check(L.md_moe_gather_compact(t.xm3.data_ptr(), d, t.rowidx_c.data_ptr(), t.xin.data_ptr(), E, rows, Bk, d, st),
+                          "gather_compact")
             t.hpre = self.empty(E, Bk, f)         # the pre-activation -- or, with moe_cache_dact, gelu'(pre-activation): nothing but
             t.hact = self.empty(E, Bk, f)         # the backward's activation derivative ever reads it (md_gemm_args.dact_cached)
             t.hpre_is_dact = 1 if self.moe_cache_dact else 0
             w1, w2 = self.S[n + ".mlp.w1"], self.S[n + ".mlp.w2"]       # [E, d, f], [E, f, d]
-            self._gemm(A=t.xin.data_ptr(), B=w1.data_ptr(), C=t.hact.data_ptr(), C2=t.hpre.data_ptr(), M=Bk, N=f, K=d, lda=d,
+            self._gemm(A=t.xin.data_ptr(), B=w1.data_ptr(), C=t.hact.data_ptr(), C2=t.hpre.data_ptr(), M=rows, N=f, K=d, lda=d,
                        ldb=f, ldc=f, ldc2=f, sA=Bk * d, sB=d * f, sC=Bk * f, sC2=Bk * f, batch=E, ksplit=1, a_kcontig=1,
                        b_kcontig=0, mode=hip.EPI_STORE_BF16, act=hip.ACT_GELU_ERF, alpha=1.0, dact_cached=t.hpre_is_dact)
             t.h2 = self.empty(E, Bk, d)
-            self._gemm(A=t.hact.data_ptr(), B=w2.data_ptr(), C=t.h2.data_ptr(), M=Bk, N=d, K=f, lda=f, ldb=d, ldc=d,
+            self._gemm(A=t.hact.data_ptr(), B=w2.data_ptr(), C=t.h2.data_ptr(), M=rows, N=d, K=f, lda=f, ldb=d, ldc=d,
                        sA=Bk * f, sB=f * d, sC=Bk * d, batch=E, ksplit=1, a_kcontig=1, b_kcontig=0, mode=hip.EPI_STORE_BF16,
                        act=0, alpha=1.0)
-            hip.check(L.md_moe_combine(t.h2.data_ptr(), t.gval.data_ptr(), t.slot.data_ptr(), x2.data_ptr(), gate_mlp, ldm,
-                                       t.br3.data_ptr(), x3.data_ptr(), B, S, E, k, d, st), "moe_combine")
+            if t.cap is None:
+                hip.check(L.md_moe_combine(t.h2.data_ptr(), t.gval.data_ptr(), t.slot.data_ptr(), x2.data_ptr(), gate_mlp, ldm,
+                                           t.br3.data_ptr(), x3.data_ptr(), B, S, E, k, d, st), "moe_combine")
+            else:       # every token row is written: a dropped token gets br3 = 0 and x3 = x2
+                hip.check(L.md_moe_combine_abs(t.h2.data_ptr(), t.gval_c.data_ptr(), t.slot_c.data_ptr(), x2.data_ptr(), gate_mlp, ldm,
+                                               t.br3.data_ptr(), x3.data_ptr(), B, S, E, Bk, d, st), "moe_combine_abs")
+            if self.route_log is not None:
+                self.route_log += ["moe_route", "gather" if t.cap is None else "gather_compact", "combine" if t.cap is None else "combine_abs"]
         return x3, t
+
+    def _compact_kept(self, t, keep, B, S, E, k):
+        """Compact lists of the routed rows whose token survives the mask (md_moe_compact_kept; after any route_override) on the tape
+        (rowidx_c, gval_c [E, B*k], slot_c [B*S, E]); returns the rows per expert the pruned GEMMs run on, or None: nothing to gain
+        (the fullest expert needs all B*k rows once rounded up to the granule), the block runs dense.
+        The per-expert counts come back through pinned memory and the host WAITS for them: the one synchronisation of the step path."""
+        ids_restore, Tk = keep
+        Bk = B * k
+        t.rowidx_c = self.empty(E, Bk, dtype=I32)
+        t.gval_c = self.empty(E, Bk, dtype=F32)
+        t.slot_c = self.empty(B * S, E, dtype=I32)
+        count = self.empty(16, dtype=I32)
+        ws = self.empty(E * ((Bk + 1023) // 1024), dtype=I32)
+        hip.check(self.L.md_moe_compact_kept(t.rowidx.data_ptr(), t.gval.data_ptr(), ids_restore.data_ptr(), Tk, B, S, E, k,
+                                             t.rowidx_c.data_ptr(), t.gval_c.data_ptr(), count.data_ptr(), t.slot_c.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), self._st()), "moe_compact_kept")
+        if self.route_log is not None:
+            self.route_log.append("compact_kept")
+        if self._prune_host is None:
+            self._prune_host = torch.empty(16, dtype=I32, pin_memory=True)
+        t0 = time.perf_counter()
+        self._prune_host[:E].copy_(count[:E], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        if self.prune_wait_us is not None:
+            self.prune_wait_us.append((time.perf_counter() - t0) * 1e6)
+        g = max(1, int(self.prune_granule))
+        cap = max(1, -(-int(self._prune_host[:E].max()) // g)) * g
+        return cap if cap < Bk else None
 
     def _override_routing(self, t, m_idx, B, S, E, k):
         """Parity-test hook (never on the product path): replace the expert-choice selection of one layer by given token
@@ -854,26 +910,39 @@ class DiTEngine:
             g1, g2 = self.G[n + ".mlp.w1"], self.G[n + ".mlp.w2"]
             dh2 = self.empty(E, Bk, d)
             dgval = self.empty(E, Bk, dtype=F32)
-            hip.check(L.md_moe_combine_bwd(dbr3.data_ptr(), t.h2.data_ptr(), t.rowidx.data_ptr(), t.gval.data_ptr(),
-                                           dh2.data_ptr(), dgval.data_ptr(), E * Bk, d, st), "combine_bwd")
+            # pruned (t.cap): the same launches on the first t.cap rows of every expert's compact list.  Pad rows have gate value 0, so
+            # their dh2 -- and with it their dhpre, dxin and weight-gradient contributions -- is exactly 0; their dgval is never read.
+            rows = t.cap or Bk
+            if t.cap is None:
+                hip.check(L.md_moe_combine_bwd(dbr3.data_ptr(), t.h2.data_ptr(), t.rowidx.data_ptr(), t.gval.data_ptr(),
+                                               dh2.data_ptr(), dgval.data_ptr(), E * Bk, d, st), "combine_bwd")
+            else:
+                hip.check(L.md_moe_combine_bwd_compact(dbr3.data_ptr(), t.h2.data_ptr(), t.rowidx_c.data_ptr(), t.gval_c.data_ptr(),
+                                                       dh2.data_ptr(), dgval.data_ptr(), E, rows, Bk, d, st), "combine_bwd_compact")
             # dW2[e][f, d] += hact[e]^T dh2[e]
-            self.gemm_f32_acc(out_ptr=g2.data_ptr(), M=f, N=d, K=Bk, ldo=d, batch=E, sOut=f * d, A=t.hact.data_ptr(),
+            self.gemm_f32_acc(out_ptr=g2.data_ptr(), M=f, N=d, K=rows, ldo=d, batch=E, sOut=f * d, A=t.hact.data_ptr(),
                               B=dh2.data_ptr(), lda=f, ldb=d, sA=Bk * f, sB=Bk * d, a_kcontig=0, b_kcontig=0)
             # dhpre = (dh2 @ W2[e]^T) * gelu'(hpre)
             dhpre = self.empty(E, Bk, f)
-            self._gemm(A=dh2.data_ptr(), B=w2.data_ptr(), C=dhpre.data_ptr(), aux=t.hpre.data_ptr(), M=Bk, N=f, K=d, lda=d,
+            self._gemm(A=dh2.data_ptr(), B=w2.data_ptr(), C=dhpre.data_ptr(), aux=t.hpre.data_ptr(), M=rows, N=f, K=d, lda=d,
                        ldb=d, ldc=f, ldaux=f, sA=Bk * d, sB=f * d, sC=Bk * f, sAux=Bk * f, batch=E, ksplit=1, a_kcontig=1,
                        b_kcontig=1, mode=hip.EPI_DACT, act=hip.ACT_GELU_ERF, alpha=1.0, dact_cached=t.hpre_is_dact)
             # dW1[e][d, f] += xin[e]^T dhpre[e]
-            self.gemm_f32_acc(out_ptr=g1.data_ptr(), M=d, N=f, K=Bk, ldo=f, batch=E, sOut=d * f, A=t.xin.data_ptr(),
+            self.gemm_f32_acc(out_ptr=g1.data_ptr(), M=d, N=f, K=rows, ldo=f, batch=E, sOut=d * f, A=t.xin.data_ptr(),
                               B=dhpre.data_ptr(), lda=d, ldb=f, sA=Bk * d, sB=Bk * f, a_kcontig=0, b_kcontig=0)
             # dxin = dhpre @ W1[e]^T
             dxin = self.empty(E, Bk, d)
-            self._gemm(A=dhpre.data_ptr(), B=w1.data_ptr(), C=dxin.data_ptr(), M=Bk, N=d, K=f, lda=f, ldb=f, ldc=d, sA=Bk * f,
+            self._gemm(A=dhpre.data_ptr(), B=w1.data_ptr(), C=dxin.data_ptr(), M=rows, N=d, K=f, lda=f, ldb=f, ldc=d, sA=Bk * f,
                        sB=d * f, sC=Bk * d, batch=E, ksplit=1, a_kcontig=1, b_kcontig=1, mode=hip.EPI_STORE_BF16, act=0, alpha=1.0)
             dlog = self.empty(M, ldl)
-            hip.check(L.md_moe_dispatch_bwd(dxin.data_ptr(), t.slot.data_ptr(), dxm3.data_ptr(), t.probs.data_ptr(), ldl,
-                                            dgval.data_ptr(), dlog.data_ptr(), ldl, B, S, E, k, d, st), "dispatch_bwd")
+            if t.cap is None:
+                hip.check(L.md_moe_dispatch_bwd(dxin.data_ptr(), t.slot.data_ptr(), dxm3.data_ptr(), t.probs.data_ptr(), ldl,
+                                                dgval.data_ptr(), dlog.data_ptr(), ldl, B, S, E, k, d, st), "dispatch_bwd")
+            else:       # every token row is written: a dropped token gets dxm3 = 0 and dlog = 0
+                hip.check(L.md_moe_dispatch_bwd_abs(dxin.data_ptr(), t.slot_c.data_ptr(), dxm3.data_ptr(), t.probs.data_ptr(), ldl,
+                                                    dgval.data_ptr(), dlog.data_ptr(), ldl, B, S, E, Bk, d, st), "dispatch_bwd_abs")
+            if self.route_log is not None:
+                self.route_log += ["combine_bwd", "dispatch_bwd"] if t.cap is None else ["combine_bwd_compact", "dispatch_bwd_abs"]
             # gate: dWg[E, d] += dlog^T xm3 ; dxm3 += dlog @ Wg
             self.lin_wgrad(dlog, t.xm3, n + ".mlp.gate", M, E, d, lddy=ldl)
             self.lin_dgrad(dlog, n + ".mlp.gate", dxm3, M, E, d, lddy=ldl, mode=hip.EPI_RESIDUAL, res=dxm3)
@@ -1111,7 +1180,7 @@ class DiTEngine:
         grad_pass = self.use_arena and arena and record_tape
         self._record = record_tape or self.keep_last_tape
         if grad_pass:
-            self._tape_arena.begin((B, H, W, Lc, Dc, float(mask_ratio), ydt))
+            self._tape_arena.begin((B, H, W, Lc, Dc, float(mask_ratio), ydt, bool(self.prune_masked_experts)))
             self._arena = self._tape_arena
         ok = False
         try:
@@ -1264,26 +1333,36 @@ class DiTEngine:
         seg("adaln.b")
         mod_all = self._adaln_all(gc, B) if (self.batch_adaln and self._adaln is not None) else None
         tp.mixer = []
-        for bp in self.mixer:
-            seg(bp.name)
-            x, bt = self._block_fwd(bp, x, ym, B, T, Lc, gc, mod_all, kv=cond.kv[bp.name] if cond is not None else None)
-            if self._record:
-                tp.mixer.append(bt)
-        # ---- masking, dit.py:495-504
-        Wd = x.shape[1]
-        if mask_ratio > 0:
-            Tk = int(T * (1 - mask_ratio))
+        Tk = int(T * (1 - mask_ratio)) if mask_ratio > 0 else T
+
+        def get_mask():
             assert mask_noise is not None and mask_noise.dtype == F32 and mask_noise.shape == (B, T)
             tp.keep_rows = self.empty(B * Tk, dtype=I32)
             tp.ids_restore = self.empty(B, T, dtype=I32)
             tp.mask = self.empty(B, T, dtype=F32)
             hip.check(L.md_get_mask(mask_noise.contiguous().data_ptr(), B, T, Tk, tp.keep_rows.data_ptr(),
                                     tp.ids_restore.data_ptr(), tp.mask.data_ptr(), st), "get_mask")
+
+        # masked-expert pruning: the mask depends on the noise alone, so it is drawn before the last mixer block instead of behind it
+        prune = mask_ratio > 0 and self.prune_masked_experts and bool(self.mixer) and self.mixer[-1].moe
+        for bp in self.mixer:
+            seg(bp.name)
+            keep = None
+            if prune and bp is self.mixer[-1]:
+                get_mask()
+                keep = (tp.ids_restore, Tk)
+            x, bt = self._block_fwd(bp, x, ym, B, T, Lc, gc, mod_all, kv=cond.kv[bp.name] if cond is not None else None, keep=keep)
+            if self._record:
+                tp.mixer.append(bt)
+        # ---- masking, dit.py:495-504
+        Wd = x.shape[1]
+        if mask_ratio > 0:
+            if not prune:
+                get_mask()
             xk = self.empty(B * Tk, Wd)
             hip.check(L.md_gather_rows(x.data_ptr(), Wd, tp.keep_rows.data_ptr(), xk.data_ptr(), Wd, B * Tk, Wd, st), "gather")
             x = xk
         else:
-            Tk = T
             tp.keep_rows = tp.ids_restore = tp.mask = None
         tp.Tk = Tk
         # ---- mixer -> backbone projection (after masking), dit.py:506-508

@@ -210,6 +210,12 @@ _sig("md_moe_route", P, P, I64, I64, I64, I32, I32, P, P, P, P)
 _sig("md_moe_combine", P, P, P, P, P, I64, P, P, I64, I64, I32, I32, I64, P)
 _sig("md_moe_combine_bwd", P, P, P, P, P, P, I64, I64, P)
 _sig("md_moe_dispatch_bwd", P, P, P, P, I64, P, P, I64, I64, I64, I32, I32, I64, P)
+# masked-expert pruning of the last patch-mixer block: compact lists of the routed rows whose token survives the mask
+_sig("md_moe_compact_kept", P, P, P, I64, I64, I64, I32, I32, P, P, P, P, P, I64, P)
+_sig("md_moe_gather_compact", P, I64, P, P, I32, I64, I64, I64, P)
+_sig("md_moe_combine_abs", P, P, P, P, P, I64, P, P, I64, I64, I32, I64, I64, P)
+_sig("md_moe_combine_bwd_compact", P, P, P, P, P, P, I32, I64, I64, I64, P)
+_sig("md_moe_dispatch_bwd_abs", P, P, P, P, I64, P, P, I64, I64, I64, I32, I64, I64, P)
 _sig("md_edm_prepare", P, P, P, P, P, P, P, I64, I64, F32, F32, F32, P)
 _sig("md_edm_prepare_f16", P, P, P, P, P, P, P, P, I64, I64, F32, F32, F32, P)
 _sig("md_patchify", P, P, P, I64, I32, I32, I32, I32, P)
