@@ -682,6 +682,30 @@ int md_lora_grad_ws_floats(md_lora_item* items_host, int32_t n_items, int32_t ra
 int md_lora_grad(const float* g, const float* adapter, const md_lora_item* items, const md_lora_item* items_host, int32_t n_items,
                  int32_t rank, float scale, float grad_scale, float* d_adapter, float* ws, int64_t ws_floats, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------- dispersive loss */
+/* (Added under ABI 6: new symbols only.)  Batch-repulsion regulariser on one block's output (Wang & He 2025, "Diffuse and Disperse",
+ * the InfoNCE-l2 form; no reference counterpart).  Z [B, K] bf16 is the block output of a microbatch, one row per sample:
+ *   G = Z Z^T (fp32)     D_ij = max(0, G_ii + G_jj - 2 G_ij) / K (i != j), D_ii = 0     E_ij = exp(-D_ij / tau)     S = sum_ij E_ij
+ *   L = log(S / B^2)     p_ij = E_ij / S     W_aj = p_aj (j != a), W_aa = -sum_{j != a} p_aj     dL/dz_a = 4 / (tau K) sum_j W_aj z_j
+ * md_disperse_pairs reads the fp32 Gram G [B, ldg] (columns >= B are not read) and writes
+ *   W [B, ldw] bf16 = coef * W, ldw a multiple of 8, the pad columns [B, ldw) zero (the injection GEMM reads whole 16-byte chunks);
+ *   result[0 .. 3] fp64 = L, the mean off-diagonal D, the mean off-diagonal p * B^2 (1 = uniform, -> 0 = saturated: every pair so
+ *   far apart that only the diagonal is left in S), S;     *loss_accum += accum_weight * L, *dist_accum += accum_weight * mean D
+ *   (either may be NULL).
+ * W_aa is the negative off-diagonal row sum (never p_aa - rho_a, which cancels).  The squared distance is formed in fp64 from the fp32
+ * Gram, exp is fp32, S and the row sums are fp64 in two stages (per row, then over the rows by one workgroup) in an order that is a
+ * function of B alone: no atomics, nothing returns to the host, two calls on the same G give identical bits.  ws: fp64 workspace of at
+ * least md_disperse_ws_doubles(B) = 2 B entries, written before it is read.  1 <= B <= MD_DISPERSE_MAX_B (B = 1: L = 0, W = 0);
+ * tau > 0.  Three launches.
+ * md_disperse_gram_small: G [B, ldg] fp32 = Z Z^T for the batch sizes whose fp32 split-K slices md_gemm_bf16 / md_splitk_reduce do
+ * not take (B not a multiple of 8).  Plain and bounds-checked: one workgroup per output row, fp32 FMA over the contraction in a fixed
+ * order, rows >= B of Z are never read; columns >= B of G are not written.  K and ldz multiples of 8, Z 16-byte aligned. */
+#define MD_DISPERSE_MAX_B 4096
+int md_disperse_ws_doubles(int64_t B, int64_t* out);
+int md_disperse_pairs(const float* G, int64_t ldg, int64_t B, int64_t K, float tau, double coef, void* W, int64_t ldw, double* result,
+                      double* ws, int64_t ws_doubles, float* loss_accum, float* dist_accum, float accum_weight, hipStream_t stream);
+int md_disperse_gram_small(const void* Z, int64_t ldz, int64_t B, int64_t K, float* G, int64_t ldg, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

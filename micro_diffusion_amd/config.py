@@ -185,6 +185,32 @@ def loss_weighting_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
     return {"enabled": True, "channels": ch, "lr": lr}
 
 
+def disperse_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The dispersive-loss switches of the `misc` section, off unless the config sets them: misc.disperse_weight
+    (lambda; 0 / absent: off; the untuned starting value is 0.5), misc.disperse_tau (default 0.5) and misc.disperse_block (index of the
+    backbone block whose output is regularised; default depth // 4, checked against the model by the Trainer).
+    Returns {"enabled": bool, "weight": float, "tau": float, "block": int or None}; raises ValueError on values the kernels cannot honour
+    and on tau / block given without a positive weight."""
+    import math
+    misc = cfg.get("misc") or {}
+    w = misc.get("disperse_weight", 0.0)
+    w = 0.0 if w is None else w
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
+        raise ValueError(f"misc.disperse_weight must be a finite number >= 0, got {w!r}")
+    tau, blk = misc.get("disperse_tau"), misc.get("disperse_block")
+    if not w > 0:
+        for key, v in (("disperse_tau", tau), ("disperse_block", blk)):
+            if v is not None:
+                raise ValueError(f"misc.{key} needs misc.disperse_weight > 0")
+        return {"enabled": False, "weight": 0.0, "tau": 0.5, "block": None}
+    tau = 0.5 if tau is None else tau
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not math.isfinite(tau) or not tau > 0:
+        raise ValueError(f"misc.disperse_tau must be a finite number > 0, got {tau!r}")
+    if blk is not None and (isinstance(blk, bool) or not isinstance(blk, int) or blk < 0):
+        raise ValueError(f"misc.disperse_block must be a block index >= 0, got {blk!r}")
+    return {"enabled": True, "weight": float(w), "tau": float(tau), "block": blk}
+
+
 def lora_options(cfg: Dict[str, Any], world: Any = None) -> Dict[str, Any]:
     """The LoRA switches of the `misc` section, off unless the config sets them: misc.lora_rank (0 / absent: off; one of
     4, 8, 16, 32, 64), misc.lora_alpha (default: the rank), misc.lora_targets (regular expressions on parameter names; default: the five

@@ -173,6 +173,15 @@ class DiTEngine:
         self.prune_wait_us = None          # tests / profiling: list that receives the host time of every count readback, in microseconds
         self._prune_host = None            # pinned int32[16] the counts land in
         self.route_log = None              # tests: list that receives the name of every routing-family entry point a MoE block calls
+        # Dispersive loss (opt-in): None, or (k, weight, tau) armed for the training forwards that follow (the model's
+        # train_microbatch arms and disarms it): right behind backbone block k the Gram of its output over the microbatch and
+        # md_disperse_pairs run, and the backward adds weight * grad_scale * dL/dZ to dx in front of block k's backward (one GEMM).
+        # disperse_train = (grad_scale, loss_accum, dist_accum, accum_weight) of the microbatch.  None: the launches of an unarmed pass.
+        self.disperse = None
+        self.disperse_train = (1.0, None, None, 0.0)
+        self.disperse_log = None           # tests: list that receives ("gram" | "apply", "gemm" | "small", B, K) per product
+        self._disperse_on = False
+        self._disperse_result = None       # fp64 [4] result block of md_disperse_pairs (L, mean D, mean p B^2, S): one fixed buffer
         self.ws = torch.empty(128 << 20, device=self.dev, dtype=F32)  # 512 MiB split-K workspace
         # Fixed-address activation memory (opt-in: the caller must run forward -> backward strictly in turn, as the Trainer
         # does; two forwards in flight would share the tape arena).
@@ -1179,8 +1188,14 @@ class DiTEngine:
             Lc, Dc, ydt = y.shape[-2], y.shape[-1], str(y.dtype)
         grad_pass = self.use_arena and arena and record_tape
         self._record = record_tape or self.keep_last_tape
+        dsp = self.disperse
+        self._disperse_on = bool(record_tape and dsp is not None and dsp[1] > 0)
+        if self._disperse_on and not 0 <= dsp[0] < len(self.backbone):
+            raise ValueError(f"disperse: block {dsp[0]} is outside the backbone's {len(self.backbone)} blocks")
         if grad_pass:
-            self._tape_arena.begin((B, H, W, Lc, Dc, float(mask_ratio), ydt, bool(self.prune_masked_experts)))
+            # an armed pass allocates the Gram, W' and the result block behind block k: part of the shape key
+            self._tape_arena.begin((B, H, W, Lc, Dc, float(mask_ratio), ydt, bool(self.prune_masked_experts))
+                                   + ((("disperse", int(dsp[0])),) if self._disperse_on else ()))
             self._arena = self._tape_arena
         ok = False
         try:
@@ -1376,11 +1391,14 @@ class DiTEngine:
             self.lin_fwd(tp.xout_ln, "patch_mixer_map_xout.1", xb, B * Tk, D, Dm)
             x = xb
         tp.blocks = []
-        for bp in self.backbone:
+        tp.disperse = None
+        for i, bp in enumerate(self.backbone):
             seg(bp.name)
             x, bt = self._block_fwd(bp, x, y2, B, Tk, Lc, gc, mod_all, kv=cond.kv[bp.name] if cond is not None else None)
             if self._record:
                 tp.blocks.append(bt)
+            if self._disperse_on and i == self.disperse[0] and B > 1:       # B = 1: L = 0 and the gradient is 0 -- nothing to launch
+                tp.disperse = self._disperse_fwd(x, B, Tk * D)
         # ---- final layer, dit.py:513
         seg("final_layer")
         tp.xlast = x
@@ -1397,6 +1415,56 @@ class DiTEngine:
         if self.keep_last_tape:
             self.last_tape = tp
         return tp
+
+    # ------------------------------------------------------------------------------------------ dispersive loss
+    def disperse_gram(self, z, B, K, G, ldg):
+        """G [B, ldg] fp32 = Z Z^T for Z [B, K] bf16 (rows K apart).  B a multiple of 8: the GEMM family with its deterministic split-K
+        (workspace slices + md_splitk_reduce need whole 16-byte column chunks of an N = B wide slice).  Otherwise md_disperse_gram_small:
+        the family would only take such a B by reading rows of Z past the batch."""
+        if B % 8 == 0:
+            self.gemm_f32_acc(out_ptr=G.data_ptr(), M=B, N=B, K=K, ldo=ldg, accumulate=False, A=z.data_ptr(), B=z.data_ptr(), lda=K, ldb=K,
+                              a_kcontig=1, b_kcontig=1)
+            path = "gemm"
+        else:
+            hip.check(self.L.md_disperse_gram_small(z.data_ptr(), K, B, K, G.data_ptr(), ldg, self._st()), "md_disperse_gram_small")
+            path = "small"
+        if self.disperse_log is not None:
+            self.disperse_log.append(("gram", path, B, K))
+
+    def disperse_apply(self, W, ldw, z, dx, B, K):
+        """dx [B, K] += W' [B, ldw] Z [B, K]: a data-gradient-shaped launch (contraction over the batch, Z the K-strided operand) with the
+        residual epilogue reading and writing dx.  res == C is safe in every kernel of the family: an output element is read (as the
+        residual) and written by the one workgroup that owns its tile, the write depends on the read, and no other launch or workgroup
+        touches it.  The family takes every B: a contraction that ends inside a k-tile is zero-filled per row (K-strided operand: rows
+        >= B are never read) and per 16-byte chunk (W': the pad columns md_disperse_pairs writes as zero)."""
+        self._gemm(A=W.data_ptr(), B=z.data_ptr(), C=dx.data_ptr(), res=dx.data_ptr(), M=B, N=K, K=B, lda=ldw, ldb=K, ldc=K, ldr=K,
+                   batch=1, ksplit=1, a_kcontig=1, b_kcontig=0, mode=hip.EPI_RESIDUAL, act=0, alpha=1.0)
+        if self.disperse_log is not None:
+            self.disperse_log.append(("apply", "gemm", B, K))
+
+    def disperse_pairs(self, G, ldg, B, K, tau, coef, W, ldw, result, loss_accum=None, dist_accum=None, accum_weight=0.0):
+        ws = self.empty(2 * B, dtype=torch.float64)
+        hip.check(self.L.md_disperse_pairs(G.data_ptr(), ldg, B, K, tau, coef, W.data_ptr(), ldw, result.data_ptr(), ws.data_ptr(), 2 * B,
+                                           _p(loss_accum), _p(dist_accum), accum_weight, self._st()), "md_disperse_pairs")
+
+    def _disperse_fwd(self, x, B, K):
+        """Behind backbone block k: Gram of its output x [B * Tk, D] seen as Z [B, K], then md_disperse_pairs.  Z is not copied: x is the
+        next block's saved input (or tp.xlast) in the forward arena.  Returns what the backward needs."""
+        k, lam, tau = self.disperse
+        gscale, loss_accum, dist_accum, aw = self.disperse_train
+        if B > hip.DISPERSE_MAX_B:
+            raise ValueError(f"disperse: microbatch {B} exceeds {hip.DISPERSE_MAX_B} samples")
+        ld = (B + 7) // 8 * 8
+        d = Tape()
+        d.k, d.z, d.B, d.K, d.ldw, d.tau = k, x, B, K, ld, tau
+        G = self.empty(B, ld, dtype=F32)
+        d.W = self.empty(B, ld)
+        if self._disperse_result is None:
+            self._disperse_result = torch.zeros(4, device=self.dev, dtype=torch.float64)
+        d.result = self._disperse_result
+        self.disperse_gram(x, B, K, G, ld)
+        self.disperse_pairs(G, ld, B, K, tau, 4.0 * lam * gscale / (tau * K), d.W, ld, d.result, loss_accum, dist_accum, aw)
+        return d
 
     def sample_image(self, tp: Tape) -> torch.Tensor:
         """unmask_tokens + unpatchify (utils.py:417-426, dit.py:566-575) -> f32 [B, C, H, W]."""
@@ -1467,7 +1535,10 @@ class DiTEngine:
         self._adaln_bwd("final_layer.adaLN_modulation.1", dfm, B, 2 * D, gc, dgc)
         seg("final_layer")
         # ---- backbone
-        for bp, bt in zip(reversed(self.backbone), reversed(tp.blocks)):
+        dsp = getattr(tp, "disperse", None)
+        for i, bp, bt in zip(reversed(range(len(self.backbone))), reversed(self.backbone), reversed(tp.blocks)):
+            if dsp is not None and i == dsp.k:
+                self.disperse_apply(dsp.W, dsp.ldw, dsp.z, dx, dsp.B, dsp.K)       # dx is dL/d(output of block k) here
             self._block_bwd_scoped(bp, bt, dx, tp.y2, dy2_f32, B, Tk, Lc, gc, dgc, grp_b, kv_b)
             seg(bp.name)
         if kv_b is not None:

@@ -284,6 +284,11 @@ _sig("md_ema_power_update_ranges", P, P, P, I32, P, P, I32, P, P)
 _sig("md_lora_merge", P, P, P, P, I32, I32, F32, P, I32, P)
 _sig("md_lora_grad_ws_floats", P, I32, I32, POINTER(c_int64))
 _sig("md_lora_grad", P, P, P, P, I32, I32, F32, F32, P, P, I64, P)
+# dispersive loss (disperse.py): the pairwise stage between the Gram and the injection GEMM, and the bounds-checked Gram
+_sig("md_disperse_ws_doubles", I64, POINTER(c_int64))
+_sig("md_disperse_pairs", P, I64, I64, I64, F32, F64, P, I64, P, P, I64, P, P, F32, P)
+_sig("md_disperse_gram_small", P, I64, I64, I64, P, I64, P)
+DISPERSE_MAX_B = 4096    # MD_DISPERSE_MAX_B
 LORA_RANKS = (4, 8, 16, 32, 64)
 EMA_MAX_PROFILES = 4     # MD_EMA_MAX_PROFILES
 ADAMW_MAX_RANGES = 64    # MD_ADAMW_MAX_RANGES

@@ -82,6 +82,13 @@ class LatentDiffusion(nn.Module):
         # step then runs md_logvar_fwd -> md_edm_loss_train_weighted -> md_logvar_bwd.  None: the launches of today.  Evaluation and
         # sampling never read it.
         self.loss_weighting = None
+        # Dispersive loss (opt-in): a disperse.DisperseLoss; the Trainer's microbatch step then arms the engine, which
+        # adds weight * L_disp(output of one backbone block) to the objective (Gram, md_disperse_pairs, one injection GEMM in the
+        # backward).  None or weight 0: the launches of today.  Evaluation and sampling never read it.
+        # disperse_accum: f32 [2] the Trainer hands in per step; += accum_weight * (L, mean off-diagonal D) per microbatch.
+        self.disperse = None
+        self.disperse_accum = None
+        self._disperse_result = None
         assert self.train_mask_ratio >= 0, "Masking ratio must be non-negative!"
         self.randn_like = torch.randn_like
         self.latent_scale = self.vae.config.scaling_factor
@@ -177,6 +184,10 @@ class LatentDiffusion(nn.Module):
         """model.py:181-210 on the HIP engine.  `_noise=(rnd_normal, eps, mask_noise)` injects the three random
         draws (parity tests); otherwise they are drawn here in the reference's order.  `_y_rowscale` [B] f32: per-sample
         factor on the caption rows (the caption-drop mask)."""
+        if self.disperse is not None and self.disperse.enabled and torch.is_grad_enabled() and next(self.dit.parameters()).requires_grad:
+            raise RuntimeError("the dispersive loss is armed (LatentDiffusion.disperse): its gradient exists only on the "
+                               "Trainer's microbatch path (train_microbatch); the autograd surface would train the network on the "
+                               "unregularised loss.  Disarm it or run under torch.no_grad()")
         x, y, rnd, eps, mnoise = self._prep(x, y, mask_ratio, _noise)
         dit = self.dit
         need_grad = torch.is_grad_enabled() and dit._plist[0].requires_grad
@@ -200,8 +211,19 @@ class LatentDiffusion(nn.Module):
         mask_ratio = self.train_mask_ratio if self.training else self.eval_mask_ratio
         x, y, rnd, eps, mnoise = self._prep(latents, conditioning, mask_ratio, _noise)
         dit = self.dit
-        loss, tape, dtb = _edm_forward(self, None, x, y, rnd, eps, mnoise, float(mask_ratio), drop,
-                                       train=(float(grad_scale), loss_accum, float(accum_weight)))
+        dl, eng = self.disperse, dit._engine
+        if dl is not None and dl.enabled and dit.training:
+            acc = self.disperse_accum
+            eng.disperse = (dl.resolve_block(len(eng.backbone)), dl.weight, dl.tau)
+            eng.disperse_train = (float(grad_scale), None if acc is None else acc[0:1], None if acc is None else acc[1:2],
+                                  float(accum_weight))
+        try:
+            loss, tape, dtb = _edm_forward(self, None, x, y, rnd, eps, mnoise, float(mask_ratio), drop,
+                                           train=(float(grad_scale), loss_accum, float(accum_weight)))
+        finally:
+            eng.disperse = None
+        if getattr(tape, "disperse", None) is not None:
+            self._disperse_result = tape.disperse.result
         dit.attach_grads()
         dit._engine.backward(tape, dtb, on_segment=getattr(dit, "_on_segment", None))
         return loss

@@ -28,7 +28,10 @@ configs/*.yaml), re-designed for one process per GPU with RCCL over xGMI:
     synthesises the average for any EMA length afterwards (Karras et al. 2024, section 3);
   * learned loss weighting (opt-in): `Trainer(loss_weighting=LossWeighting())` trains u(sigma) next to the network (loss_weighting.py,
     Karras et al. 2024, section 2.2): two more tiny launches per microbatch, one fp32 all-reduce of its C gradient values per step and
-    one C-element AdamW launch behind the main optimiser pass.
+    one C-element AdamW launch behind the main optimiser pass;
+  * dispersive loss (opt-in): `Trainer(disperse=DisperseLoss())` adds a batch-repulsion term on one backbone block's output to every
+    microbatch's objective (disperse.py, Wang & He 2025): a Gram, md_disperse_pairs and one injection GEMM per microbatch, no
+    parameters, no collective on the step path.
 """
 from __future__ import annotations
 
@@ -47,6 +50,7 @@ import torch.distributed as dist
 from . import hip
 from . import diagnostics as mddiag
 from . import posthoc_ema
+from .disperse import DisperseLoss
 from .loss_weighting import LossWeighting
 
 
@@ -885,8 +889,11 @@ class Trainer:
                  microbatch_size: int = 256, process_group=None, log: Optional[Callable[[dict], None]] = None,
                  exchange: str = "auto", single_rank_exchange: bool = False, dp_mode: str = "auto", transport: str = "auto",
                  monitor_interval: int = 0, diagnostics_interval: int = 0, loss_by_sigma_bins: int = 0, moe_routing: bool = False,
-                 loss_weighting: Optional[LossWeighting] = None):
-        """loss_weighting (None: off -- no launch, no buffer, no collective): a LossWeighting armed as model.loss_weighting.  Its C
+                 loss_weighting: Optional[LossWeighting] = None, disperse: Optional[DisperseLoss] = None):
+        """disperse (None or weight 0: off -- no launch, no buffer): a DisperseLoss armed as model.disperse; every microbatch then adds
+        weight * L_disp(output of one backbone block) to its objective.  train_step's return value and the logged `loss`
+        stay the raw EDM loss; disperse_stats() reports the term, diagnostics()["disperse"] the last microbatch's result block.
+        loss_weighting (None: off -- no launch, no buffer, no collective): a LossWeighting armed as model.loss_weighting.  Its C
         gradient values are all-reduced (fp32 sum) after the main exchange in every exchange mode, its AdamW launch runs behind the
         main optimiser pass at `loss_weighting.lr` (default: the optimiser's lr) times the schedule factor, outside the clipped norm,
         under the optimiser's step guard when that is on; weighted_objective() is the rank-mean objective of the last step.
@@ -948,6 +955,11 @@ class Trainer:
         self.loss_weighting = loss_weighting
         self._objective = None               # with the loss weighting: rank-mean weighted objective of the last step (device scalar)
         model.loss_weighting = loss_weighting      # unconditionally: a model armed by an earlier Trainer must not stay armed unstepped
+        if disperse is not None:
+            disperse.resolve_block(len(model.dit.engine.backbone))      # raises on a block outside the backbone
+        self.disperse = disperse if (disperse is not None and disperse.enabled) else None     # weight 0 is off
+        model.disperse = self.disperse             # unconditionally, as above
+        model.disperse_accum = self._disperse_acc = None
         self.log = log
         self._win: List[tuple] = []
         self.measure_comm = False          # bench.py: event pairs around GradSync.finish() (exposed exchange time)
@@ -969,6 +981,9 @@ class Trainer:
         if lw is not None:                   # a fresh scalar per step, like `total`: the step's rank-mean weighted objective
             lw.objective_accum = self._objective = torch.empty(1, device=total.device)
             hip.check(hip.lib().md_fill_zero(self._objective.data_ptr(), 4, torch.cuda.current_stream().cuda_stream), "md_fill_zero")
+        if self.disperse is not None:        # a fresh pair per step: the step's (L_disp, mean off-diagonal D), microbatches weighted like the loss
+            model.disperse_accum = self._disperse_acc = torch.empty(2, device=total.device)
+            hip.check(hip.lib().md_fill_zero(self._disperse_acc.data_ptr(), 8, torch.cuda.current_stream().cuda_stream), "md_fill_zero")
         if (self._route_stats is not None and self.diagnostics_interval > 0
                 and (self.batches_seen + 1) % self.diagnostics_interval == 0):
             self._route_stats.zero()
@@ -1028,6 +1043,21 @@ class Trainer:
         """The rank-mean weighted objective (1 / B) sum_b (L_b e^{-u_b} + u_b) of the last step (device scalar; None before the first
         step or without the loss weighting).  train_step's return value stays the raw loss."""
         return self._objective.reshape(()) if self.loss_weighting is not None and self._objective is not None else None
+
+    # ------------------------------------------------------------------ dispersive loss
+    def disperse_stats(self) -> Optional[dict]:
+        """{"disperse_loss": mean of L_disp over the last step's microbatches (each weighted by its share of the rank batch, like the
+        loss), "disperse_mean_dist": the same mean of the mean off-diagonal D}; None without the feature or before the first step.
+        Synchronises; with more than one rank a collective (every rank calls it): the ranks' pairs are gathered and added in rank
+        order, then divided by the world size -- the same numbers on every rank."""
+        if self.disperse is None or self._disperse_acc is None:
+            return None
+        vals = self._disperse_acc.double()
+        if self.world > 1:
+            _, sums = mddiag.gather_rank_diagnostics(torch.empty(0, dtype=torch.int64, device=vals.device), vals, self.sync.pg)
+            vals = sums / self.world
+        vals = vals.tolist()
+        return {"disperse_loss": vals[0], "disperse_mean_dist": vals[1]}
 
     # ------------------------------------------------------------------ per-tensor statistics (optimizer monitor)
     def _stats_names(self) -> List[str]:
@@ -1150,6 +1180,11 @@ class Trainer:
                     wk.wait()
                 obj = obj / self.world
             out["loss_weighting"] = {"ln_sigma": pts, "u": lw.u_at(pts), "objective": None if obj is None else float(obj)}
+        res = getattr(model, "_disperse_result", None)
+        if self.disperse is not None and res is not None:
+            # the result block of this rank's last microbatch: L, mean off-diagonal D, mean off-diagonal p B^2 (1 = uniform, -> 0 = saturated)
+            r = res.tolist()
+            out["disperse"] = {"loss": r[0], "mean_dist": r[1], "mean_offdiag_p_b2": r[2]}
         return out
 
     def exposed_comm_ms(self, last: int = 0) -> Optional[float]:

@@ -19,6 +19,7 @@ sys.path.insert(0, ROOT)
 
 from micro_diffusion_amd import config as mdcfg  # noqa: E402
 from micro_diffusion_amd import loss_weighting as mdlw  # noqa: E402
+from micro_diffusion_amd.disperse import DisperseLoss  # noqa: E402
 from micro_diffusion_amd.lora import LoRA, LoRAAdamW  # noqa: E402
 from micro_diffusion_amd.model import text_encoder_embedding_format  # noqa: E402
 from micro_diffusion_amd.trainer import FusedAdamW, LRSchedule, Trainer, parse_batches  # noqa: E402
@@ -27,6 +28,7 @@ from micro_diffusion_amd.trainer import FusedAdamW, LRSchedule, Trainer, parse_b
 def train(cfg: dict):
     posthoc = mdcfg.posthoc_ema_options(cfg)     #  checked before anything is allocated: raises on values it cannot honour
     lwopt = mdcfg.loss_weighting_options(cfg)    #  likewise: channels / lr checked here
+    dsp = mdcfg.disperse_options(cfg)            #  likewise: weight / tau / block checked here
     lora = mdcfg.lora_options(cfg)               #  likewise: rank / targets checked, unsupported combinations refused
     if lora["enabled"] and not cfg["trainer"].get("load_path"):
         raise ValueError("misc.lora_rank needs trainer.load_path: the adapter is trained on a frozen, trained base")
@@ -126,7 +128,8 @@ def train(cfg: dict):
     diag_kw = {k: v for k, v in mdcfg.diagnostics_options(cfg).items() if v}
     diag_every = diag_kw.get("diagnostics_interval", 0)
     trainer = Trainer(model, opt, sched, clip_norm=clip, microbatch_size=int(cfg["trainer"]["device_train_microbatch_size"]),
-                      **monitor_kw, **diag_kw, **(dict(loss_weighting=lw) if lw is not None else {}))
+                      **monitor_kw, **diag_kw, **(dict(loss_weighting=lw) if lw is not None else {}),
+                      **(dict(disperse=DisperseLoss(dsp["weight"], dsp["tau"], dsp["block"])) if dsp["enabled"] else {}))
     save_every = parse_batches(cfg["trainer"].get("save_interval", "0ba"))
     folder = cfg["trainer"].get("save_folder")
     log_every = int(cfg.get("misc", {}).get("log_interval", 10))
@@ -194,11 +197,12 @@ def train(cfg: dict):
                 raise RuntimeError(f"{skipped - skipped_logged} optimizer steps since batch {max(step + 1 - log_every, start)} had a "
                                    f"non-finite gradient norm and were skipped (misc.max_skipped_steps = {max_skipped})")
             skipped_logged = skipped
+        dstats = trainer.disperse_stats() if (step + 1) % log_every == 0 else None     # every rank: a collective under data parallelism
         if rank == 0 and (step + 1) % log_every == 0:
             torch.cuda.synchronize()
             dt, t_last = time.time() - t_last, time.time()
             print(json.dumps(log_line(step + 1, loss, opt.lr * sched.factor(step), ds["train_batch_size"] * log_every / dt,
-                                      skipped_logged if skip_nonfinite else None, trainer)), flush=True)
+                                      skipped_logged if skip_nonfinite else None, trainer, dstats)), flush=True)
         snap_now = bool(folder and snap_every and (step + 1) % snap_every == 0)
         if snap_now or (folder and save_every and (step + 1) % save_every == 0):
             trainer.consolidate()                                  # a collective under the sharded optimiser: every rank calls it
@@ -220,15 +224,18 @@ def train(cfg: dict):
     return trainer
 
 
-def log_line(batch: int, loss, lr: float, samples_per_sec: float, skipped=None, trainer=None) -> dict:
-    """The periodic log line.  `loss` is the raw EDM loss with or without the learned loss weighting (the curves stay comparable);
-    `weighted_loss`, the objective the weighting minimises, appears only when the feature is on."""
+def log_line(batch: int, loss, lr: float, samples_per_sec: float, skipped=None, trainer=None, disperse=None) -> dict:
+    """The periodic log line.  `loss` is the raw EDM loss with or without the learned loss weighting or the dispersive loss (the curves
+    stay comparable); `weighted_loss`, the objective the weighting minimises, appears only when that feature is on, and so do
+    `disperse_loss` / `disperse_mean_dist` (Trainer.disperse_stats()) for the dispersive loss."""
     line = {"batch": batch, "loss": float(loss), "lr": lr, "samples_per_sec": samples_per_sec}
     if skipped is not None:
         line["skipped_steps"] = skipped
     obj = trainer.weighted_objective() if trainer is not None and getattr(trainer, "loss_weighting", None) is not None else None
     if obj is not None:
         line["weighted_loss"] = float(obj)
+    if disperse is not None:
+        line.update(disperse)
     return line
 
 
