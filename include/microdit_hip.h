@@ -706,6 +706,30 @@ int md_disperse_pairs(const float* G, int64_t ldg, int64_t B, int64_t K, float t
                       double* ws, int64_t ws_doubles, float* loss_accum, float* dist_accum, float accum_weight, hipStream_t stream);
 int md_disperse_gram_small(const void* Z, int64_t ldz, int64_t B, int64_t K, float* G, int64_t ldg, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------- input gradients */
+/* (Added under ABI 6: new symbols only.)  The last step of the backward to the three network inputs (no reference source: the
+ * reference gets them from autograd).
+ * md_patch_embed_dgrad: the transpose of md_patchify(scale) followed by the x_embedder.proj GEMM (dit.py:312-314,479), in one launch:
+ *   dpatch[row, j] = sum_d dtok[row, d] * w[d, j]                                     (fp32 accumulation, never rounded to bf16)
+ *   dx[b, c, ti*p + ph, tj*p + pw] = scale[b] * dpatch[b*T + ti*(W/p) + tj, c*p*p + ph*p + pw]
+ * dtok bf16 [B*T, D] with row pitch ld_dtok >= D, w the bf16 weight [D, patch_vec = C*p*p], scale f32 [B] or NULL (= 1), dx f32
+ * [B, C, H, W], written, not accumulated.  patch_vec a multiple of 16 with 16-byte aligned dtok / w and ld_dtok % 8 == 0 runs on
+ * v_mfma_f32_16x16x32_bf16 (w staged in LDS, transposed, 256 rows of it at a time); everything else on a plain fp32 FMA kernel.
+ * *path (host pointer, may be NULL) receives 1 for the MFMA kernel, 0 for the plain one.  No atomics; two calls give the same bits.
+ * MD_BAD_ARG, nothing launched: a null dtok / w / dx, a non-positive size, H % p or W % p non-zero, D % 8 != 0, ld_dtok < D, or
+ * patch_vec > MD_PATCH_EMBED_DGRAD_MAX_PV.
+ * md_timestep_embed_bwd: dt[b] = sum_k f_k * (cos(t_b f_k) * dsin[b, k] - sin(t_b f_k) * dcos[b, k]) from dout bf16 [B, dim] in
+ * md_timestep_embed's [cos | sin] layout (utils.py:266-281), f_k from the device function the forward uses.  One wave per sample,
+ * fixed-order fp32 sum.
+ * md_cast_rows_from_bf16: y[r, :] = float(x_bf16[r, :]) * rowscale[r / rows_per_sample] (rowscale NULL = 1), y f16 (y_dtype 0) or
+ * f32 (1): the transpose of md_cast_rows_bf16 (the caption cast + drop, model.py:132-139); any C. */
+#define MD_PATCH_EMBED_DGRAD_MAX_PV 64
+int md_patch_embed_dgrad(const void* dtok, int64_t ld_dtok, const void* w, const float* scale, float* dx, int64_t B, int32_t C, int32_t H,
+                         int32_t W, int32_t p, int32_t D, int32_t* path, hipStream_t stream);
+int md_timestep_embed_bwd(const float* t, const void* dout, float* dt, int64_t B, int32_t dim, hipStream_t stream);
+int md_cast_rows_from_bf16(const void* x, void* y, int32_t y_dtype, int64_t rows, int64_t C, const float* rowscale,
+                           int64_t rows_per_sample, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

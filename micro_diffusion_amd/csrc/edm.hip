@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void timestep_embed_kernel(const float* t, bf1
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / half;
         const int k = (int)(i % half);
-        const float f = expf(-9.210340371976184f * (float)k / (float)half);  // ln(10000)
+        const float f = timestep_freq(k, half);
         const float a = t[b] * f;
         out[b * dim + k] = f2bf(cosf(a));
         out[b * dim + half + k] = f2bf(sinf(a));

@@ -167,6 +167,9 @@ __device__ __forceinline__ void gelu_dgelu_erf_2(f32x2 x, f32x2& g, f32x2& d) {
     g = x * cdf;
     d = cdf + (x * 0.3989422804014327f) * e;
 }
+// Frequency k of the sinusoidal timestep features (utils.py:266-281): 10000^(-k / half).  md_timestep_embed and md_timestep_embed_bwd
+// both take it from here, so the backward differentiates exactly the angles the forward formed.
+__device__ __forceinline__ float timestep_freq(int k, int half) { return expf(-9.210340371976184f * (float)k / (float)half); }  // ln(10000)
 __device__ __forceinline__ float silu_f(float x) { return x * fast_rcp(1.f + __expf(-x)); }
 __device__ __forceinline__ float dsilu_f(float x) {
     float s = fast_rcp(1.f + __expf(-x));

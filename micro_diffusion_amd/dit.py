@@ -280,8 +280,9 @@ class DiT(nn.Module):
 
     # ------------------------------------------------------------------------------------------ forward
     @staticmethod
-    def _caption_input(y):
-        yin = y.detach()
+    def _caption_input(y, keep_graph: bool = False):
+        """y as the engine reads it: f16 | f32, contiguous.  keep_graph: the conversions stay differentiable torch ops (y requires grad)."""
+        yin = y if keep_graph else y.detach()
         if yin.dtype not in (torch.float16, torch.float32):
             yin = yin.float()
         return yin.contiguous()
@@ -296,7 +297,11 @@ class DiT(nn.Module):
         return self._engine.encode_condition(self._caption_input(y))
 
     def forward_without_cfg(self, x, t, y, mask_ratio: float = 0, mask_noise: Optional[torch.Tensor] = None, cond=None, **kwargs):
-        """cond: an encode_condition(y) result for these captions (y is then not read)."""
+        """cond: an encode_condition(y) result for these captions (y is then not read).
+        Gradients: with grad mode on, the output carries a graph when any parameter or any of x, t, y requires grad.
+        x.grad / t.grad / y.grad come back in each input's own shape and dtype (a one-element t gets the batch sum, an f16 y an f16
+        gradient).  With every parameter frozen the backward is the engine's dgrad-only one: no p.grad is attached, the flat gradient
+        buffer is not touched and no weight-gradient kernel runs.  cond stays inference-only."""
         self._ensure_flat()
         self.refresh_shadow()
         self.h = x.shape[-2] // self.patch_size
@@ -304,15 +309,21 @@ class DiT(nn.Module):
         B = x.shape[0]
         if mask_ratio > 0 and mask_noise is None:
             mask_noise = torch.rand(B, self.h * self.w, device=x.device)     # same draw as utils.py:390
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        xin = x.detach().to(torch.float32).contiguous()
-        yin = self._caption_input(y) if y is not None else None
+        grad_on = torch.is_grad_enabled()
+        gx, gt, gy = (grad_on and v is not None and v.requires_grad for v in (x, t, y))
+        need_grad = grad_on and (gx or gt or gy or any(p.requires_grad for p in self.parameters()))
+        xin = (x if gx else x.detach()).to(torch.float32).contiguous()
+        yin = self._caption_input(y, gy) if y is not None else None
+        tin = t.detach()
+        if gt:      # one value per sample through differentiable torch ops: a one-element t gets the batch sum from expand's backward
+            tin = t.to(torch.float32).reshape(-1).expand(B).contiguous()
         if need_grad:
             if cond is not None:
-                raise RuntimeError("cond is inference-only: call under torch.no_grad() (or with frozen parameters)")
-            sample, mask = _DiTFunction.apply(self, self._grad_anchor, xin, t.detach(), yin, float(mask_ratio), mask_noise)
+                raise RuntimeError("cond is inference-only: call under torch.no_grad() (or with frozen parameters and inputs that "
+                                   "do not require grad)")
+            sample, mask = _DiTFunction.apply(self, self._grad_anchor, xin, tin, yin, float(mask_ratio), mask_noise)
         else:
-            tape = self._engine.forward(xin, t.detach(), yin, mask_ratio=float(mask_ratio), mask_noise=mask_noise, cond=cond)
+            tape = self._engine.forward(xin, tin, yin, mask_ratio=float(mask_ratio), mask_noise=mask_noise, cond=cond)
             sample, mask = self._engine.sample_image(tape), tape.mask
         return {"sample": sample, "mask": mask}
 
@@ -340,13 +351,15 @@ class DiT(nn.Module):
 
 class _DiTFunction(torch.autograd.Function):
     """The whole network as one autograd node.  Parameter gradients are accumulated by the engine directly into
-    the flat fp32 gradient buffer (every parameter's .grad is a view of it), not returned through autograd."""
+    the flat fp32 gradient buffer (every parameter's .grad is a view of it), not returned through autograd; the gradients of
+    x, t and y are returned through it when they are asked for (ctx.needs_input_grad)."""
 
     @staticmethod
     def forward(ctx, module: DiT, anchor, x, t, y, mask_ratio, mask_noise):
         eng = module._engine
         tape = eng.forward(x, t, y, mask_ratio=mask_ratio, mask_noise=mask_noise, record_tape=True)
         ctx.module, ctx.tape = module, tape
+        ctx.t_shape, ctx.y_shape = t.shape, (y.shape if y is not None else None)
         img = eng.sample_image(tape)
         mask = tape.mask
         if mask is not None:
@@ -358,16 +371,21 @@ class _DiTFunction(torch.autograd.Function):
         module, tape = ctx.module, ctx.tape
         eng = module._engine
         cfg = module.config
-        module.attach_grads()
+        pgrad = any(p.requires_grad for p in module._plist)
+        if pgrad:
+            module.attach_grads()
         # d(sample)/d(token output): gather the image grad into kept-token rows, (ph, pw, c) order
         B, C, H, W, p = tape.B, cfg.in_channels, tape.H, tape.W, cfg.patch_size
         g = H // p
         dtok_all = dimg.contiguous().view(B, C, g, p, g, p).permute(0, 2, 4, 3, 5, 1).reshape(B * g * g, p * p * C)
         if tape.keep_rows is not None:
             dtok_all = dtok_all[tape.keep_rows.long()]
-        eng.backward(tape, dtok_all.to(torch.bfloat16).contiguous())
+        want = [k for k, i in (("x", 2), ("t", 3), ("y", 4)) if ctx.needs_input_grad[i]]
+        g = eng.backward(tape, dtok_all.to(torch.bfloat16).contiguous(), input_grads=want, param_grads=pgrad)
         ctx.tape = None
-        return None, torch.zeros_like(module._grad_anchor), None, None, None, None, None
+        dt = None if g.dt is None else g.dt.view(ctx.t_shape)
+        dy = None if g.dy is None else g.dy.view(ctx.y_shape)
+        return None, torch.zeros_like(module._grad_anchor), g.dx, dt, dy, None, None
 
 
 # ---------------------------------------------------------------------------------------------- model zoo

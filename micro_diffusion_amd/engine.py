@@ -125,7 +125,20 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+class InputGrads:
+    """What DiTEngine.backward returns: the gradients of the network inputs that were asked for (the others None).
+      dx f32 [B, C, H, W]; dt f32 [B]; dy [B*Lc, Dc] in the dtype of the forward's y (f32 | f16)"""
+    __slots__ = ("dx", "dt", "dy")
+
+    def __init__(self):
+        self.dx = self.dt = self.dy = None
+
+
 class DiTEngine:
+    # False inside a dgrad-only backward (backward(param_grads=False), DESIGN.md 4.17): the helpers that write self.G -- lin_wgrad,
+    # _param_acc, _param_colsum, ln_bwd's weight reduction -- launch nothing; every data-gradient launch is the one of a full backward
+    _param_grads = True
+
     def __init__(self, cfg: DiTConfig, params: Dict[str, torch.Tensor], shadows: Dict[str, torch.Tensor],
                  grads: Dict[str, torch.Tensor], buffers: Dict[str, torch.Tensor]):
         """params: fp32 masters; shadows: bf16 copies (same names); grads: fp32 accumulators; buffers: pos_embed,
@@ -211,6 +224,7 @@ class DiTEngine:
         self.wgrad_bf16 = None
         self.fuse_swiglu_bwd = os.environ.get("MD_FUSE_SWIGLU_BWD", "1") != "0"   # A/B: 0 = data gradient + md_swiglu_bwd as two launches
         self.weights_version = 0    # set by the owning DiT whenever it rewrites the bf16 shadow: a Conditioning is valid for one version
+        self.input_grad_log = None  # tests: list that receives (entry point, kernel path or None) of every input-gradient launch
         self.cu_limit_fn = None     # data parallelism: callable() -> CUs the persistent GEMM may occupy right now (0 = all): the
         #                             Trainer leaves the CUs of RCCL's channels free while a collective is in flight
 
@@ -487,6 +501,8 @@ class DiTEngine:
         grad b[N] += column sums of dy.
         defer: with a weight-gradient group open (_wgrad_begin), only record the problem -- the whole group runs as ONE grouped
         launch at _wgrad_flush().  The caller guarantees that dy and x are not modified before the flush."""
+        if not self._param_grads:
+            return
         gb = self.G.get(wname + ".bias")
         if gb is not None:
             src = dy if bias_from is None else bias_from
@@ -500,6 +516,15 @@ class DiTEngine:
         self.gemm_f32_acc(out_ptr=self.G[wname + ".weight"].data_ptr(), M=N, N=K, K=M, ldo=K,
                           A=dy.data_ptr() + 2 * dyoff, B=x.data_ptr() + 2 * xoff, lda=lddy or N, ldb=ldx or K,
                           a_kcontig=0, b_kcontig=0)
+
+    def _param_acc(self, **kw):
+        """gemm_f32_acc into a tensor of self.G (the weight gradients that are not a Linear's: experts, patch embedding)."""
+        if self._param_grads:
+            self.gemm_f32_acc(**kw)
+
+    def _param_colsum(self, *a):
+        if self._param_grads:
+            self._colsum(*a)
 
     def _wgrad_begin(self):
         self._wgroup = [] if self.group_wgrad else None
@@ -596,6 +621,8 @@ class DiTEngine:
         finished from."""
         rps = a.rows_per_sample if a.rows_per_sample > 0 else a.rows
         rpb = self._rows_per_block(a.rows, rps, 1024)
+        if not self._param_grads:
+            wname = None                   # no weight gradient: a plain norm needs no per-sample sums either (dscale stays None)
         is_out = 1 if dscale is not None else 0
         if dscale is None and wname is not None:
             scratch = self.zeros(a.rows // rps, a.C)
@@ -929,16 +956,16 @@ class DiTEngine:
                 hip.check(L.md_moe_combine_bwd_compact(dbr3.data_ptr(), t.h2.data_ptr(), t.rowidx_c.data_ptr(), t.gval_c.data_ptr(),
                                                        dh2.data_ptr(), dgval.data_ptr(), E, rows, Bk, d, st), "combine_bwd_compact")
             # dW2[e][f, d] += hact[e]^T dh2[e]
-            self.gemm_f32_acc(out_ptr=g2.data_ptr(), M=f, N=d, K=rows, ldo=d, batch=E, sOut=f * d, A=t.hact.data_ptr(),
-                              B=dh2.data_ptr(), lda=f, ldb=d, sA=Bk * f, sB=Bk * d, a_kcontig=0, b_kcontig=0)
+            self._param_acc(out_ptr=g2.data_ptr(), M=f, N=d, K=rows, ldo=d, batch=E, sOut=f * d, A=t.hact.data_ptr(),
+                            B=dh2.data_ptr(), lda=f, ldb=d, sA=Bk * f, sB=Bk * d, a_kcontig=0, b_kcontig=0)
             # dhpre = (dh2 @ W2[e]^T) * gelu'(hpre)
             dhpre = self.empty(E, Bk, f)
             self._gemm(A=dh2.data_ptr(), B=w2.data_ptr(), C=dhpre.data_ptr(), aux=t.hpre.data_ptr(), M=rows, N=f, K=d, lda=d,
                        ldb=d, ldc=f, ldaux=f, sA=Bk * d, sB=f * d, sC=Bk * f, sAux=Bk * f, batch=E, ksplit=1, a_kcontig=1,
                        b_kcontig=1, mode=hip.EPI_DACT, act=hip.ACT_GELU_ERF, alpha=1.0, dact_cached=t.hpre_is_dact)
             # dW1[e][d, f] += xin[e]^T dhpre[e]
-            self.gemm_f32_acc(out_ptr=g1.data_ptr(), M=d, N=f, K=rows, ldo=f, batch=E, sOut=d * f, A=t.xin.data_ptr(),
-                              B=dhpre.data_ptr(), lda=d, ldb=f, sA=Bk * d, sB=Bk * f, a_kcontig=0, b_kcontig=0)
+            self._param_acc(out_ptr=g1.data_ptr(), M=d, N=f, K=rows, ldo=f, batch=E, sOut=d * f, A=t.xin.data_ptr(),
+                            B=dhpre.data_ptr(), lda=d, ldb=f, sA=Bk * d, sB=Bk * f, a_kcontig=0, b_kcontig=0)
             # dxin = dhpre @ W1[e]^T
             dxin = self.empty(E, Bk, d)
             self._gemm(A=dhpre.data_ptr(), B=w1.data_ptr(), C=dxin.data_ptr(), M=rows, N=d, K=f, lda=f, ldb=f, ldc=d, sA=Bk * f,
@@ -1213,6 +1240,7 @@ class DiTEngine:
         cfg, L, st = self.cfg, self.L, self._st()
         D, Dc = cfg.dim, y.shape[-1]
         Mc = B * Lc
+        tp.y_dtype, tp.y_rowscale = y.dtype, y_rowscale
         tp.ycap = self.empty(Mc, Dc)
         hip.check(L.md_cast_rows_bf16(y.data_ptr(), 0 if y.dtype == torch.float16 else 1, tp.ycap.data_ptr(), Mc, Dc,
                                       _p(y_rowscale), Lc, st), "cast_rows")
@@ -1291,6 +1319,7 @@ class DiTEngine:
         tp.arena = self._arena is not None
         tp.B, tp.T, tp.Lc, tp.H, tp.W = B, T, Lc, H, W
         # ---- patch embedding (+ pos), dit.py:479
+        tp.in_scale, tp.from_patches = in_scale, patches is not None      # (the image gradient multiplies by the same per-sample factor)
         if patches is None:
             tp.patches = self.empty(B * T, cfg.patch_vec)
             hip.check(L.md_patchify(x_img.data_ptr(), _p(in_scale), tp.patches.data_ptr(), B, C, H, W, p, st), "patchify")
@@ -1305,6 +1334,7 @@ class DiTEngine:
         tp.tfreq = self.empty(B, 512)
         t_f = t_in if (t_in.dtype == F32 and t_in.numel() == B and t_in.is_contiguous()) else t_in.to(F32).expand(B).contiguous()
         hip.check(L.md_timestep_embed(t_f.data_ptr(), tp.tfreq.data_ptr(), B, 512, st), "timestep_embed")
+        tp.t_f = t_f
         tp.t_pre = self.empty(B, D)
         tp.t_h = self.empty(B, D)
         self.lin_fwd(tp.tfreq, "t_embedder.mlp.0", tp.t_h, B, D, 512, act=hip.ACT_GELU_TANH, C2=tp.t_pre)
@@ -1475,19 +1505,29 @@ class DiTEngine:
                                        cfg.in_channels, tp.H, tp.W, cfg.patch_size, self._st()), "unpatchify")
         return img
 
-    def backward(self, tp: Tape, dtok: torch.Tensor, on_segment=None) -> None:
+    def backward(self, tp: Tape, dtok: torch.Tensor, on_segment=None, *, input_grads=(), param_grads: bool = True) -> InputGrads:
         """dtok: bf16 [B*Tk, p*p*C] grad of the network output for the kept tokens.  Accumulates every parameter
         gradient into the fp32 grad buffers (self.G).  `on_segment(prefix)` is called as soon as every kernel that
-        writes the gradients of the parameters under `prefix` has been enqueued (data-parallel bucket hand-off)."""
+        writes the gradients of the parameters under `prefix` has been enqueued (data-parallel bucket hand-off).
+        input_grads: subset of {"x", "t", "y"} -- the returned InputGrads holds the gradients of those network inputs (DESIGN.md
+        4.17); they are fresh tensors of the torch allocator, never arena memory.  Empty: the launches of a backward without them.
+        param_grads=False: the dgrad-only backward -- nothing under self.G is written or zeroed and no weight-gradient, bias or
+        LayerNorm-weight reduction is launched; every data-gradient launch is the one of a full backward."""
+        want = frozenset(input_grads)
+        if not want <= {"x", "t", "y"}:
+            raise ValueError(f"input_grads must be a subset of {{'x', 't', 'y'}}, got {sorted(want)}")
         use = self.use_arena and getattr(tp, "arena", False)
         if use:
             self._scratch_arena.begin((tp.B, tp.T, tp.Tk, tp.Lc, tp.H, tp.W))
             self._arena = self._scratch_arena
         ok = False
+        self._param_grads = bool(param_grads)
         try:
-            self._backward(tp, dtok, on_segment)
+            out = self._backward(tp, dtok, on_segment, want)
             ok = True
+            return out
         finally:
+            self._param_grads = True
             if use:
                 self._scratch_arena.end(ok)
             self._arena = None
@@ -1500,8 +1540,9 @@ class DiTEngine:
         self._block_bwd(*a)
         self._arena.release(m)
 
-    def _backward(self, tp: Tape, dtok: torch.Tensor, on_segment=None) -> None:
+    def _backward(self, tp: Tape, dtok: torch.Tensor, on_segment=None, want=frozenset()) -> InputGrads:
         cfg, L, st = self.cfg, self.L, self._st()
+        out = InputGrads()
         seg = on_segment if on_segment is not None else (lambda name: None)
         B, T, Tk, Lc = tp.B, tp.T, tp.Tk, tp.Lc
         D, Dm, pv = cfg.dim, cfg.patch_mixer_dim, cfg.patch_vec
@@ -1577,9 +1618,20 @@ class DiTEngine:
             self.ln_bwd(a, dln, dtok_e, accumulate=False, wname="patch_mixer_map_xin.0")
         else:
             dtok_e = dx
-        self.gemm_f32_acc(out_ptr=self.G["x_embedder.proj.weight"].data_ptr(), M=D, N=pv, K=B * T, ldo=pv,
-                          A=dtok_e.data_ptr(), B=tp.patches.data_ptr(), lda=D, ldb=pv, a_kcontig=0, b_kcontig=0)
-        self._colsum(dtok_e.data_ptr(), 0, D, self.G["x_embedder.proj.bias"].data_ptr(), B * T, D)
+        self._param_acc(out_ptr=self.G["x_embedder.proj.weight"].data_ptr(), M=D, N=pv, K=B * T, ldo=pv,
+                        A=dtok_e.data_ptr(), B=tp.patches.data_ptr(), lda=D, ldb=pv, a_kcontig=0, b_kcontig=0)
+        self._param_colsum(dtok_e.data_ptr(), 0, D, self.G["x_embedder.proj.bias"].data_ptr(), B * T, D)
+        if "x" in want:
+            # image: the transpose of md_patchify(in_scale) + the x_embedder.proj GEMM in one launch, fp32 straight from the accumulators
+            if tp.from_patches:
+                raise RuntimeError("the image gradient needs a forward that patchified its own input (patches= is inference-only)")
+            out.dx = torch.empty(B, cfg.in_channels, tp.H, tp.W, device=self.dev, dtype=F32)
+            path = ctypes.c_int32(-1)
+            self._prof("patch_embed_dgrad", 2.0 * B * T * D, lambda: hip.check(self.L.md_patch_embed_dgrad(
+                dtok_e.data_ptr(), D, self.S["x_embedder.proj.weight"].data_ptr(), _p(tp.in_scale), out.dx.data_ptr(), B, cfg.in_channels,
+                tp.H, tp.W, cfg.patch_size, D, byref(path), st), "md_patch_embed_dgrad"))
+            if self.input_grad_log is not None:
+                self.input_grad_log.append(("md_patch_embed_dgrad", path.value))
         # ---- condition vector: c = temb + pooled ; gc = gelu(c)
         if grp_b is not None:
             self._adaln_dgrad_grouped(grp_b, B, 6 * self.backbone[0].dim, dgc)
@@ -1592,6 +1644,13 @@ class DiTEngine:
         dtpre = self.empty(B, D)
         self.lin_dgrad(dc, "t_embedder.mlp.2", dtpre, B, D, D, mode=hip.EPI_DACT, act=hip.ACT_GELU_TANH, aux=tp.t_pre)
         self.lin_wgrad(dtpre, tp.tfreq, "t_embedder.mlp.0", B, D, 512)
+        if "t" in want:
+            dtfreq = self.empty(B, 512)
+            self.lin_dgrad(dtpre, "t_embedder.mlp.0", dtfreq, B, D, 512)
+            out.dt = torch.empty(B, device=self.dev, dtype=F32)
+            hip.check(L.md_timestep_embed_bwd(tp.t_f.data_ptr(), dtfreq.data_ptr(), out.dt.data_ptr(), B, 512, st), "md_timestep_embed_bwd")
+            if self.input_grad_log is not None:
+                self.input_grad_log.append(("md_timestep_embed_bwd", None))
         # pooled-caption MLP -> mean over tokens
         dymean = self._mlp_norm_bwd("pooled_y_emb_process", tp.pool, dc, B, D, 1, need_dx=True)
         hip.check(L.md_mean_tokens_bwd(dymean.data_ptr(), dy2_f32.data_ptr(), B, Lc, D, st), "mean_bwd")
@@ -1632,6 +1691,14 @@ class DiTEngine:
         dxn1 = self._self_attn_bwd("y_emb_preprocess.attn", cb.xn1, do, B, Lc, D, D, heads_c, cb.sa)
         a = self.ln_args(tp.y0, "y_emb_preprocess.norm1", None, Mc, D, mean=cb.st1[0], rstd=cb.st1[1], rps=Lc)
         self.ln_bwd(a, dxn1, dy, accumulate=True, wname="y_emb_preprocess.norm1")
-        # ---- caption projection (inputs need no grad)
-        self._mlp_norm_bwd("y_embedder.y_proj", tp.yproj, dy, Mc, tp.ycap.shape[1], Lc, need_dx=False)
+        # ---- caption projection, then (asked for) the transpose of the caption cast: rows times the forward's y_rowscale
+        Dc = tp.ycap.shape[1]
+        dycap = self._mlp_norm_bwd("y_embedder.y_proj", tp.yproj, dy, Mc, Dc, Lc, need_dx="y" in want)
+        if "y" in want:
+            out.dy = torch.empty(Mc, Dc, device=self.dev, dtype=tp.y_dtype)
+            hip.check(L.md_cast_rows_from_bf16(dycap.data_ptr(), out.dy.data_ptr(), 0 if tp.y_dtype == torch.float16 else 1, Mc, Dc,
+                                               _p(tp.y_rowscale), Lc, st), "md_cast_rows_from_bf16")
+            if self.input_grad_log is not None:
+                self.input_grad_log.append(("md_cast_rows_from_bf16", None))
         seg("rest")
+        return out

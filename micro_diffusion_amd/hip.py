@@ -288,6 +288,11 @@ _sig("md_lora_grad", P, P, P, P, I32, I32, F32, F32, P, P, I64, P)
 _sig("md_disperse_ws_doubles", I64, POINTER(c_int64))
 _sig("md_disperse_pairs", P, I64, I64, I64, F32, F64, P, I64, P, P, I64, P, P, F32, P)
 _sig("md_disperse_gram_small", P, I64, I64, I64, P, I64, P)
+# input gradients: embedded-token gradient -> image gradient, timestep-feature gradient -> dt, bf16 caption rows -> f32 | f16
+_sig("md_patch_embed_dgrad", P, I64, P, P, P, I64, I32, I32, I32, I32, I32, POINTER(c_int32), P)
+_sig("md_timestep_embed_bwd", P, P, P, I64, I32, P)
+_sig("md_cast_rows_from_bf16", P, P, I32, I64, I64, P, I64, P)
+PATCH_EMBED_DGRAD_MAX_PV = 64   # MD_PATCH_EMBED_DGRAD_MAX_PV
 DISPERSE_MAX_B = 4096    # MD_DISPERSE_MAX_B
 LORA_RANKS = (4, 8, 16, 32, 64)
 EMA_MAX_PROFILES = 4     # MD_EMA_MAX_PROFILES

@@ -169,7 +169,8 @@ class LatentDiffusion(nn.Module):
         rnd, eps, mnoise = self._draws(x, T, mask_ratio) if _noise is None else _noise
         if mask_ratio > 0:
             assert dit.training, "Masking is only recommended during training"
-        y = y.detach()
+        if not (torch.is_grad_enabled() and y.requires_grad):     # (a y that requires grad: the conversions stay differentiable torch ops)
+            y = y.detach()
         if y.dtype not in (torch.float16, torch.float32):
             y = y.float()
         y = y.contiguous()
@@ -183,7 +184,10 @@ class LatentDiffusion(nn.Module):
     def edm_loss(self, x: torch.Tensor, y: torch.Tensor, mask_ratio: float = 0, _noise=None, _y_rowscale=None, **kwargs) -> torch.Tensor:
         """model.py:181-210 on the HIP engine.  `_noise=(rnd_normal, eps, mask_noise)` injects the three random
         draws (parity tests); otherwise they are drawn here in the reference's order.  `_y_rowscale` [B] f32: per-sample
-        factor on the caption rows (the caption-drop mask)."""
+        factor on the caption rows (the caption-drop mask).
+        Gradients: the parameters' (when they require grad) and d loss / d y when y requires grad -- through the same
+        row factor, so a dropped caption gets an exactly zero gradient; with a frozen network the backward is the engine's dgrad-only
+        one.  The gradient with respect to the clean latents x is NOT provided: x is detached here."""
         if self.disperse is not None and self.disperse.enabled and torch.is_grad_enabled() and next(self.dit.parameters()).requires_grad:
             raise RuntimeError("the dispersive loss is armed (LatentDiffusion.disperse): its gradient exists only on the "
                                "Trainer's microbatch path (train_microbatch); the autograd surface would train the network on the "
@@ -196,7 +200,7 @@ class LatentDiffusion(nn.Module):
                                "Trainer's microbatch path (train_microbatch); the autograd surface would train the network on the "
                                "unweighted loss.  Disarm it or run under torch.no_grad()")
         args = (self, dit._grad_anchor, x, y, rnd, eps, mnoise, float(mask_ratio), _y_rowscale)
-        if need_grad:
+        if need_grad or (torch.is_grad_enabled() and y.requires_grad):
             return _EDMLossFunction.apply(*args)
         return _edm_forward(*args)[0]
 
@@ -731,21 +735,25 @@ class _EDMLossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, anchor, x, y, rnd, eps, mnoise, mask_ratio, y_rowscale):
         loss, tape, dtok = _edm_forward(model, anchor, x, y, rnd, eps, mnoise, mask_ratio, y_rowscale, record_tape=True)
-        ctx.model, ctx.tape, ctx.dtok = model, tape, dtok
+        ctx.model, ctx.tape, ctx.dtok, ctx.y_shape = model, tape, dtok, y.shape
         return loss
 
     @staticmethod
     def backward(ctx, gloss):
         model, tape, dtok = ctx.model, ctx.tape, ctx.dtok
         dit = model.dit
-        dit.attach_grads()
+        pgrad = any(p.requires_grad for p in dit._plist)
+        if pgrad:
+            dit.attach_grads()
         g = gloss.detach().to(torch.float32).contiguous()
         dtb = torch.empty(dtok.shape, device=dtok.device, dtype=torch.bfloat16)
         hip.check(hip.lib().md_cast_f32_bf16(dtok.data_ptr(), dtb.data_ptr(), dtok.numel(), g.data_ptr(),
                                              torch.cuda.current_stream().cuda_stream), "md_cast_f32_bf16")
-        dit._engine.backward(tape, dtb, on_segment=getattr(dit, "_on_segment", None))
+        ig = dit._engine.backward(tape, dtb, on_segment=getattr(dit, "_on_segment", None),
+                                  input_grads=("y",) if ctx.needs_input_grad[3] else (), param_grads=pgrad)
         ctx.tape = ctx.dtok = None
-        return None, torch.zeros_like(dit._grad_anchor), None, None, None, None, None, None, None
+        dy = None if ig.dy is None else ig.dy.view(ctx.y_shape)
+        return None, torch.zeros_like(dit._grad_anchor), None, dy, None, None, None, None, None
 
 
 class _FrozenStub(nn.Module):
