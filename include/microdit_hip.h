@@ -730,6 +730,42 @@ int md_timestep_embed_bwd(const float* t, const void* dout, float* dt, int64_t B
 int md_cast_rows_from_bf16(const void* x, void* y, int32_t y_dtype, int64_t rows, int64_t C, const float* rowscale,
                            int64_t rows_per_sample, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------- measurement-guided sampling */
+/* (Added under ABI 6: new symbols only.)  Everything around the two network passes of a guided sampler step (Chung et
+ * al. 2023 on the EDM loop; no reference source).  x_hat is the fp64 state the step's first evaluation read at level t_in, F the
+ * network output of that evaluation (has_uncond: the unconditional half behind the conditional one, combined as in the update
+ * kernels).  Bandwidth-bound, no atomics, nothing returns to the host; two calls give the same bits.
+ * md_edm_denoised(_tok): D f32 [B, C, H, W] = c_skip * float(x_hat) + c_out * F with F = F_u + cfg * (F_c - F_u) under has_uncond -- the
+ *   same fp32 expressions (sampler_math.h) as `den` inside md_edm_heun_update / md_edm_solver_update, so D has the bits of the value the
+ *   step's own update forms.  F is the fp32 image [B or 2B, per_sample], or (_tok) the bf16 token rows in md_edm_heun_update_tok's
+ *   layout; the token form gives the bits of md_unpatchify followed by the image form.
+ * md_measure_residual: for the measurement operator A = s x s average pooling (s = 1: the identity), per pooled cell in fp32
+ *   r = m * (meas - A(D)),  q = -2 * m * r / s^2 written to every pixel of the cell's window (q = dL/dD, f32 [B, C, H, W]),
+ *   L[b] = sum over the sample of r^2: the fp32 squares summed in fp64, one workgroup per sample, fixed order (per-thread partials,
+ *   then a tree over the 256 partials in LDS).  meas f32 [B, C, H/s, W/s]; mask f32 [mask_B, H/s * W/s] with mask_B 1 or B,
+ *   broadcast over the channels, or NULL (= 1).  For a 0 / 1 mask q is -2 * A^T(m * (meas - A(D))).
+ * md_guide_cotangent_tok: dtok bf16 [B*T or 2B*T, C*p*p] in the network's output-token layout (element (ph*p + pw)*C + c): the
+ *   cotangent of the network output under q.  Rows of the conditional half are (cfg * c_out) * q, with has_uncond rows from B*T on
+ *   are ((1 - cfg) * c_out) * q; without has_uncond the one half is c_out * q (cfg is not read).  One bf16 rounding.
+ * md_edm_guide_apply: x_next[b] -= zeta / max(sqrt(L[b]), MD_GUIDE_TINY) * (c_skip * q[b] + c_in * (dx[b] + dx[B + b])), in fp64, in
+ *   place on the state the solver wrote.  dx f32 [B or 2B, per_sample]: the gradient of the network input from the engine, the
+ *   unconditional half (has_uncond) behind the conditional; c_skip and c_in are the fp32 values of level t_in, widened.
+ * 16-byte accesses where the sizes and the pointers allow (4 elements per item, patch_vec % 8 == 0 for token rows, W % 4 == 0 and s in
+ * {1, 2, 4} for the residual), element by element otherwise.
+ * MD_BAD_ARG, nothing launched: a null pointer (mask excepted), a non-positive size, H % p or W % p non-zero, H % s or W % s non-zero,
+ * mask_B other than 1 or B, t_in <= 0, or a non-finite cfg, zeta, t_in or sigma_data. */
+#define MD_GUIDE_TINY 1e-30 /* floor of sqrt(L[b]) in md_edm_guide_apply: a sample whose residual is exactly zero gets a finite step (its q, dx are zero too) */
+int md_edm_denoised(const double* x_hat, const float* F, float* D, int64_t B, int64_t per_sample, float cfg, int32_t has_uncond, double t_in,
+                    float sigma_data, hipStream_t stream);
+int md_edm_denoised_tok(const double* x_hat, const void* tok_bf16, float* D, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg,
+                        int32_t has_uncond, double t_in, float sigma_data, hipStream_t stream);
+int md_measure_residual(const float* D, const float* meas, const float* mask, int32_t mask_B, float* q, double* L, int64_t B, int32_t C,
+                        int32_t H, int32_t W, int32_t s, hipStream_t stream);
+int md_guide_cotangent_tok(const float* q, void* dtok_bf16, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg,
+                           int32_t has_uncond, double t_in, float sigma_data, hipStream_t stream);
+int md_edm_guide_apply(double* x_next, const float* q, const float* dx, const double* L, int64_t B, int64_t per_sample, int32_t has_uncond,
+                       double zeta, double t_in, float sigma_data, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 //   md_edm_loss         D = c_skip*xn + c_out*F, weighted SE, mean over the UN-MASKED patches per sample, batch
 //                       mean (model.py:177,199-210) and its gradient w.r.t. the kept-token network output.
 #include "md_common.h"
+#include "sampler_math.h"
 #include "../../include/microdit_hip.h"
 #include <cmath>
 
@@ -161,27 +162,7 @@ inline int egrid(int64_t work) {
 //                   second half-step: x_next = x_hat + (t_next - t_hat) * (0.5 d_cur + 0.5 d)
 //   sampler_patchify / heun_update_tok: the same two, writing bf16 patch rows / reading the bf16 token output directly
 // ---------------------------------------------------------------------------------------------------------------------
-// The per-element arithmetic, shared by the image-space and the token-space kernels below.  Every multiply-add is written as an
-// explicit fma: left to the compiler, the same expression was contracted in one kernel and evaluated as multiply, multiply, add in
-// another (it vectorises the two products first), and the two forms of a step must give the same bits.
-__device__ __forceinline__ float sampler_c_in(float sigma, float sigma_data) {
-    return 1.f / sqrtf(fmaf(sigma, sigma, sigma_data * sigma_data));
-}
-__device__ __forceinline__ float sampler_net_in(float c_in, double x) { return c_in * (float)x; }
-__device__ __forceinline__ void heun_coef(double t_in, float sigma_data, float& c_skip, float& c_out) {
-    const float sg = (float)t_in;
-    const float den = fmaf(sg, sg, sigma_data * sigma_data);
-    c_skip = sigma_data * sigma_data / den;
-    c_out = sg * sigma_data / sqrtf(den);
-}
-__device__ __forceinline__ float cfg_combine(float fc, float fu, float cfg) { return fmaf(cfg, fc - fu, fu); }
-// D = c_skip * float(x_in) + c_out * F in fp32 (model.py:177), widened to the fp64 of the state.
-__device__ __forceinline__ float sampler_denoised_f32(double xi, float f, float c_skip, float c_out) {
-    return fmaf(c_skip, (float)xi, c_out * f);
-}
-__device__ __forceinline__ double sampler_denoised(double xi, float f, float c_skip, float c_out) {
-    return (double)sampler_denoised_f32(xi, f, c_skip, c_out);
-}
+// The per-element arithmetic, shared by the image-space and the token-space kernels below (and by guide.hip): sampler_math.h.
 // The combine of the guidance modes, in the space of the denoised value: D = alpha_b * D_c + gamma_b * M with D_c the
 // conditional prediction, M the running difference md_guidance_prepare left in the layout of the state and (alpha_b, gamma_b) the
 // per-sample coefficients it formed.  fp32 like the preconditioning, widened to the fp64 of the state.

@@ -138,6 +138,9 @@ class DiTEngine:
     # False inside a dgrad-only backward (backward(param_grads=False)): the helpers that write self.G -- lin_wgrad,
     # _param_acc, _param_colsum, ln_bwd's weight reduction -- launch nothing; every data-gradient launch is the one of a full backward
     _param_grads = True
+    # True inside a backward that stops at the image (input_grads=("x",), param_grads=False): nothing that dx does not
+    # depend on is launched -- the K side of the cross-attention QK-LayerNorm, the caption-token and condition-vector contractions
+    _x_only = False
 
     def __init__(self, cfg: DiTConfig, params: Dict[str, torch.Tensor], shadows: Dict[str, torch.Tensor],
                  grads: Dict[str, torch.Tensor], buffers: Dict[str, torch.Tensor]):
@@ -998,20 +1001,27 @@ class DiTEngine:
                                 delta=delta, lddv=2 * hx, hm_qk=True)
             self._attn_bwd(ax)
             self._qkln_bwd_hm(dq2n, t.q2n, dq2.data_ptr(), hx, 0, M, hx, S, t.rq2.data_ptr())
-            self._qkln_bwd_hm(dk2n, t.k2n, dkv.data_ptr(), 2 * hx, 0, Mc, hx, Lc, t.rk2.data_ptr())
+            if not self._x_only:
+                self._qkln_bwd_hm(dk2n, t.k2n, dkv.data_ptr(), 2 * hx, 0, Mc, hx, Lc, t.rk2.data_ptr())
         else:
             ax = self.attn_args(t.q2.data_ptr(), t.kv.data_ptr(), t.kv.data_ptr() + 2 * hx, t.o2, t.lse2, B, bp.xheads, S, Lc, hx,
                                 2 * hx, 2 * hx, hx, do=do2, dq=dq2.data_ptr(), dk=dkv.data_ptr(), dv=dkv.data_ptr() + 2 * hx,
                                 delta=delta, lddq=hx, lddk=2 * hx, lddv=2 * hx)
             self._attn_bwd(ax)
             self._qkln_bwd(dq2.data_ptr(), hx, 0, t.q2.data_ptr(), hx, 0, M, hx, t.rq2.data_ptr())
-            self._qkln_bwd(dkv.data_ptr(), 2 * hx, 0, t.kv.data_ptr(), 2 * hx, 0, Mc, hx, t.rk2.data_ptr())
+            if not self._x_only:
+                self._qkln_bwd(dkv.data_ptr(), 2 * hx, 0, t.kv.data_ptr(), 2 * hx, 0, Mc, hx, t.rk2.data_ptr())
         self.lin_wgrad(dq2, t.xn2, n + ".cross_attn.q_linear", M, hx, d, defer=True)
-        self.lin_wgrad(dkv, ycond, n + ".cross_attn.kv_linear", Mc, 2 * hx, d)
+        # (stopping at the image, _x_only: dK / dV of the fused attention backward are not consumed -- no K-LayerNorm backward above, no
+        # kv_linear gradient of either kind below, so a frozen conditioning needs neither the K rstd nor the caption tokens)
+        if not self._x_only:
+            self.lin_wgrad(dkv, ycond, n + ".cross_attn.kv_linear", Mc, 2 * hx, d)
         # d(ycond) accumulates in fp32 over all blocks that attend to these caption tokens: per block (split-K slices + a
         # reduction pass into the [B*L, d] fp32 buffer, 28 times), or -- kvgroup -- deferred: dkv of every block is kept and ONE
         # launch contracts the concatenation [dkv_0 | dkv_1 | ...] with [Wkv_0; Wkv_1; ...] (_dycond_grouped)
-        if kvgroup is None:
+        if self._x_only:
+            pass
+        elif kvgroup is None:
             self.gemm_f32_acc(out_ptr=dycond_f32.data_ptr(), M=Mc, N=d, K=2 * hx, ldo=d, A=dkv.data_ptr(),
                               B=self.S[n + ".cross_attn.kv_linear.weight"].data_ptr(), lda=2 * hx, ldb=d, a_kcontig=1, b_kcontig=0)
         else:
@@ -1033,7 +1043,8 @@ class DiTEngine:
         self.ln_bwd(a1, dxm1, dx, accumulate=True, wname=n + ".norm1", dscale=dmp + 4 * d, dshift=dmp, ldg=6 * d)
         self._wgroup = None
         # ---------------- adaLN linear: mod = W gelu(c) + b
-        self._adaln_bwd(n + ".adaLN_modulation.1", dmod, B, 6 * d, gc, dgc_f32, group)
+        if not self._x_only:
+            self._adaln_bwd(n + ".adaLN_modulation.1", dmod, B, 6 * d, gc, dgc_f32, group)
 
     def _adaln_bwd(self, wname, dmod_f32, B, N, gc, dgc_f32, group=None):
         """Backward of mod = W gelu(c) + b for one layer.  The weight / bias gradients are taken at once; the gradient w.r.t.
@@ -1174,7 +1185,7 @@ class DiTEngine:
     def forward(self, x_img: Optional[torch.Tensor], t_in: torch.Tensor, y: Optional[torch.Tensor] = None, *, mask_ratio: float = 0.0,
                 mask_noise: Optional[torch.Tensor] = None, in_scale: Optional[torch.Tensor] = None,
                 y_rowscale: Optional[torch.Tensor] = None, record_tape: bool = False, arena: bool = False,
-                cond: Optional[Conditioning] = None, patches: Optional[torch.Tensor] = None) -> Tape:
+                cond: Optional[Conditioning] = None, patches: Optional[torch.Tensor] = None, input_tape: bool = False) -> Tape:
         """x_img f32 [B,C,H,W] (multiplied by in_scale[b] if given), t_in f32 [B], y f16|f32 [B,(1,)L,Dc]
         (rows multiplied by y_rowscale[b] if given).  Returns the tape; tape.out_tok is the network output for the
         kept tokens, bf16 [B*Tk, p*p*C].
@@ -1185,11 +1196,16 @@ class DiTEngine:
         cond: the result of encode_condition() for these captions -- the caption stream and every block's kv_linear / K-LayerNorm
         are skipped and the cached buffers used instead (y is not read and may be None).
         patches: bf16 [B*T, patch_vec] patch rows as md_patchify writes them -- used in place of patchifying x_img (which may be
-        None: the latent grid is then the model's input_size).  cond and patches are inference-only."""
+        None: the latent grid is then the model's input_size).  cond and patches are inference-only.
+        input_tape (with cond and / or patches): keep what a backward to the network input alone needs -- every block's
+        activations and references to the cached K / V the blocks read; the conditioning is frozen.  backward() on such a tape takes
+        input_grads=("x",), param_grads=False and nothing else."""
         cfg = self.cfg
         if cond is not None or patches is not None:
             if record_tape or arena or mask_ratio > 0:
                 raise RuntimeError("cond / patches are inference-only: they cannot be combined with record_tape, arena or mask_ratio > 0")
+        elif input_tape:
+            raise ValueError("input_tape records a pass that reads cond= and / or patches=; without them use record_tape")
         if patches is not None:
             assert patches.dtype == BF16 and patches.is_contiguous() and patches.dim() == 2 and patches.shape[1] == cfg.patch_vec
             B, rem = divmod(patches.shape[0], cfg.tokens)
@@ -1214,7 +1230,7 @@ class DiTEngine:
             assert y.is_contiguous() and y.dtype in (torch.float16, F32)
             Lc, Dc, ydt = y.shape[-2], y.shape[-1], str(y.dtype)
         grad_pass = self.use_arena and arena and record_tape
-        self._record = record_tape or self.keep_last_tape
+        self._record = record_tape or input_tape or self.keep_last_tape
         dsp = self.disperse
         self._disperse_on = bool(record_tape and dsp is not None and dsp[1] > 0)
         if self._disperse_on and not 0 <= dsp[0] < len(self.backbone):
@@ -1227,6 +1243,7 @@ class DiTEngine:
         ok = False
         try:
             tp = self._forward(x_img, t_in, y, mask_ratio, mask_noise, in_scale, y_rowscale, cond, patches, B, H, W, Lc)
+            tp.input_tape = bool(input_tape)
             ok = True
             return tp
         finally:
@@ -1349,6 +1366,7 @@ class DiTEngine:
             pooled = tp.pool.hn
         else:
             y2, pooled = None, cond.pooled
+            tp.y2 = None                            # (an input_tape's backward passes it on as the caption tokens nobody reads)
         c = self._mlp_norm_out("pooled_y_emb_process", pooled, B, res=temb)
         tp.c = c
         gc = self.empty(B, D)
@@ -1512,22 +1530,30 @@ class DiTEngine:
         input_grads: subset of {"x", "t", "y"} -- the returned InputGrads holds the gradients of those network inputs (DESIGN.md
         4.17); they are fresh tensors of the torch allocator, never arena memory.  Empty: the launches of a backward without them.
         param_grads=False: the dgrad-only backward -- nothing under self.G is written or zeroed and no weight-gradient, bias or
-        LayerNorm-weight reduction is launched; every data-gradient launch is the one of a full backward."""
+        LayerNorm-weight reduction is launched; every data-gradient launch is the one of a full backward.
+        input_grads=("x",) with param_grads=False stops at the image: it returns right after md_patch_embed_dgrad and
+        launches nothing dx does not depend on; dx has the bits of the full dgrad-only backward.  It is the only backward of an
+        input_tape (forward(..., input_tape=True)), whose conditioning is frozen; a tape of a forward that read patches= gives the
+        gradient with respect to the un-patchified network input."""
         want = frozenset(input_grads)
         if not want <= {"x", "t", "y"}:
             raise ValueError(f"input_grads must be a subset of {{'x', 't', 'y'}}, got {sorted(want)}")
+        x_only = want == {"x"} and not param_grads
+        if getattr(tp, "input_tape", False) and not x_only:
+            raise RuntimeError("an input_tape holds a frozen conditioning: its backward takes input_grads=('x',) and param_grads=False, "
+                               f"got input_grads={sorted(want)}, param_grads={bool(param_grads)}")
         use = self.use_arena and getattr(tp, "arena", False)
         if use:
             self._scratch_arena.begin((tp.B, tp.T, tp.Tk, tp.Lc, tp.H, tp.W))
             self._arena = self._scratch_arena
         ok = False
-        self._param_grads = bool(param_grads)
+        self._param_grads, self._x_only = bool(param_grads), x_only
         try:
             out = self._backward(tp, dtok, on_segment, want)
             ok = True
             return out
         finally:
-            self._param_grads = True
+            self._param_grads, self._x_only = True, False
             if use:
                 self._scratch_arena.end(ok)
             self._arena = None
@@ -1548,16 +1574,17 @@ class DiTEngine:
         D, Dm, pv = cfg.dim, cfg.patch_mixer_dim, cfg.patch_vec
         Mc = B * Lc
         gc = tp.gc
-        dgc = self.zeros(B, D)                      # fp32: sums the adaLN dgrads of all 6+28+1 layers
-        dy2_f32 = self.zeros(Mc, D)                 # fp32: caption-token grads from the 28 backbone kv_linears + pooling
+        x_only = self._x_only                       # stop at the image: no condition-vector or caption-token gradient is formed
+        dgc = None if x_only else self.zeros(B, D)          # fp32: sums the adaLN dgrads of all 6+28+1 layers
+        dy2_f32 = None if x_only else self.zeros(Mc, D)     # fp32: caption-token grads from the 28 backbone kv_linears + pooling
         grp_b = grp_m = None
-        if self.group_adaln:                        # bf16 dmod of every layer, kept until the grouped contraction below
+        if self.group_adaln and not x_only:                    # bf16 dmod of every layer, kept until the grouped contraction below
             if self.backbone:
                 grp_b = {"buf": self.empty(len(self.backbone), B, 6 * self.backbone[0].dim), "w": []}
             if self.mixer:
                 grp_m = {"buf": self.empty(len(self.mixer), B, 6 * self.mixer[0].dim), "w": []}
         kv_b = kv_m = None
-        if self.group_dycond:                       # dkv of every block, kept until the concatenated contraction
+        if self.group_dycond and not x_only:        # dkv of every block, kept until the concatenated contraction
             if self.backbone:
                 kv_b = {"buf": self.empty(len(self.backbone), Mc, 2 * self.backbone[0].xattn_hidden), "w": []}
             if self.mixer:
@@ -1573,7 +1600,8 @@ class DiTEngine:
                           mean=tp.st_f[0], rstd=tp.st_f[1])
         self.ln_bwd(af, dxf, dx, accumulate=False, wname="final_layer.norm_final", dscale=dfm.data_ptr() + 4 * D,
                     dshift=dfm.data_ptr(), ldg=2 * D)
-        self._adaln_bwd("final_layer.adaLN_modulation.1", dfm, B, 2 * D, gc, dgc)
+        if not x_only:
+            self._adaln_bwd("final_layer.adaLN_modulation.1", dfm, B, 2 * D, gc, dgc)
         seg("final_layer")
         # ---- backbone
         dsp = getattr(tp, "disperse", None)
@@ -1601,7 +1629,7 @@ class DiTEngine:
             dx = dfull
         # ---- patch mixer
         has_maps = cfg.use_patch_mixer and cfg.has_maps
-        dym_f32 = self.zeros(Mc, Dm) if has_maps else dy2_f32
+        dym_f32 = self.zeros(Mc, Dm) if has_maps and not x_only else dy2_f32
         for bp, bt in zip(reversed(self.mixer), reversed(tp.mixer)):
             self._block_bwd_scoped(bp, bt, dx, tp.ym, dym_f32, B, T, Lc, gc, dgc, grp_m, kv_m)
             seg(bp.name)
@@ -1623,8 +1651,7 @@ class DiTEngine:
         self._param_colsum(dtok_e.data_ptr(), 0, D, self.G["x_embedder.proj.bias"].data_ptr(), B * T, D)
         if "x" in want:
             # image: the transpose of md_patchify(in_scale) + the x_embedder.proj GEMM in one launch, fp32 straight from the accumulators
-            if tp.from_patches:
-                raise RuntimeError("the image gradient needs a forward that patchified its own input (patches= is inference-only)")
+            # (a forward that read patches= has no in_scale: dx is then the gradient of the un-patchified network input)
             out.dx = torch.empty(B, cfg.in_channels, tp.H, tp.W, device=self.dev, dtype=F32)
             path = ctypes.c_int32(-1)
             self._prof("patch_embed_dgrad", 2.0 * B * T * D, lambda: hip.check(self.L.md_patch_embed_dgrad(
@@ -1632,6 +1659,8 @@ class DiTEngine:
                 tp.H, tp.W, cfg.patch_size, D, byref(path), st), "md_patch_embed_dgrad"))
             if self.input_grad_log is not None:
                 self.input_grad_log.append(("md_patch_embed_dgrad", path.value))
+        if x_only:
+            return out
         # ---- condition vector: c = temb + pooled ; gc = gelu(c)
         if grp_b is not None:
             self._adaln_dgrad_grouped(grp_b, B, 6 * self.backbone[0].dim, dgc)

@@ -293,6 +293,14 @@ _sig("md_patch_embed_dgrad", P, I64, P, P, P, I64, I32, I32, I32, I32, I32, POIN
 _sig("md_timestep_embed_bwd", P, P, P, I64, I32, P)
 _sig("md_cast_rows_from_bf16", P, P, I32, I64, I64, P, I64, P)
 PATCH_EMBED_DGRAD_MAX_PV = 64   # MD_PATCH_EMBED_DGRAD_MAX_PV
+# measurement-guided sampling: the denoised prediction, the residual / its gradient / the per-sample loss, the cotangent of
+# the network output in token rows, and the correction of the fp64 state
+_sig("md_edm_denoised", P, P, P, I64, I64, F32, I32, F64, F32, P)
+_sig("md_edm_denoised_tok", P, P, P, I64, I32, I32, I32, I32, F32, I32, F64, F32, P)
+_sig("md_measure_residual", P, P, P, I32, P, P, I64, I32, I32, I32, I32, P)
+_sig("md_guide_cotangent_tok", P, P, I64, I32, I32, I32, I32, F32, I32, F64, F32, P)
+_sig("md_edm_guide_apply", P, P, P, P, I64, I64, I32, F64, F64, F32, P)
+GUIDE_TINY = 1e-30              # MD_GUIDE_TINY
 DISPERSE_MAX_B = 4096    # MD_DISPERSE_MAX_B
 LORA_RANKS = (4, 8, 16, 32, 64)
 EMA_MAX_PROFILES = 4     # MD_EMA_MAX_PROFILES

@@ -271,7 +271,7 @@ class LatentDiffusion(nn.Module):
                          cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
                          guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
                          guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
-                         apg_momentum: float = 0.0, **kwargs):
+                         apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, **kwargs):
         """EDM sampler, fp64 state (model.py:231-297).  `fused` (None = whenever possible) selects the loop whose per-step arithmetic
         runs in fused HIP kernels; False keeps the reference's tensor-op formulation (generic forward functions).
         `cond_cache` (None = the environment variable MD_SAMPLER_CACHE, default off): encode the captions once for the whole run
@@ -304,9 +304,25 @@ class LatentDiffusion(nn.Module):
         sample.  "apg" (`apg_eta`, `apg_norm_threshold` = r or None, `apg_momentum` = beta in (-1, 1)): the update M = (D_c - D_u) +
         beta * M_prev of the previous guided evaluation, clipped to norm r per sample, its component parallel to D_c weighted by eta.
         Both are alpha_b * D_c + gamma_b * M with per-sample coefficients (samplers.guidance_coefficients); they compose with every
-        argument above, and cfg <= 1 or an evaluation outside the interval runs unguided as in "cfg"."""
+        argument above, and cfg <= 1 or an evaluation outside the interval runs unguided as in "cfg".
+        Measurement-guided sampling (Chung et al. 2023; this loop with fused=False is the definition): `measurement`, an
+        inverse.LinearMeasurement (A = s x s average pooling, an observation meas = A(x0), an optional mask), or `guidance_loss`, a callable
+        taking the denoised prediction D (fp32 [B, C, H, W], requires grad) and returning per-sample losses [B] through differentiable torch
+        ops; one of the two.  At the first evaluation of every executed step (state x_hat, after the blend and the churn) the guided
+        prediction D gives L_b (for a measurement ||m * (meas - A(D))||^2), the solver computes x_next as without guidance (Heun's second
+        evaluation is not differentiated, dpmpp_2m's history holds the uncorrected D), and then
+        x_next[b] -= measurement_scale / max(sqrt(L_b), samplers.GUIDE_TINY) * dL_b/dx_hat, the gradient taken through the network, before
+        the RePaint re-noise.  The network is frozen for the run (requires_grad is restored afterwards, no .grad is written).  Composes with
+        the solvers, churn, guidance_interval, cond_cache, init_latents / inpaint_mask / resample; not done: with `guide`, with a
+        guidance_mode other than "cfg", with extra forward arguments."""
         ec = self.edm_config
         samplers.check_sampler(sampler, ec.S_churn)
+        guided_by = samplers.check_measurement(tuple(x.shape), measurement, measurement_scale, guidance_loss)
+        if guided_by:
+            for bad, what in ((guide is not None, "a guide network (autoguidance)"), (guidance_mode != "cfg", f"guidance_mode={guidance_mode!r}"),
+                              (bool(kwargs), f"extra forward arguments {sorted(kwargs)}")):
+                if bad:
+                    raise NotImplementedError(f"measurement / guidance_loss with {what}: not done (DESIGN.md 4.18)")
         interval = samplers.guidance_interval_bounds(guidance_interval)
         samplers.check_guide(self.dit, guide, guide_captions)
         samplers.check_guidance(guidance_mode, cfg, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum)
@@ -325,7 +341,14 @@ class LatentDiffusion(nn.Module):
             fused = can_fuse
         if fused:
             assert can_fuse, "the fused sampler needs CUDA tensors and no extra forward arguments"
-            return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, guide, guide_captions == "null", edit, gmode)
+            if not guided_by:
+                return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, guide, guide_captions == "null", edit, gmode)
+            guidance = (measurement, guidance_loss, float(measurement_scale))
+            with self._frozen_network():
+                return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, None, False, edit, None, guidance)
+        if guided_by:
+            with self._frozen_network():
+                return self._edm_sampler_guided_ops(x, y, n, cfg, sampler, interval, edit, measurement, guidance_loss, float(measurement_scale))
         if guide is not None:
             fwd = self._autoguided_forward(guide, torch.zeros_like(y) if guide_captions == "null" else y, cfg) if cfg > 1.0 else self.dit.forward
         else:
@@ -395,6 +418,87 @@ class LatentDiffusion(nn.Module):
                 raise ValueError("inpaint_mask must be bool or hold values in [0, 1] (1 = generate, 0 = keep init_latents)")
         return x0, m, samplers.edit_start_index(n, strength), resample
 
+    def _frozen_network(self):
+        """Context of a guided sampling run: every parameter of the network has requires_grad False inside (the backward to the image
+        is the engine's dgrad-only one and writes no .grad), and what it was before afterwards."""
+        from contextlib import contextmanager
+
+        @contextmanager
+        def frozen():
+            params = list(self.dit.parameters())
+            was = [p.requires_grad for p in params]
+            for p in params:
+                p.requires_grad_(False)
+            try:
+                yield
+            finally:
+                for p, r in zip(params, was):
+                    p.requires_grad_(r)
+        return frozen()
+
+    def _edm_sampler_guided_ops(self, x, y, n, cfg, sampler, interval, edit, measurement, guidance_loss, zeta):
+        """The tensor-op loop of edm_sampler_loop with measurement guidance: the definition the fused loop follows.  The
+        step's first evaluation runs model_forward_wrapper under torch.enable_grad() on the fp32 x_hat, torch.autograd.grad of L.sum() gives
+        g = dL/dx_hat through the (frozen) network, and the correction is applied in fp64 to the solver's result."""
+        ec = self.edm_config
+        loss_fn = guidance_loss if measurement is None else measurement.loss_fn(x)
+        fwd = partial(self.dit.forward, cfg=cfg) if cfg > 1.0 else self.dit.forward
+
+        def pick(sigma):
+            return fwd if interval is None or interval[0] <= float(sigma) <= interval[1] else self.dit.forward
+
+        def denoise(xs, sigma):
+            return self.model_forward_wrapper(xs.to(torch.float32), sigma.to(torch.float32), y, pick(sigma), mask_ratio=0)["sample"].to(torch.float64)
+
+        def denoise_with_gradient(xs, sigma):
+            """(D, g, L): the guided prediction at xs, dL/dxs and the per-sample losses, the last two in fp64."""
+            with torch.enable_grad():
+                x32 = xs.to(torch.float32).detach().requires_grad_(True)
+                D = self.model_forward_wrapper(x32, sigma.to(torch.float32), y, pick(sigma), mask_ratio=0)["sample"]
+                L = loss_fn(D)
+                g, = torch.autograd.grad(L.sum(), x32)
+            return D.detach().to(torch.float64), g.to(torch.float64), L.detach().to(torch.float64)
+        idx = torch.arange(n, dtype=torch.float64, device=x.device)
+        inv_rho = 1 / ec.rho
+        t_steps = (ec.sigma_max ** inv_rho + idx / (n - 1) * (ec.sigma_min ** inv_rho - ec.sigma_max ** inv_rho)) ** ec.rho
+        t_steps = torch.cat([t_steps, torch.zeros_like(t_steps[:1])])
+        x0, m, i0, resample = (None, None, 0, 1) if edit is None else edit
+        if m is not None:
+            m = m.view(m.shape[0], 1, x.shape[-2], x.shape[-1]).to(torch.float64)
+        if sampler != "heun":
+            levels = t_steps.tolist()
+            coef = samplers.solver_coefficients(sampler, levels[i0:], self._churned_levels(levels, n)[i0:])
+        reps = samplers.edit_repetitions(t_steps.tolist(), i0, resample) if resample > 1 else [1] * (n - i0)
+        draw_churn = m is None or ec.S_churn > 0
+        x_next = x.to(torch.float64) * t_steps[0] if edit is None else x0 + t_steps[i0] * x.to(torch.float64)
+        for i in range(i0, n):
+            t_cur, t_next = t_steps[i], t_steps[i + 1]
+            for rep in range(reps[i - i0]):
+                x_cur = x_next
+                if m is not None:
+                    x_cur = m * x_cur + (1 - m) * (x0 + t_cur * self.randn_like(x_cur))
+                gamma = min(ec.S_churn / n, np.sqrt(2) - 1) if ec.S_min <= t_cur <= ec.S_max else 0
+                t_hat = torch.as_tensor(t_cur + gamma * t_cur)
+                x_hat = x_cur + (t_hat ** 2 - t_cur ** 2).sqrt() * ec.S_noise * self.randn_like(x_cur) if draw_churn else x_cur
+                den, g, L = denoise_with_gradient(x_hat, t_hat)
+                if sampler != "heun":
+                    a, b, c1, c2 = coef[i - i0]
+                    x_next = a * x_hat + b * (c1 * den - c2 * hist if c2 != 0 else c1 * den)
+                    hist = den                      # the uncorrected prediction
+                else:
+                    d_cur = (x_hat - den) / t_hat
+                    x_next = x_hat + (t_next - t_hat) * d_cur
+                    if i < n - 1:
+                        den = denoise(x_next, t_next)
+                        d_prime = (x_next - den) / t_next
+                        x_next = x_hat + (t_next - t_hat) * (0.5 * d_cur + 0.5 * d_prime)
+                x_next = x_next - (zeta / L.sqrt().clamp_min(samplers.GUIDE_TINY)).view(-1, 1, 1, 1) * g
+                if rep < reps[i - i0] - 1:
+                    x_next = x_next + (t_cur ** 2 - t_next ** 2).sqrt() * self.randn_like(x_next)
+        if m is not None:
+            x_next = m * x_next + (1 - m) * x0
+        return x_next.to(torch.float32)
+
     def _mode_guided_denoise(self, unguided, y, w: float, interval, guide, guide_null: bool, gmode, kwargs):
         """denoise(xs, sigma) of the tensor-op loop in guidance mode "rescale" or "apg" (DESIGN.md 4.14), in plain torch: the
         preconditioning of model_forward_wrapper (fp32) around one doubled-batch forward without cfg=, or with a guide around two
@@ -438,7 +542,7 @@ class LatentDiffusion(nn.Module):
 
     @torch.no_grad()
     def _edm_sampler_fused(self, x, y, steps: Optional[int], cfg: float, cond_cache: bool = False, sampler: str = "heun", interval=None,
-                           guide=None, guide_null: bool = False, edit=None, gmode=None):
+                           guide=None, guide_null: bool = False, edit=None, gmode=None, guidance=None):
         """The same loops with everything around the network evaluations in fused HIP kernels: md_edm_sampler_input (c_in scaling +
         guidance batch doubling) and md_edm_heun_update (guidance combine + preconditioning + fp64 Euler / Heun update) or, for
         euler / dpmpp_2m, md_edm_solver_update (the same with the linear-multistep update of samplers.solver_coefficients).
@@ -458,7 +562,14 @@ class LatentDiffusion(nn.Module):
         gmode = (mode, phi, eta, r or None, beta) of guidance mode "rescale" / "apg" (DESIGN.md 4.14): M (fp32, the state's layout), coef
         [B, 2] and moments [B, 5] are allocated once; every guided evaluation runs md_guidance_prepare(_tok) on the two outputs -- the
         halves of the doubled batch, or main's and the guide's -- and then the _coef form of its update kernel, which reads the
-        conditional output, M and coef.  Nothing comes back to the host.  None ("cfg"): none of it."""
+        conditional output, M and coef.  Nothing comes back to the host.  None ("cfg"): none of it.
+        guidance = (inverse.LinearMeasurement or None, loss callable or None, scale) of measurement-guided sampling (no guide,
+        no gmode): the first evaluation of every step keeps a tape -- cond_cache: engine.forward(patches=, cond=, input_tape=True), the
+        captions stay frozen in the cache; otherwise engine.forward(net_in, y, record_tape=True) --, then md_edm_denoised(_tok) -> D,
+        md_measure_residual -> q = dL/dD and L (or the callable under torch.enable_grad(), torch autograd supplying q),
+        md_guide_cotangent_tok -> the bf16 cotangent of both halves of the output, engine.backward(("x",), param_grads=False) -> the
+        gradient of the network input, which stops at the image; the tape is dropped, the step's usual update runs (Heun's second
+        evaluation without a tape) and md_edm_guide_apply corrects its result in place.  None: none of it."""
         ec, L, st = self.edm_config, hip.lib(), torch.cuda.current_stream().cuda_stream
         n = ec.num_steps if steps is None else steps
         idx = torch.arange(n, dtype=torch.float64)
@@ -507,6 +618,64 @@ class LatentDiffusion(nn.Module):
             patches = torch.empty(Bn * (H // p) * (W // p), dit.config.patch_vec, device=x.device, dtype=torch.bfloat16)
         else:
             net_in = torch.empty((Bn,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
+
+        if guidance is not None:
+            g_meas, g_loss, g_zeta = guidance
+            dit = self.dit
+            C, H, W, p = x.shape[1], x.shape[2], x.shape[3], dit.patch_size
+            g_T = (H // p) * (W // p)
+            if g_meas is not None:
+                g_m, g_mask = g_meas.operands(x)
+            g_D, g_q = (torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32) for _ in range(2))
+            g_L = torch.empty(B, device=x.device, dtype=torch.float64)
+            g_dtok = torch.empty(Bn * g_T, dit.config.patch_vec, device=x.device, dtype=torch.bfloat16)
+
+        def network_with_gradient(xs, sigma):
+            """network(xs, sigma) for a measurement-guided step's first evaluation, and the gradient of the network input under the
+            loss: returns ((network output, dup, None), dx fp32 [B or 2B, C, H, W]); q and L are left in g_q and g_L."""
+            c_noise = float(np.log(np.float32(sigma)) / 4)
+            dup = 1 if guided and samplers.is_guided(sigma, cfg, interval) else 0
+            Be = 2 * B if dup else B
+            eng = dit.engine
+            if cond_cache:
+                pt = patches if Be == Bn else patches[:B * g_T]
+                hip.check(L.md_edm_sampler_patchify(xs.data_ptr(), pt.data_ptr(), B, C, H, W, p, float(sigma), ec.sigma_data, dup, st),
+                          "md_edm_sampler_patchify")
+                t = torch.full((Be,), c_noise, device=x.device, dtype=torch.float32)
+                tape = eng.forward(None, t, None, cond=cond.narrow(Be), patches=pt, input_tape=True)
+                F = tape.out_tok
+                hip.check(L.md_edm_denoised_tok(xs.data_ptr(), F.data_ptr(), g_D.data_ptr(), B, C, H, W, p, float(cfg), dup, float(sigma),
+                                                ec.sigma_data, st), "md_edm_denoised_tok")
+            else:
+                hip.check(L.md_edm_sampler_input(xs.data_ptr(), net_in.data_ptr(), numel, float(sigma), ec.sigma_data, dup, st),
+                          "md_edm_sampler_input")
+                t = torch.full((1,), c_noise, device=x.device, dtype=torch.float32)
+                dit.refresh_shadow()
+                tape = eng.forward(net_in if Be == Bn else net_in[:B], t, dit._caption_input(y2 if Be == Bn else y), record_tape=True)
+                F = eng.sample_image(tape)
+                hip.check(L.md_edm_denoised(xs.data_ptr(), F.data_ptr(), g_D.data_ptr(), B, numel // B, float(cfg), dup, float(sigma),
+                                            ec.sigma_data, st), "md_edm_denoised")
+            if g_meas is not None:
+                hip.check(L.md_measure_residual(g_D.data_ptr(), g_m.data_ptr(), None if g_mask is None else g_mask.data_ptr(),
+                                                1 if g_mask is None else g_mask.shape[0], g_q.data_ptr(), g_L.data_ptr(), B, C, H, W,
+                                                g_meas.pool, st), "md_measure_residual")
+            else:
+                with torch.enable_grad():
+                    Dg = g_D.detach().clone().requires_grad_(True)
+                    loss = g_loss(Dg)
+                    gq, = torch.autograd.grad(loss.sum(), Dg)
+                g_q.copy_(gq)
+                g_L.copy_(loss.detach().reshape(B))
+            dtok = g_dtok if Be == Bn else g_dtok[:B * g_T]
+            hip.check(L.md_guide_cotangent_tok(g_q.data_ptr(), dtok.data_ptr(), B, C, H, W, p, float(cfg), dup, float(sigma), ec.sigma_data, st),
+                      "md_guide_cotangent_tok")
+            dx = eng.backward(tape, dtok, input_grads=("x",), param_grads=False).dx
+            return (F, dup, None), dx
+
+        def guide_apply(dx, dup, sigma):
+            """The correction of the step's result x_nxt along g = c_skip q + c_in (dx_c + dx_u), the coefficients of level sigma."""
+            hip.check(L.md_edm_guide_apply(x_nxt.data_ptr(), g_q.data_ptr(), dx.data_ptr(), g_L.data_ptr(), B, numel // B, dup, g_zeta,
+                                           float(sigma), ec.sigma_data, st), "md_edm_guide_apply")
 
         def network(xs, sigma):
             """(network output, dup, guide output) for state xs at noise level sigma: the fp32 image F, or (cond_cache) the bf16 token
@@ -618,12 +787,15 @@ class LatentDiffusion(nn.Module):
                         noise = noise.to(torch.float64).contiguous()
                         hip.check(L.md_edm_churn(x_cur.data_ptr(), noise.data_ptr(), x_cur.data_ptr(), numel,
                                                  float(np.sqrt(t_hat ** 2 - t_cur ** 2) * ec.S_noise), st), "md_edm_churn")
+                Fd, g_dx = (network(x_cur, t_hat), None) if guidance is None else network_with_gradient(x_cur, t_hat)
                 if heun:
-                    update(network(x_cur, t_hat), x_cur, t_hat, t_hat, t_next, 0)
+                    update(Fd, x_cur, t_hat, t_hat, t_next, 0)
                     if i < n - 1:
-                        update(network(x_nxt, t_next), x_nxt, t_next, t_hat, t_next, 1)
+                        update(network(x_nxt, t_next), x_nxt, t_next, t_hat, t_next, 1)      # not differentiated: no tape
                 else:
-                    solver_update(network(x_cur, t_hat), t_hat, coefs[i - i0])
+                    solver_update(Fd, t_hat, coefs[i - i0])
+                if g_dx is not None:
+                    guide_apply(g_dx, Fd[1], t_hat)
                 x_cur, x_nxt = x_nxt, x_cur
                 if rep < reps[i - i0] - 1:          # RePaint: the state this repetition produced goes back to level t_cur
                     noise = self.randn_like(x_cur).to(torch.float64).contiguous()
@@ -639,14 +811,17 @@ class LatentDiffusion(nn.Module):
                  cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
                  guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
                  guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
-                 apg_momentum: float = 0.0, **kwargs):
+                 apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, **kwargs):
         """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache, sampler,
         guidance_interval, guide and guide_captions: as in edm_sampler_loop (with a guide, guidance_scale is the autoguidance weight).
         init_latents, strength, inpaint_mask and resample: image-to-image and inpainting as in edm_sampler_loop; the seeded draw below is
         then the unit noise added to init_latents.  init_latents are latents already (VAE latents * latent_scale, the space of the
         trainer's image_latents): encoding an image into them stays the caller's vae.encode, a frozen third-party model.
         guidance_mode, guidance_rescale, apg_eta, apg_norm_threshold and apg_momentum: CFG rescale and adaptive projected guidance as in
-        edm_sampler_loop; they tame the over-saturation of plain guidance at this default guidance_scale."""
+        edm_sampler_loop; they tame the over-saturation of plain guidance at this default guidance_scale.
+        measurement, measurement_scale and guidance_loss: measurement-guided sampling as in edm_sampler_loop (the measurement lives in the
+        sampler's latent space, like init_latents)."""
+        samplers.check_measurement(None, measurement, measurement_scale, guidance_loss)
         samplers.check_guide(self.dit, guide, guide_captions)
         samplers.check_guidance(guidance_mode, guidance_scale, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum)
         samplers.check_edit(sampler, init_latents is not None, strength, inpaint_mask is not None, resample)
@@ -666,7 +841,8 @@ class LatentDiffusion(nn.Module):
                                         guidance_interval=guidance_interval, guide=guide, guide_captions=guide_captions,
                                         init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, resample=resample,
                                         guidance_mode=guidance_mode, guidance_rescale=guidance_rescale, apg_eta=apg_eta,
-                                        apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum)
+                                        apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, measurement=measurement,
+                                        measurement_scale=measurement_scale, guidance_loss=guidance_loss)
         if return_only_latents:
             return latents
         image = self.vae.decode((latents / self.latent_scale).to(DATA_TYPES[self.dtype])).sample

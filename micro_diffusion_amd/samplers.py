@@ -177,6 +177,67 @@ def guidance_coefficients(mode: str, moments, n: int, w: float, guidance_rescale
     return k, k * w1
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Measurement-guided sampling (Chung et al. 2023, "Diffusion Posterior Sampling").  At a step's first evaluation the
+# guided denoised prediction D(x_hat) gives a per-sample loss L_b -- ||m * (meas - A(D))||^2 for an inverse.LinearMeasurement, or a
+# caller's differentiable function --, and after the solver step x_next[b] -= scale / max(sqrt(L_b), GUIDE_TINY) * dL_b/dx_hat, the
+# gradient taken through the network.
+# ---------------------------------------------------------------------------------------------------------------------
+GUIDE_TINY = 1e-30                          # floor of sqrt(L_b): MD_GUIDE_TINY of the native library
+
+
+def _mask_shapes(B: int, H: int, W: int):
+    return [(H, W), (1, H, W), (B, H, W), (1, 1, H, W), (B, 1, H, W)]
+
+
+def check_measurement(shape, measurement=None, measurement_scale: float = 1.0, guidance_loss=None) -> bool:
+    """Refuse, before anything is launched or allocated, a guided-sampling request that is not defined; True when the run is guided.
+    shape: (B, C, H, W) of the sampler's state (None: only what does not depend on it is checked).  ValueError for a measurement_scale
+    that is not a finite number >= 0, for measurement and guidance_loss together, for a measurement_scale other than 1 with nothing
+    to scale, a guidance_loss that is not callable, and for a measurement (an object with meas, pool, mask: inverse.LinearMeasurement)
+    whose pool is no integer >= 1 dividing H and W, whose meas is not a floating tensor [B, C, H / pool, W / pool], or whose mask is not
+    [B or 1, 1, H / pool, W / pool] (or [B or 1, H / pool, W / pool], [H / pool, W / pool]), bool or float with values in [0, 1]."""
+    if not _finite_number(measurement_scale) or float(measurement_scale) < 0.0:
+        raise ValueError(f"measurement_scale must be a finite number >= 0, got {measurement_scale!r}")
+    if measurement is not None and guidance_loss is not None:
+        raise ValueError("measurement and guidance_loss are mutually exclusive: state the measurement's loss inside guidance_loss")
+    if measurement is None and guidance_loss is None:
+        if float(measurement_scale) != 1.0:
+            raise ValueError(f"measurement_scale={measurement_scale!r} has nothing to scale: it needs measurement or guidance_loss")
+        return False
+    if guidance_loss is not None:
+        if not callable(guidance_loss):
+            raise ValueError(f"guidance_loss must be callable (D [B, C, H, W] -> losses [B]), got {type(guidance_loss).__name__}")
+        return True
+    for name in ("meas", "pool", "mask"):
+        if not hasattr(measurement, name):
+            raise ValueError(f"measurement must be an inverse.LinearMeasurement (meas, pool, mask), got {type(measurement).__name__}")
+    s, meas, mask = measurement.pool, measurement.meas, measurement.mask
+    if isinstance(s, bool) or not isinstance(s, int) or s < 1:
+        raise ValueError(f"measurement.pool must be an integer >= 1, got {s!r}")
+    if not hasattr(meas, "shape") or not getattr(meas, "is_floating_point", lambda: False)():
+        raise ValueError("measurement.meas must be a floating-point tensor")
+    if mask is not None and not hasattr(mask, "shape"):
+        raise ValueError("measurement.mask must be a tensor or None")
+    if shape is None:
+        return True
+    B, C, H, W = (int(v) for v in shape)
+    if H % s or W % s:
+        raise ValueError(f"measurement.pool={s} does not divide the latent grid {H} x {W}")
+    Hs, Ws = H // s, W // s
+    if tuple(meas.shape) != (B, C, Hs, Ws):
+        raise ValueError(f"measurement.meas has shape {tuple(meas.shape)}: expected {(B, C, Hs, Ws)} (the pooled grid of {(B, C, H, W)})")
+    if mask is not None:
+        if tuple(mask.shape) not in _mask_shapes(B, Hs, Ws):
+            raise ValueError(f"measurement.mask has shape {tuple(mask.shape)}: expected [{B} or 1, 1, {Hs}, {Ws}], [{B} or 1, {Hs}, {Ws}] or "
+                             f"[{Hs}, {Ws}]")
+        import torch
+        if mask.dtype != torch.bool:
+            if not mask.is_floating_point() or not bool(((mask >= 0) & (mask <= 1)).all()):
+                raise ValueError("measurement.mask must be bool or hold float values in [0, 1] (1 = measured, 0 = ignored)")
+    return True
+
+
 GUIDE_CAPTIONS = ("same", "null")           # what an autoguidance guide is conditioned on: the captions, or zeroed captions
 GUIDE_GEOMETRY = ("in_channels", "patch_size", "input_size", "caption_channels")
 
