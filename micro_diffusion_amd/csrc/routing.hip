@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void moe_softmax_kernel(const float* logits, f
     const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
     float v[16];
-    float mx = -1e30f;
+    float mx = -INFINITY;  // the row's own maximum: a start of -1e30f lies ABOVE bf16(-1e30), and an all-sentinel row became 0 * inf
     for (int e = 0; e < E; ++e) {
         v[e] = bf2f(f2bf(logits[m * ld + e]));  // the gate Linear runs under bf16 autocast: logits are bf16
         mx = fmaxf(mx, v[e]);

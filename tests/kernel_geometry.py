@@ -1,4 +1,4 @@
-"""The shapes of tests/test_kernel_geometry_gpu.py and the launch geometry each one is meant to reach.
+"""The shapes of tests/test_kernel_geometry_gpu.py and tests/test_moe_geometry_gpu.py and the launch geometry each one is meant to reach.
 
 Each case names the heuristic branch it exists for.  The GPU tests run the shapes; tests/test_kernel_geometry_cpu.py reads the
 heuristic constants out of the kernel sources and checks, through the functions below, that every shape still lands in the branch
@@ -88,3 +88,69 @@ EDM_B, EDM_C, EDM_HW, EDM_P = 130, 4, 64, 2      # 64 x 64 latents (res 512): T 
 
 GateBwd = namedtuple("GateBwd", "id B rps C rpb")
 GATE_BWD = [GateBwd(f"nch{nch(C)}-C{C}-rps{rps}-rpb64", 128, rps, C, 64) for C in (256, 1024, 2048) for rps in (64, 77)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- MoE routing
+# The cases of tests/test_moe_geometry_gpu.py (csrc/routing.hip).
+def wave_grid_passes(rows, K):
+    """wgrid: grid-stride passes of the wave-per-row kernels over `rows` rows (4 waves per workgroup, at most wgrid_max workgroups),
+    and the rows of the last pass."""
+    waves = 4 * max(1, min(K["wgrid_max"], -(-rows // 4)))
+    return -(-rows // waves), rows - (-(-rows // waves) - 1) * waves
+
+
+def col_trips(C):
+    """Trips of the `for (c = lane * 8; c < C; c += 512)` loops taken by lane 0 (the most any lane takes)."""
+    return -(-C // 512)
+
+
+def emax(E):
+    """The template instance of moe_combine_kernel / moe_scatter_sum_kernel the launchers pick."""
+    return 8 if E <= 8 else 16
+
+
+def compact_chunks(B, k, K):
+    """md_moe_compact_kept: chunks of compact_chunk list entries per expert (gridDim.x; the chunk-prefix loop strides by 256)."""
+    return -(-B * k // K["compact_chunk"])
+
+
+MoeRoute = namedtuple("MoeRoute", "id B S E k ld special")         # special: sentinel / saturated rows written over the first tokens
+MOE_ROUTE = [
+    MoeRoute("S100-E4-k25-sentinel-rows", 3, 100, 4, 25, 8, True),
+    MoeRoute("S257-E3-k1", 2, 257, 3, 1, 8, False),
+    MoeRoute("S300-E16-k-is-S", 2, 300, 16, 300, 16, False),
+    MoeRoute("E1", 2, 64, 1, 7, 8, False),
+    MoeRoute("S130-E9-odd", 2, 130, 9, 29, 16, False),
+    MoeRoute("ld24", 2, 64, 8, 16, 24, False),
+    MoeRoute("S16384-lds-64KiB", 1, 16384, 2, 4096, 8, False),
+]
+
+# combine / combine backward / dispatch backward on synthetic tables; ldp / ldo: row lengths of probs and dlogits
+MoeTable = namedtuple("MoeTable", "id B S E k C ldp ldo")
+MOE_SECOND_PASS_M = 5 * 6557                                       # 32768 + 17 token rows
+MOE_TABLES = [
+    MoeTable("one-lane-E8-C8", 2, 24, 8, 6, 8, 8, 8),
+    MoeTable("trips2-one-lane-active-E8-C520", 2, 24, 8, 6, 520, 16, 16),
+    MoeTable("trips3-emax16-E12-C1032", 2, 24, 12, 5, 1032, 24, 16),
+    MoeTable("emax16-E16-C128", 2, 24, 16, 3, 128, 16, 16),
+    MoeTable("odd-E5-C128", 2, 23, 5, 9, 128, 8, 8),
+    MoeTable("second-pass-E8-C8", 5, 6557, 8, 1639, 8, 8, 8),
+    MoeTable("second-pass-emax16-E12-C8", 5, 6557, 12, 1092, 8, 24, 16),
+]
+MOE_BWD_SECOND_PASS = 32768 + 17                                   # R of md_moe_combine_bwd, cap of md_moe_combine_bwd_compact (C = 8)
+
+MoeCompact = namedtuple("MoeCompact", "id B S E k len_keep dead")  # dead: an expert all of whose tokens are dropped, or None
+MOE_COMPACT = [
+    MoeCompact("E16", 3, 32, 16, 8, 8, None),
+    MoeCompact("E5-one-expert-keeps-nothing", 3, 32, 5, 8, 8, 2),
+    MoeCompact("Bk2048-exact-chunks", 4, 1024, 2, 512, 256, None),
+    MoeCompact("chunk-prefix-second-trip-E1", 17, 16384, 1, 16384, 4096, None),
+]
+
+MoeMask = namedtuple("MoeMask", "id B T len_keep")
+MOE_MASK = [
+    MoeMask("T100-keep25", 3, 100, 25),
+    MoeMask("T257-keep1", 2, 257, 1),
+    MoeMask("T300-keep-all", 2, 300, 300),
+    MoeMask("T16384-lds-64KiB", 1, 16384, 4096),
+]

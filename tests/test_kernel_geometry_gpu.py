@@ -1,6 +1,7 @@
-"""The norm, elementwise, EDM and routing kernels at the shapes where their launch heuristics take the production branch
-(tests/kernel_geometry.py names the branch of every case), each element against an fp64 reference built from the same bf16 /
-fp16 / fp32 inputs.
+"""The norm, elementwise, EDM and row gather / scatter kernels at the shapes where their launch heuristics take the production
+branch (tests/kernel_geometry.py names the branch of every case), each element against an fp64 reference built from the same bf16 /
+fp16 / fp32 inputs.  The MoE routing kernels (mask ranking, softmax / top-k, combine, the backward kernels, compaction) have their own
+file with the same helpers: tests/test_moe_geometry_gpu.py.
 
 How outputs are compared (helpers below; U = 2^-24 is the fp32 unit roundoff, ulp(r) the bf16 spacing at |r|):
   * exact      -- the kernel does one correctly rounded fp32 operation (or a copy) and nothing else: the bits must equal torch's

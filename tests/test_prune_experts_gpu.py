@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import microdit_ref as orc
+from tests.moe_ref import compact as _compact_ref
 
 pytestmark = pytest.mark.gpu
 I32, F32, BF16 = torch.int32, torch.float32, torch.bfloat16
@@ -44,25 +45,6 @@ def _compact(hip, rowidx, gval, ids_restore, Tk, B, S, E, k):
     hip.check(hip.lib().md_moe_compact_kept(rowidx.data_ptr(), gval.data_ptr(), ids_restore.data_ptr(), Tk, B, S, E, k, rowidx_c.data_ptr(),
                                             gval_c.data_ptr(), count.data_ptr(), slot_c.data_ptr(), ws.data_ptr(), ws.numel(), _st()), "compact")
     torch.cuda.synchronize()
-    return rowidx_c, gval_c, count, slot_c
-
-
-def _compact_ref(rowidx, gval, ids_restore, Tk, B, S, E, k):
-    """List order = the order of the expert's routed list (sample-major, then rank); pads: the expert's first routed row, gate 0."""
-    keep = ids_restore.view(-1) < Tk
-    rowidx_c = torch.empty_like(rowidx)
-    gval_c = torch.zeros_like(gval)
-    count = torch.empty(E, device="cuda", dtype=I32)
-    slot_c = torch.full((B * S, E), -1, device="cuda", dtype=I32)
-    for e in range(E):
-        toks = rowidx[e].long()
-        kp = keep[toks]
-        c = int(kp.sum())
-        rowidx_c[e, :c] = rowidx[e][kp]
-        rowidx_c[e, c:] = rowidx[e, 0]
-        gval_c[e, :c] = gval[e][kp]
-        slot_c[toks[kp], e] = torch.arange(c, device="cuda", dtype=I32)
-        count[e] = c
     return rowidx_c, gval_c, count, slot_c
 
 
