@@ -74,7 +74,10 @@ typedef struct md_gemm_args {
     int64_t M, N, K;
     int64_t lda, ldb, ldc, ldc2, ldr, ldg, ldaux;
     int64_t sA, sB, sC, sC2, sBias, sAux; /* batch strides (elements) */
-    int64_t sSplit;                       /* STORE_F32 with ksplit > 1: split s writes its partial at C + s * sSplit */
+    int64_t sSplit;                       /* STORE_F32 with ksplit > 1: split s writes its partial at C + s * sSplit; ignored by every
+                                             other mode (ATOMIC_F32 splits all add into C).  K is cut in whole 64-wide k-tiles,
+                                             ceil(tiles / ksplit) per split: the last split may be shorter, and a split left without
+                                             work (K = 64, ksplit = 3) still WRITES its slice (alpha * 0 + bias: zeros) */
     int64_t rows_per_sample;
     int32_t batch;
     int32_t ksplit;

@@ -642,6 +642,9 @@ extern "C" int md_gemm_bf16(const md_gemm_args* a_in, hipStream_t stream) {
     if (a->C2 && a->ldc2 % 8) return MD_BAD_ARG;
     // split-K: either atomics into C, or every split stores its own fp32 slice (C + split * sSplit) for md_splitk_reduce
     if (a->ksplit > 1 && !(a->mode == MD_EPI_ATOMIC_F32 || (a->mode == MD_EPI_STORE_F32 && a->sSplit > 0))) return MD_BAD_ARG;
+    // sSplit belongs to the STORE_F32 slices alone: the atomic splits all add into C itself, whatever the caller left in the field
+    // (the shared epilogue forms C + split * sSplit for every fp32 mode)
+    if (a->mode != MD_EPI_STORE_F32) a_copy.sSplit = 0;
     if (a->mode == MD_EPI_RESIDUAL && (!a->res || (a->gate && a->rows_per_sample <= 0))) return MD_BAD_ARG;
     if (a->mode == MD_EPI_DACT && !a->aux) return MD_BAD_ARG;
     if (a->mode < MD_EPI_STORE_BF16 || a->mode > MD_EPI_SWIGLU_BWD) return MD_BAD_ARG;
