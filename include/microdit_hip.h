@@ -769,6 +769,29 @@ int md_guide_cotangent_tok(const float* q, void* dtok_bf16, int64_t B, int32_t C
 int md_edm_guide_apply(double* x_next, const float* q, const float* dx, const double* L, int64_t B, int64_t per_sample, int32_t has_uncond,
                        double zeta, double t_in, float sigma_data, hipStream_t stream);
 
+/* ---- step cache (symbols added, MD_ABI_VERSION stays 6): the contribution of a run of blocks to the residual stream,
+ * kept from one sampler evaluation and added back in the next (Delta-DiT / FORA / TeaCache), and the distance probe of the adaptive policy.
+ * md_residual_delta: delta = bf16(f32(x_out) - f32(x_in)) over n bf16 elements, one rounding.  16-byte work items in a grid-stride loop
+ *   of min(ceil(n / 8 / 256), MD_STEP_DELTA_MAX_BLOCKS) workgroups.  The apply step is md_add_bf16(x_in', delta, x).
+ *   MD_BAD_ARG, nothing launched: a null pointer, n <= 0, n % 8 != 0, a pointer that is not 16-byte aligned, delta overlapping an input.
+ * md_step_probe: x, ref bf16 [B, per_sample].  One pass: workgroup (g, b) forms sum |f32(x) - f32(ref)| and sum |f32(ref)| over the 16-byte
+ *   chunks [g * MD_STEP_PROBE_CHUNKS, (g + 1) * MD_STEP_PROBE_CHUNKS) of sample b in fp64 (per thread in ascending order, a fixed shuffle
+ *   tree, the waves in ascending order) and stores the pair into ws; every chunk of ref is overwritten with x's by the thread that
+ *   read it.  No workgroup straddles two samples.  ws: at least md_step_probe_ws_doubles(B, per_sample) doubles: a header of two (the
+ *   workgroups per sample, which the finish reads), then [B][workgroups per sample][2]; written before it is read.
+ *   MD_BAD_ARG, nothing launched: a null pointer, B < 1 or > 65535, per_sample < 8 or % 8 != 0, x or ref not 16-byte aligned, x and ref
+ *   overlapping.
+ * md_step_probe_finish: one workgroup; one thread per sample adds its partials in ascending order: rel[b] = f32(sum |x - ref| / sum |ref|),
+ *   +inf when sum |ref| is 0 (a zero reference is never close), NaN when a sum is NaN; rel_max[0] = max_b rel[b] (NaN if any is).
+ *   No atomics; two calls on the same operands give identical bits.  B as in the md_step_probe launch that wrote ws.
+ * Nothing here synchronises, allocates or returns to the host. */
+#define MD_STEP_DELTA_MAX_BLOCKS 2048 /* 256-thread workgroups of md_residual_delta: eight waves on every SIMD of the chip, once */
+#define MD_STEP_PROBE_CHUNKS 1024     /* 16-byte chunks one md_step_probe workgroup reads of each operand (16 KB) */
+int md_residual_delta(const void* x_out, const void* x_in, void* delta, int64_t n, hipStream_t stream);
+int md_step_probe_ws_doubles(int64_t B, int64_t per_sample, int64_t* out);
+int md_step_probe(const void* x, void* ref, int64_t B, int64_t per_sample, double* ws, hipStream_t stream);
+int md_step_probe_finish(const double* ws, int64_t B, float* rel, float* rel_max, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

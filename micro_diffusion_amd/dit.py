@@ -296,8 +296,10 @@ class DiT(nn.Module):
         self.refresh_shadow()
         return self._engine.encode_condition(self._caption_input(y))
 
-    def forward_without_cfg(self, x, t, y, mask_ratio: float = 0, mask_noise: Optional[torch.Tensor] = None, cond=None, **kwargs):
+    def forward_without_cfg(self, x, t, y, mask_ratio: float = 0, mask_noise: Optional[torch.Tensor] = None, cond=None, step_cache=None,
+                            reuse=False, **kwargs):
         """cond: an encode_condition(y) result for these captions (y is then not read).
+        step_cache, reuse: an engine.ResidualCache and the decision to reuse it, as in DiTEngine.forward; inference-only.
         Gradients: with grad mode on, the output carries a graph when any parameter or any of x, t, y requires grad.
         x.grad / t.grad / y.grad come back in each input's own shape and dtype (a one-element t gets the batch sum, an f16 y an f16
         gradient).  With every parameter frozen the backward is the engine's dgrad-only one: no p.grad is attached, the flat gradient
@@ -321,9 +323,13 @@ class DiT(nn.Module):
             if cond is not None:
                 raise RuntimeError("cond is inference-only: call under torch.no_grad() (or with frozen parameters and inputs that "
                                    "do not require grad)")
+            if step_cache is not None:
+                raise RuntimeError("step_cache is inference-only: call under torch.no_grad() (or with frozen parameters and inputs that "
+                                   "do not require grad)")
             sample, mask = _DiTFunction.apply(self, self._grad_anchor, xin, tin, yin, float(mask_ratio), mask_noise)
         else:
-            tape = self._engine.forward(xin, tin, yin, mask_ratio=float(mask_ratio), mask_noise=mask_noise, cond=cond)
+            tape = self._engine.forward(xin, tin, yin, mask_ratio=float(mask_ratio), mask_noise=mask_noise, cond=cond,
+                                        step_cache=step_cache, reuse=reuse)
             sample, mask = self._engine.sample_image(tape), tape.mask
         return {"sample": sample, "mask": mask}
 

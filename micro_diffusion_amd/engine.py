@@ -121,6 +121,82 @@ class Conditioning:
         return Conditioning(B, self.Lc, self.head_major, self.version, self.pooled[:B], kv)
 
 
+class ResidualCache:
+    """State of the step cache: what backbone blocks [lo, hi) added to the residual stream in the last full evaluation,
+    handed to `DiTEngine.forward(..., step_cache=, reuse=)`.
+      delta   [B*T, D] bf16 = bf16(output of block hi - 1 - input of block lo) (md_residual_delta), allocated on first use
+      ref     [B*T, D] bf16, only with probe=True: the backbone's input of the previous evaluation (md_step_probe keeps it current)
+      lo, hi  the block range inside the engine's backbone; blocks=None: all of it (resolved by the first forward)
+      B, T, version   the batch, token count and DiTEngine.weights_version `delta` was filled at (None: empty)
+    Each buffer takes 2 * B * T * D bytes.  One cache serves one batch shape at a time: a full evaluation at another shape refills it."""
+
+    def __init__(self, blocks=None, probe: bool = False):
+        if blocks is not None:
+            lo, hi = blocks
+            if any(isinstance(v, bool) or not isinstance(v, int) for v in (lo, hi)) or not 0 <= lo < hi:
+                raise ValueError(f"blocks must be (lo, hi) with 0 <= lo < hi, backbone block indices, got {blocks!r}")
+            blocks = (lo, hi)
+        self.blocks, self.with_probe = blocks, bool(probe)
+        self.lo = self.hi = None
+        self.delta = self.ref = None
+        self.B = self.T = self.version = None
+        self._ref_key = None
+        self._ws = self._rel = self._rel_max = None
+
+    def reset(self) -> None:
+        """Forget the filled state and the probe reference (the buffers stay allocated): the start of a sampling run."""
+        self.B = self.T = self.version = None
+        self._ref_key = None
+
+    def valid(self, B: int, T: int, version) -> bool:
+        return self.delta is not None and (self.B, self.T, self.version) == (B, T, version)
+
+    def resolve(self, n_backbone: int):
+        """(lo, hi) inside a backbone of n_backbone blocks."""
+        lo, hi = (0, n_backbone) if self.blocks is None else self.blocks
+        if not 0 <= lo < hi <= n_backbone:
+            raise ValueError(f"step cache: blocks [{lo}, {hi}) are outside the backbone's {n_backbone} blocks")
+        self.lo, self.hi = lo, hi
+        return lo, hi
+
+    def store(self, x_out: torch.Tensor, x_in: torch.Tensor, B: int, T: int, version) -> None:
+        """delta <- bf16(x_out - x_in): one launch."""
+        if self.delta is None or self.delta.shape != x_in.shape or self.delta.device != x_in.device:
+            self.delta = torch.empty_like(x_in)
+        hip.check(hip.lib().md_residual_delta(x_out.data_ptr(), x_in.data_ptr(), self.delta.data_ptr(), x_in.numel(),
+                                              torch.cuda.current_stream().cuda_stream), "md_residual_delta")
+        self.B, self.T, self.version = B, T, version
+
+    def probe(self, x: torch.Tensor, B: int, version=None):
+        """The relative L1 distance of x [B*T, D] (the backbone's input, B samples) from the previous evaluation's, as the device scalar
+        rel_max = max_b sum |x_b - ref_b| / sum |ref_b| (fp32 [1]), and ref <- x: two launches, nothing returns
+        to the host.  The first probe after a reset, or at another shape or weight version, only fills ref and returns None."""
+        key = (tuple(x.shape), B, version)
+        if self.ref is None or self.ref.shape != x.shape or self.ref.device != x.device:
+            self.ref = torch.empty_like(x)
+            self._ref_key = None
+        if self._ref_key != key:
+            self.ref.copy_(x)
+            self._ref_key = key
+            return None
+        L, st = hip.lib(), torch.cuda.current_stream().cuda_stream
+        per = x.numel() // B
+        need = ctypes.c_int64(0)
+        hip.check(L.md_step_probe_ws_doubles(B, per, byref(need)), "md_step_probe_ws_doubles")
+        if self._ws is None or self._ws.numel() < need.value or self._ws.device != x.device:
+            self._ws = torch.empty(need.value, device=x.device, dtype=torch.float64)
+        if self._rel is None or self._rel.numel() != B or self._rel.device != x.device:
+            self._rel = torch.empty(B, device=x.device, dtype=F32)
+            self._rel_max = torch.empty(1, device=x.device, dtype=F32)
+        hip.check(L.md_step_probe(x.data_ptr(), self.ref.data_ptr(), B, per, self._ws.data_ptr(), st), "md_step_probe")
+        hip.check(L.md_step_probe_finish(self._ws.data_ptr(), B, self._rel.data_ptr(), self._rel_max.data_ptr(), st), "md_step_probe_finish")
+        return self._rel_max
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.delta, self.ref) if t is not None)
+
+
 def _p(t):
     return None if t is None else t.data_ptr()
 
@@ -1185,7 +1261,8 @@ class DiTEngine:
     def forward(self, x_img: Optional[torch.Tensor], t_in: torch.Tensor, y: Optional[torch.Tensor] = None, *, mask_ratio: float = 0.0,
                 mask_noise: Optional[torch.Tensor] = None, in_scale: Optional[torch.Tensor] = None,
                 y_rowscale: Optional[torch.Tensor] = None, record_tape: bool = False, arena: bool = False,
-                cond: Optional[Conditioning] = None, patches: Optional[torch.Tensor] = None, input_tape: bool = False) -> Tape:
+                cond: Optional[Conditioning] = None, patches: Optional[torch.Tensor] = None, input_tape: bool = False,
+                step_cache: Optional[ResidualCache] = None, reuse=False) -> Tape:
         """x_img f32 [B,C,H,W] (multiplied by in_scale[b] if given), t_in f32 [B], y f16|f32 [B,(1,)L,Dc]
         (rows multiplied by y_rowscale[b] if given).  Returns the tape; tape.out_tok is the network output for the
         kept tokens, bf16 [B*Tk, p*p*C].
@@ -1199,8 +1276,23 @@ class DiTEngine:
         None: the latent grid is then the model's input_size).  cond and patches are inference-only.
         input_tape (with cond and / or patches): keep what a backward to the network input alone needs -- every block's
         activations and references to the cached K / V the blocks read; the conditioning is frozen.  backward() on such a tape takes
-        input_grads=("x",), param_grads=False and nothing else."""
+        input_grads=("x",), param_grads=False and nothing else.
+        step_cache (a ResidualCache; inference-only, with or without cond / patches): with reuse false the pass is the
+        one without the argument plus one md_residual_delta launch behind backbone block hi - 1, which leaves what blocks [lo, hi) added
+        to the residual stream in the cache.  With reuse true those blocks are not launched (nor announced to before_segment): their
+        input plus the cached delta (md_add_bf16) stands in for their output; the cache must be valid for this batch, token count and
+        weight version.  reuse may be a callable: it is called once, between the mixer and the backbone, with the device scalar
+        step_cache.probe() measured on the backbone's input (None without probe=True, or when the probe only filled its reference),
+        and returns the decision.  The probe runs in every evaluation of a cache built with probe=True, before that point."""
         cfg = self.cfg
+        if step_cache is not None:
+            if record_tape or arena or input_tape or mask_ratio > 0:
+                raise RuntimeError("step_cache is inference-only: it cannot be combined with record_tape, arena, input_tape or mask_ratio > 0")
+            if not self.backbone:
+                raise ValueError("step_cache: the model has no backbone blocks to cache")
+            step_cache.resolve(len(self.backbone))
+        elif reuse is not False:
+            raise ValueError("reuse needs a step_cache")
         if cond is not None or patches is not None:
             if record_tape or arena or mask_ratio > 0:
                 raise RuntimeError("cond / patches are inference-only: they cannot be combined with record_tape, arena or mask_ratio > 0")
@@ -1215,6 +1307,8 @@ class DiTEngine:
             assert x_img.dtype == F32 and x_img.is_contiguous()
             B, H, W = x_img.shape[0], x_img.shape[-2], x_img.shape[-1]
         assert (H // cfg.patch_size) * (W // cfg.patch_size) == cfg.tokens, "input resolution does not match the model's position table"
+        if step_cache is not None and reuse is True:            # (a callable decides later: _forward checks what it returns)
+            self._check_reuse(step_cache, B, cfg.tokens)
         if cond is not None:
             if cond.B != B:
                 raise RuntimeError(f"conditioning mismatch: encoded for batch {cond.B}, the input has batch {B}")
@@ -1242,7 +1336,7 @@ class DiTEngine:
             self._arena = self._tape_arena
         ok = False
         try:
-            tp = self._forward(x_img, t_in, y, mask_ratio, mask_noise, in_scale, y_rowscale, cond, patches, B, H, W, Lc)
+            tp = self._forward(x_img, t_in, y, mask_ratio, mask_noise, in_scale, y_rowscale, cond, patches, B, H, W, Lc, step_cache, reuse)
             tp.input_tape = bool(input_tape)
             ok = True
             return tp
@@ -1250,6 +1344,13 @@ class DiTEngine:
             if grad_pass:
                 self._tape_arena.end(ok)
             self._arena = None
+
+    def _check_reuse(self, sc: ResidualCache, B: int, T: int) -> None:
+        if not sc.valid(B, T, self.weights_version):
+            if sc.version is None:
+                raise RuntimeError("step cache mismatch: reuse=True on an empty cache (run a full evaluation with step_cache= first)")
+            raise RuntimeError(f"step cache mismatch: filled at batch {sc.B}, {sc.T} tokens, weight version {sc.version}; this evaluation "
+                               f"has batch {B}, {T} tokens, weight version {self.weights_version}")
 
     def _caption_fwd(self, y, y_rowscale, B, Lc, tp) -> torch.Tensor:
         """Caption projection + caption block (dit.py:482-483) and the token mean the pooled MLP reads: everything that depends on
@@ -1326,7 +1427,7 @@ class DiTEngine:
                 kv[bp.name] = (k, self._k_norm_fwd(k, Mc, bp.xattn_hidden, Lc)[1])
         return Conditioning(B, Lc, self.qk_head_major, self.weights_version, pooled, kv)
 
-    def _forward(self, x_img, t_in, y, mask_ratio, mask_noise, in_scale, y_rowscale, cond, patches, B, H, W, Lc) -> Tape:
+    def _forward(self, x_img, t_in, y, mask_ratio, mask_noise, in_scale, y_rowscale, cond, patches, B, H, W, Lc, sc=None, reuse=False) -> Tape:
         cfg, L, st = self.cfg, self.L, self._st()
         C, p = cfg.in_channels, cfg.patch_size
         T, D, Dm = (H // p) * (W // p), cfg.dim, cfg.patch_mixer_dim
@@ -1440,13 +1541,34 @@ class DiTEngine:
             x = xb
         tp.blocks = []
         tp.disperse = None
+        # ---- step cache: the probe on the backbone's input, then the decision; Tk == T (mask_ratio > 0 is refused)
+        lo = hi = -1
+        if sc is not None:
+            lo, hi = sc.lo, sc.hi
+            rel_max = sc.probe(x, B, self.weights_version) if sc.with_probe else None
+            if callable(reuse):
+                reuse = bool(reuse(rel_max))
+                if reuse:
+                    self._check_reuse(sc, B, T)
+        tp.reused = bool(sc is not None and reuse)
+        x_lo = None
         for i, bp in enumerate(self.backbone):
+            if lo <= i < hi and reuse:
+                if i == lo:                         # blocks [lo, hi) are not launched: their input plus what they added last time
+                    xr = self.empty(B * Tk, D)
+                    hip.check(L.md_add_bf16(x.data_ptr(), sc.delta.data_ptr(), xr.data_ptr(), B * Tk * D, st), "add")
+                    x = xr
+                continue
+            if i == lo:
+                x_lo = x
             seg(bp.name)
             x, bt = self._block_fwd(bp, x, y2, B, Tk, Lc, gc, mod_all, kv=cond.kv[bp.name] if cond is not None else None)
             if self._record:
                 tp.blocks.append(bt)
             if self._disperse_on and i == self.disperse[0] and B > 1:       # B = 1: L = 0 and the gradient is 0 -- nothing to launch
                 tp.disperse = self._disperse_fwd(x, B, Tk * D)
+            if i == hi - 1:
+                sc.store(x, x_lo, B, T, self.weights_version)
         # ---- final layer, dit.py:513
         seg("final_layer")
         tp.xlast = x

@@ -301,6 +301,14 @@ _sig("md_measure_residual", P, P, P, I32, P, P, I64, I32, I32, I32, I32, P)
 _sig("md_guide_cotangent_tok", P, P, I64, I32, I32, I32, I32, F32, I32, F64, F32, P)
 _sig("md_edm_guide_apply", P, P, P, P, I64, I64, I32, F64, F64, F32, P)
 GUIDE_TINY = 1e-30              # MD_GUIDE_TINY
+# step cache: the residual contribution of a run of blocks (the apply step is md_add_bf16), and the two-stage fp64
+# distance probe of the adaptive policy (md_step_probe_ws_doubles sizes its workspace)
+_sig("md_residual_delta", P, P, P, I64, P)
+_sig("md_step_probe_ws_doubles", I64, I64, POINTER(c_int64))
+_sig("md_step_probe", P, P, I64, I64, P, P)
+_sig("md_step_probe_finish", P, I64, P, P, P)
+STEP_DELTA_MAX_BLOCKS = 2048    # MD_STEP_DELTA_MAX_BLOCKS
+STEP_PROBE_CHUNKS = 1024        # MD_STEP_PROBE_CHUNKS
 DISPERSE_MAX_B = 4096    # MD_DISPERSE_MAX_B
 LORA_RANKS = (4, 8, 16, 32, 64)
 EMA_MAX_PROFILES = 4     # MD_EMA_MAX_PROFILES

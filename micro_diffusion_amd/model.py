@@ -271,7 +271,8 @@ class LatentDiffusion(nn.Module):
                          cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
                          guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
                          guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
-                         apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, **kwargs):
+                         apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, step_cache=None,
+                         **kwargs):
         """EDM sampler, fp64 state (model.py:231-297).  `fused` (None = whenever possible) selects the loop whose per-step arithmetic
         runs in fused HIP kernels; False keeps the reference's tensor-op formulation (generic forward functions).
         `cond_cache` (None = the environment variable MD_SAMPLER_CACHE, default off): encode the captions once for the whole run
@@ -314,9 +315,17 @@ class LatentDiffusion(nn.Module):
         x_next[b] -= measurement_scale / max(sqrt(L_b), samplers.GUIDE_TINY) * dL_b/dx_hat, the gradient taken through the network, before
         the RePaint re-noise.  The network is frozen for the run (requires_grad is restored afterwards, no .grad is written).  Composes with
         the solvers, churn, guidance_interval, cond_cache, init_latents / inpaint_mask / resample; not done: with `guide`, with a
-        guidance_mode other than "cfg", with extra forward arguments."""
+        guidance_mode other than "cfg", with extra forward arguments.
+        `step_cache`: a step_cache.StepCache.  Evaluations its policy does not declare full skip the backbone blocks and
+        add back what those blocks contributed in the last full evaluation; the embeddings, the patch mixer and the final layer always
+        run.  Evaluations are counted from the run's own schedule (heun: two per step, resample repetitions included); the first and the
+        last are always full, and so is the first at another network batch (the edge of a guidance_interval).  It needs the fused loop
+        and composes with the solvers, churn, guidance_interval, the guidance modes, cond_cache and init_latents / inpaint_mask /
+        resample; not defined with `guide`, `measurement` or `guidance_loss` (ValueError).  step_cache.stats describes the run.  None:
+        the launches and bits of a run without the argument."""
         ec = self.edm_config
         samplers.check_sampler(sampler, ec.S_churn)
+        caching = samplers.check_step_cache(step_cache, guide, measurement, guidance_loss)
         guided_by = samplers.check_measurement(tuple(x.shape), measurement, measurement_scale, guidance_loss)
         if guided_by:
             for bad, what in ((guide is not None, "a guide network (autoguidance)"), (guidance_mode != "cfg", f"guidance_mode={guidance_mode!r}"),
@@ -337,12 +346,15 @@ class LatentDiffusion(nn.Module):
         cond_cache = sampler_cache_enabled(cond_cache)
         if cond_cache and (fused is False or not can_fuse):
             raise RuntimeError("cond_cache needs the fused sampler: no extra forward arguments, CUDA tensors")
+        if caching and (fused is False or not can_fuse):
+            raise ValueError("step_cache needs the fused sampler: no extra forward arguments, CUDA tensors")
         if fused is None:
             fused = can_fuse
         if fused:
             assert can_fuse, "the fused sampler needs CUDA tensors and no extra forward arguments"
             if not guided_by:
-                return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, guide, guide_captions == "null", edit, gmode)
+                return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, guide, guide_captions == "null", edit, gmode,
+                                               step_cache=step_cache)
             guidance = (measurement, guidance_loss, float(measurement_scale))
             with self._frozen_network():
                 return self._edm_sampler_fused(x, y, steps, cfg, cond_cache, sampler, interval, None, False, edit, None, guidance)
@@ -542,7 +554,7 @@ class LatentDiffusion(nn.Module):
 
     @torch.no_grad()
     def _edm_sampler_fused(self, x, y, steps: Optional[int], cfg: float, cond_cache: bool = False, sampler: str = "heun", interval=None,
-                           guide=None, guide_null: bool = False, edit=None, gmode=None, guidance=None):
+                           guide=None, guide_null: bool = False, edit=None, gmode=None, guidance=None, step_cache=None):
         """The same loops with everything around the network evaluations in fused HIP kernels: md_edm_sampler_input (c_in scaling +
         guidance batch doubling) and md_edm_heun_update (guidance combine + preconditioning + fp64 Euler / Heun update) or, for
         euler / dpmpp_2m, md_edm_solver_update (the same with the linear-multistep update of samplers.solver_coefficients).
@@ -569,7 +581,10 @@ class LatentDiffusion(nn.Module):
         md_measure_residual -> q = dL/dD and L (or the callable under torch.enable_grad(), torch autograd supplying q),
         md_guide_cotangent_tok -> the bf16 cotangent of both halves of the output, engine.backward(("x",), param_grads=False) -> the
         gradient of the network input, which stops at the image; the tape is dropped, the step's usual update runs (Heun's second
-        evaluation without a tape) and md_edm_guide_apply corrects its result in place.  None: none of it."""
+        evaluation without a tape) and md_edm_guide_apply corrects its result in place.  None: none of it.
+        step_cache: a step_cache.StepCache (no guide, no guidance): it is reset for the run's evaluation count, and every
+        network() call hands the engine its ResidualCache and a decision callback (StepCache.engine_args) -- through engine.forward with
+        cond_cache, through dit.forward_without_cfg without.  None: none of it."""
         ec, L, st = self.edm_config, hip.lib(), torch.cuda.current_stream().cuda_stream
         n = ec.num_steps if steps is None else steps
         idx = torch.arange(n, dtype=torch.float64)
@@ -677,6 +692,10 @@ class LatentDiffusion(nn.Module):
             hip.check(L.md_edm_guide_apply(x_nxt.data_ptr(), g_q.data_ptr(), dx.data_ptr(), g_L.data_ptr(), B, numel // B, dup, g_zeta,
                                            float(sigma), ec.sigma_data, st), "md_edm_guide_apply")
 
+        def sc_args(Be):
+            """The step-cache arguments of the main network's next evaluation at batch Be (none without a step cache)."""
+            return {} if step_cache is None else step_cache.engine_args(self.dit.engine, Be)
+
         def network(xs, sigma):
             """(network output, dup, guide output) for state xs at noise level sigma: the fp32 image F, or (cond_cache) the bf16 token
             rows; dup = 1 when the evaluation is guided by batch doubling: the output holds the unconditional half behind the
@@ -690,16 +709,16 @@ class LatentDiffusion(nn.Module):
                 hip.check(L.md_edm_sampler_patchify(xs.data_ptr(), pt.data_ptr(), B, C, H, W, p, float(sigma), ec.sigma_data, dup, st),
                           "md_edm_sampler_patchify")
                 t = torch.full((Be,), c_noise, device=x.device, dtype=torch.float32)
-                F = dit._engine.forward(None, t, None, cond=cond.narrow(Be), patches=pt).out_tok
+                F = dit._engine.forward(None, t, None, cond=cond.narrow(Be), patches=pt, **sc_args(Be)).out_tok
                 Fg = guide._engine.forward(None, t, None, cond=cond_g, patches=pt).out_tok if auto and g_eval else None
                 return F, dup, Fg
             hip.check(L.md_edm_sampler_input(xs.data_ptr(), net_in.data_ptr(), numel, float(sigma), ec.sigma_data, dup, st),
                       "md_edm_sampler_input")
             t = torch.full((1,), c_noise, device=x.device, dtype=torch.float32)
             if Be == Bn:
-                F = self.dit.forward_without_cfg(net_in, t, y2, 0)["sample"].contiguous()
+                F = self.dit.forward_without_cfg(net_in, t, y2, 0, **sc_args(Be))["sample"].contiguous()
             else:
-                F = self.dit.forward_without_cfg(net_in[:B], t, y, 0)["sample"].contiguous()
+                F = self.dit.forward_without_cfg(net_in[:B], t, y, 0, **sc_args(Be))["sample"].contiguous()
             Fg = guide.forward_without_cfg(net_in, t, y_g, 0)["sample"].to(torch.float32).contiguous() if auto and g_eval else None
             return F, dup, Fg
 
@@ -774,6 +793,8 @@ class LatentDiffusion(nn.Module):
                                                  t_in, ec.sigma_data, *coef, st), "md_edm_solver_update")
         coefs = None if heun else samplers.solver_coefficients(sampler, t_steps[i0:], t_hats[i0:])
         reps = samplers.edit_repetitions(t_steps, i0, resample) if resample > 1 else [1] * (n - i0)
+        if step_cache is not None:                  # the run's evaluations: every repetition of a step, heun twice but for the last step
+            step_cache.reset(sum(r * (2 if heun and i < n - 1 else 1) for i, r in zip(range(i0, n), reps)))
         for i in range(i0, n):
             t_cur, t_next, t_hat = t_steps[i], t_steps[i + 1], t_hats[i]
             for rep in range(reps[i - i0]):
@@ -811,7 +832,7 @@ class LatentDiffusion(nn.Module):
                  cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
                  guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
                  guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
-                 apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, **kwargs):
+                 apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, step_cache=None, **kwargs):
         """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache, sampler,
         guidance_interval, guide and guide_captions: as in edm_sampler_loop (with a guide, guidance_scale is the autoguidance weight).
         init_latents, strength, inpaint_mask and resample: image-to-image and inpainting as in edm_sampler_loop; the seeded draw below is
@@ -820,7 +841,9 @@ class LatentDiffusion(nn.Module):
         guidance_mode, guidance_rescale, apg_eta, apg_norm_threshold and apg_momentum: CFG rescale and adaptive projected guidance as in
         edm_sampler_loop; they tame the over-saturation of plain guidance at this default guidance_scale.
         measurement, measurement_scale and guidance_loss: measurement-guided sampling as in edm_sampler_loop (the measurement lives in the
-        sampler's latent space, like init_latents)."""
+        sampler's latent space, like init_latents).
+        step_cache: a step_cache.StepCache, as in edm_sampler_loop."""
+        samplers.check_step_cache(step_cache, guide, measurement, guidance_loss)
         samplers.check_measurement(None, measurement, measurement_scale, guidance_loss)
         samplers.check_guide(self.dit, guide, guide_captions)
         samplers.check_guidance(guidance_mode, guidance_scale, guidance_rescale, apg_eta, apg_norm_threshold, apg_momentum)
@@ -842,7 +865,7 @@ class LatentDiffusion(nn.Module):
                                         init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, resample=resample,
                                         guidance_mode=guidance_mode, guidance_rescale=guidance_rescale, apg_eta=apg_eta,
                                         apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, measurement=measurement,
-                                        measurement_scale=measurement_scale, guidance_loss=guidance_loss)
+                                        measurement_scale=measurement_scale, guidance_loss=guidance_loss, step_cache=step_cache)
         if return_only_latents:
             return latents
         image = self.vae.decode((latents / self.latent_scale).to(DATA_TYPES[self.dtype])).sample

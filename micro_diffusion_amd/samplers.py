@@ -270,6 +270,24 @@ def check_guide(main, guide, guide_captions: str = "same") -> None:
         raise ValueError(f"the guide is on {db}, the main network on {da}: both must be on the same device")
 
 
+def check_step_cache(step_cache=None, guide=None, measurement=None, guidance_loss=None) -> bool:
+    """Refuse, before anything is launched or allocated, a step-cache request the sampler cannot run; True when the run
+    caches.  ValueError for an object that is not a step_cache.StepCache (anything without its step / reset / engine_args), for a
+    guide network (autoguidance: the second network would need a cache and a policy of its own), and for measurement / guidance_loss,
+    whose taped evaluation needs every block."""
+    if step_cache is None:
+        return False
+    for name in ("step", "reset", "engine_args"):
+        if not callable(getattr(step_cache, name, None)):
+            raise ValueError(f"step_cache must be a step_cache.StepCache, got {type(step_cache).__name__}")
+    if guide is not None:
+        raise ValueError("step_cache with guide= (autoguidance) is not defined: the guide network would need a cache of its own")
+    if measurement is not None or guidance_loss is not None:
+        raise ValueError("step_cache with measurement= / guidance_loss= is not defined: the taped evaluation of a guided step needs "
+                         "every block")
+    return True
+
+
 def evaluation_sigmas(sampler: str, t_steps: Sequence[float]) -> List[float]:
     """The noise level of every network evaluation of a run without churn, in order."""
     out = []
