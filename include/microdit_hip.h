@@ -528,7 +528,11 @@ int md_edm_solver_update_coef_tok(const double* x_in, const void* tok_bf16, cons
 /* ------------------------------------------------------------------------------------------- optimiser */
 /* Sum of squares of a gradient buffer (fp32, or bf16 when g_is_bf16), deterministic: workgroup b of a fixed grid writes
  * partials[b] (MD_SUMSQ_PARTIALS floats per call); md_sumsq_finish adds `count` partials (several calls' worth, e.g. one per
- * data-parallel bucket) in a fixed order into out[0].  n must be a multiple of 8. */
+ * data-parallel bucket) in a fixed order into out[0].  n must be a multiple of 8 and g 16-byte aligned (16-byte loads for both
+ * types); anything else is MD_BAD_ARG with nothing launched.  md_sumsq writes ALL MD_SUMSQ_PARTIALS partials whatever n is (a
+ * workgroup without work writes 0), so partials needs no initialisation, and nothing outside them.
+ * Non-finite input is not filtered: a NaN or +-Inf element makes the sum NaN or +Inf, and so does a FINITE gradient whose sum of
+ * squares exceeds FLT_MAX (the sum is then +Inf): md_step_guard reads all three as "skip the step". */
 #define MD_SUMSQ_PARTIALS 1024
 int md_sumsq(const void* g, int32_t g_is_bf16, int64_t n, float* partials, hipStream_t stream);
 int md_sumsq_finish(const float* partials, int64_t count, float* out, hipStream_t stream);
@@ -556,7 +560,12 @@ int md_adamw_step(const md_adamw_args* a, hipStream_t stream);
  * the optimiser state): ONE launch over n_ranges <= MD_ADAMW_MAX_RANGES chunks of the flat buffers.  Range j covers flat
  * elements [flat_off[j], flat_off[j] + count[j]) of p / m / v / ema (a->p ... are the flat bases); a->g_bf16 (the
  * reduce-scattered gradient) and a->shadow (the bf16 weights to all-gather) are PACKED: range j starts at sum(count[0..j)).
- * a->n is ignored; zero_grad must be 0 (the staging cast cleared the accumulators).  flat_off / count are HOST arrays. */
+ * a->n is ignored; zero_grad must be 0 (the staging cast cleared the accumulators).  flat_off / count are HOST arrays, every entry
+ * a multiple of 4 (count > 0, flat_off >= 0); the ranges may come in any flat order and must not overlap.
+ * Both forms, MD_BAD_ARG with nothing launched otherwise: p, g, m, v non-NULL (g also in the range form, which never touches it);
+ * ema_mode in 0..2 and ema non-NULL unless it is 0; p, g, m, v (and ema unless ema_mode is 0) 16-byte aligned, g_bf16 and shadow
+ * 8-byte aligned (the widths of the kernel's vector accesses; with offsets that are multiples of 4 the bases' alignment carries to
+ * every range).  md_adamw_step: n > 0 and n % 4 == 0.  The range form: g_bf16 non-NULL and 1 <= n_ranges <= MD_ADAMW_MAX_RANGES. */
 #define MD_ADAMW_MAX_RANGES 64
 int md_adamw_step_ranges(const md_adamw_args* a, const int64_t* flat_off, const int64_t* count, int32_t n_ranges, hipStream_t stream);
 

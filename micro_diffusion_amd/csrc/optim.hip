@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(md_adamw_args a, AdamWRanges
 }  // namespace
 
 extern "C" int md_sumsq(const void* g, int32_t g_is_bf16, int64_t n, float* partials, hipStream_t st) {
-    if (!g || !partials || n <= 0 || n % 8) return MD_BAD_ARG;
+    if (!g || !partials || n <= 0 || n % 8 || ((uintptr_t)g & 15)) return MD_BAD_ARG;        // 16-byte loads, fp32 and bf16
     if (g_is_bf16) hipLaunchKernelGGL((sumsq_kernel<true>), dim3(SUMSQ_BLOCKS), dim3(256), 0, st, g, n / 8, partials);
     else hipLaunchKernelGGL((sumsq_kernel<false>), dim3(SUMSQ_BLOCKS), dim3(256), 0, st, g, n / 8, partials);
     MD_LAUNCH_CHECK();
@@ -244,9 +244,16 @@ extern "C" int md_step_guard(const float* sumsq, int32_t* state, hipStream_t st)
     return 0;
 }
 
+// The kernel's vector accesses: 16 bytes on the fp32 buffers (ema only where the pass touches it), 8 bytes on the bf16 ones.
+static bool adamw_misaligned(const md_adamw_args* a) {
+    const uintptr_t f32 = (uintptr_t)a->p | (uintptr_t)a->g | (uintptr_t)a->m | (uintptr_t)a->v | (a->ema_mode ? (uintptr_t)a->ema : 0);
+    const uintptr_t b16 = (uintptr_t)a->g_bf16 | (uintptr_t)a->shadow;
+    return (f32 & 15) || (b16 & 7);
+}
+
 extern "C" int md_adamw_step_guarded(const md_adamw_args* a, const int32_t* guard, hipStream_t st) {
     if (!a || !a->p || !a->g || !a->m || !a->v || a->n <= 0 || a->n % 4) return MD_BAD_ARG;
-    if (a->ema_mode < 0 || a->ema_mode > 2 || (a->ema_mode && !a->ema)) return MD_BAD_ARG;
+    if (a->ema_mode < 0 || a->ema_mode > 2 || (a->ema_mode && !a->ema) || adamw_misaligned(a)) return MD_BAD_ARG;
     // one 256-thread workgroup per 4 KiB of every stream and iteration; 8 workgroups resident per CU x 256 CUs x 4 rounds
     int64_t grid = (a->n / 4 + 255) / 256;
     if (grid > 8192) grid = 8192;
@@ -270,7 +277,7 @@ extern "C" int md_adamw_step_ranges_guarded(const md_adamw_args* a, const int64_
                                             const int32_t* guard, hipStream_t st) {
     if (!a || !a->p || !a->g || !a->m || !a->v || !a->g_bf16 || !flat_off || !count || n_ranges < 1 || n_ranges > ADAMW_MAX_RANGES)
         return MD_BAD_ARG;
-    if (a->ema_mode < 0 || a->ema_mode > 2 || (a->ema_mode && !a->ema) || a->zero_grad) return MD_BAD_ARG;
+    if (a->ema_mode < 0 || a->ema_mode > 2 || (a->ema_mode && !a->ema) || a->zero_grad || adamw_misaligned(a)) return MD_BAD_ARG;
     AdamWRanges rg;
     rg.n = n_ranges;
     int64_t tot = 0;
