@@ -9,7 +9,7 @@ import re
 import pytest
 import torch
 
-from micro_diffusion_amd import samplers
+from micro_diffusion_amd import samplers, sampling
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # name -> number of arguments: the existing counterpart's, has_uncond replaced by the second pointer
@@ -118,7 +118,7 @@ def test_refusals_raise_before_anything_runs(cpu_model, monkeypatch):
     x, y = torch.randn(1, 4, 8, 8), torch.randn(1, 1, 5, 32)
     monkeypatch.setattr(m.dit, "forward_without_cfg", _never)
     monkeypatch.setattr(m.dit, "encode_condition", _never)
-    monkeypatch.setattr(m, "_edm_sampler_fused", _never)
+    monkeypatch.setattr(sampling, "FusedRun", _never)                  # the fused loop's entry point: its constructor
     n = 0
     for match, kw in _bad_requests(m):
         for fused in (None, False, True):
@@ -149,11 +149,10 @@ def test_autoguided_forward_combines_in_fp32(cpu_model):
         def forward_without_cfg(self, x, t, y, **kw):
             self.seen.append(y)
             return {"sample": (self.k * x).to(torch.float64), "mask": None}
-    from micro_diffusion_amd.model import LatentDiffusion
     main, guide = Net(2.0), Net(0.5)
     holder = type("H", (), {"dit": main})()
     y, yg = torch.ones(2, 1, 3, 4), torch.zeros(2, 1, 3, 4)
-    fwd = LatentDiffusion._autoguided_forward(holder, guide, yg, 2.5)
+    fwd = sampling.autoguided_forward(holder, guide, yg, 2.5)
     x = torch.randn(2, 4, 8, 8)
     out = fwd(x, torch.zeros(1), y, mask_ratio=0)["sample"]
     assert out.dtype == torch.float32

@@ -7,7 +7,7 @@ import math
 import pytest
 import torch
 
-from micro_diffusion_amd import samplers
+from micro_diffusion_amd import samplers, sampling
 from oracle import microdit_ref as orc
 
 pytestmark = pytest.mark.gpu
@@ -249,7 +249,7 @@ def test_churn_runs_on_the_fused_loop(smooth_model, sampler):
     try:
         plain = smooth_model.edm_sampler_loop(lat, y, steps=6, cfg=3.0, fused=True, sampler=sampler)
         ec.update(S_churn=20, S_noise=1.003, S_min=math.sqrt(t[4] * t[5]), S_max=math.sqrt(t[0] * t[1]))
-        hats = smooth_model._churned_levels(t, 6)
+        hats = sampling.churned_levels(ec, t, 6)
         assert [h > s for h, s in zip(hats, t)] == [False, True, True, True, True, False]
         torch.manual_seed(21)
         a = smooth_model.edm_sampler_loop(lat, y, steps=6, cfg=3.0, fused=True, sampler=sampler)
