@@ -39,6 +39,15 @@ class Tape:
     pass
 
 
+def poison_(t: torch.Tensor) -> torch.Tensor:
+    """Debug fill of a buffer nothing has written yet (DiTEngine.poison): NaN for floating dtypes, 0 for integer ones -- every
+    integer buffer of the engine is an index table a kernel indexes with, and 0 is always inside the table.  One stream-ordered
+    fill_ on the current stream."""
+    if t.numel():
+        t.fill_(float("nan") if t.dtype.is_floating_point else 0)
+    return t
+
+
 class _Arena:
     """Bump allocator over ONE device buffer.  With it the activations, gradients and scratch of a microbatch live at fixed
     addresses and the step path makes no allocator calls (no caching-allocator bookkeeping per launch, no at::native fill
@@ -142,6 +151,11 @@ class ResidualCache:
         self.B = self.T = self.version = None
         self._ref_key = None
         self._ws = self._rel = self._rel_max = None
+        self.poison = False             # DiTEngine.forward copies its own switch here: new buffers are handed out poisoned
+
+    def _new(self, shape, like: torch.Tensor, dtype=None) -> torch.Tensor:
+        t = torch.empty(shape, device=like.device, dtype=like.dtype if dtype is None else dtype)
+        return poison_(t) if self.poison else t
 
     def reset(self) -> None:
         """Forget the filled state and the probe reference (the buffers stay allocated): the start of a sampling run."""
@@ -162,7 +176,7 @@ class ResidualCache:
     def store(self, x_out: torch.Tensor, x_in: torch.Tensor, B: int, T: int, version) -> None:
         """delta <- bf16(x_out - x_in): one launch."""
         if self.delta is None or self.delta.shape != x_in.shape or self.delta.device != x_in.device:
-            self.delta = torch.empty_like(x_in)
+            self.delta = self._new(x_in.shape, x_in)
         hip.check(hip.lib().md_residual_delta(x_out.data_ptr(), x_in.data_ptr(), self.delta.data_ptr(), x_in.numel(),
                                               torch.cuda.current_stream().cuda_stream), "md_residual_delta")
         self.B, self.T, self.version = B, T, version
@@ -173,7 +187,7 @@ class ResidualCache:
         to the host.  The first probe after a reset, or at another shape or weight version, only fills ref and returns None."""
         key = (tuple(x.shape), B, version)
         if self.ref is None or self.ref.shape != x.shape or self.ref.device != x.device:
-            self.ref = torch.empty_like(x)
+            self.ref = self._new(x.shape, x)
             self._ref_key = None
         if self._ref_key != key:
             self.ref.copy_(x)
@@ -184,10 +198,10 @@ class ResidualCache:
         need = ctypes.c_int64(0)
         hip.check(L.md_step_probe_ws_doubles(B, per, byref(need)), "md_step_probe_ws_doubles")
         if self._ws is None or self._ws.numel() < need.value or self._ws.device != x.device:
-            self._ws = torch.empty(need.value, device=x.device, dtype=torch.float64)
+            self._ws = self._new(need.value, x, torch.float64)
         if self._rel is None or self._rel.numel() != B or self._rel.device != x.device:
-            self._rel = torch.empty(B, device=x.device, dtype=F32)
-            self._rel_max = torch.empty(1, device=x.device, dtype=F32)
+            self._rel = self._new(B, x, F32)
+            self._rel_max = self._new(1, x, F32)
         hip.check(L.md_step_probe(x.data_ptr(), self.ref.data_ptr(), B, per, self._ws.data_ptr(), st), "md_step_probe")
         hip.check(L.md_step_probe_finish(self._ws.data_ptr(), B, self._rel.data_ptr(), self._rel_max.data_ptr(), st), "md_step_probe_finish")
         return self._rel_max
@@ -243,6 +257,11 @@ class DiTEngine:
         # points -- per-workgroup partial sums in a workspace, added in a fixed order -- so two runs of one step on one GPU give
         # bit-identical gradients.  Off: the launch sequence is unchanged.  (DESIGN.md "Deterministic mode")
         self.deterministic = os.environ.get("MD_DETERMINISTIC", "0") == "1"
+        # Poisoned allocations (opt-in: MD_POISON=1 or this attribute; debug only): every buffer empty() / fresh() hands
+        # out is filled first -- NaN for floating dtypes, 0 for integer ones -- and the split-K / tail workspace is filled with NaN at
+        # the start of every forward() and backward(), so a launch that reads what nothing wrote in this pass meets NaN (or index 0)
+        # instead of what the previous, identical pass left at the same arena address.  Off: one attribute test, no launch.
+        self.poison = os.environ.get("MD_POISON", "0") == "1"
         self._det_ws_floats = {}           # (kind, rows, rows per sample, rows per block, C) -> md_det_ws_floats
         self.gemm_log = None               # tests: list that receives (variant actually requested, M, N, K, batch) per launch
         self.before_segment = None         # data parallelism: callable(bucket key) run before the first kernel that reads the bf16
@@ -343,9 +362,18 @@ class DiTEngine:
         return torch.cuda.current_stream().cuda_stream
 
     def empty(self, *shape, dtype=BF16):
-        if self._arena is not None:
-            return self._arena.alloc(shape, dtype)
-        return torch.empty(*shape, device=self.dev, dtype=dtype)
+        t = self._arena.alloc(shape, dtype) if self._arena is not None else torch.empty(*shape, device=self.dev, dtype=dtype)
+        return poison_(t) if self.poison else t
+
+    def fresh(self, *shape, dtype=F32):
+        """Uninitialised memory of the torch allocator, never the arena: what outlives the pass (returned input gradients, the loss
+        glue's per-sample buffers)."""
+        t = torch.empty(*shape, device=self.dev, dtype=dtype)
+        return poison_(t) if self.poison else t
+
+    def _poison_ws(self):
+        if self.poison:
+            self.ws.fill_(float("nan"))
 
     def zeros(self, *shape, dtype=F32):
         t = self.empty(*shape, dtype=dtype)
@@ -1291,6 +1319,7 @@ class DiTEngine:
             if not self.backbone:
                 raise ValueError("step_cache: the model has no backbone blocks to cache")
             step_cache.resolve(len(self.backbone))
+            step_cache.poison = self.poison
         elif reuse is not False:
             raise ValueError("reuse needs a step_cache")
         if cond is not None or patches is not None:
@@ -1323,6 +1352,7 @@ class DiTEngine:
         else:
             assert y.is_contiguous() and y.dtype in (torch.float16, F32)
             Lc, Dc, ydt = y.shape[-2], y.shape[-1], str(y.dtype)
+        self._poison_ws()
         grad_pass = self.use_arena and arena and record_tape
         self._record = record_tape or input_tape or self.keep_last_tape
         dsp = self.disperse
@@ -1664,6 +1694,7 @@ class DiTEngine:
         if getattr(tp, "input_tape", False) and not x_only:
             raise RuntimeError("an input_tape holds a frozen conditioning: its backward takes input_grads=('x',) and param_grads=False, "
                                f"got input_grads={sorted(want)}, param_grads={bool(param_grads)}")
+        self._poison_ws()
         use = self.use_arena and getattr(tp, "arena", False)
         if use:
             self._scratch_arena.begin((tp.B, tp.T, tp.Tk, tp.Lc, tp.H, tp.W))
@@ -1774,7 +1805,7 @@ class DiTEngine:
         if "x" in want:
             # image: the transpose of md_patchify(in_scale) + the x_embedder.proj GEMM in one launch, fp32 straight from the accumulators
             # (a forward that read patches= has no in_scale: dx is then the gradient of the un-patchified network input)
-            out.dx = torch.empty(B, cfg.in_channels, tp.H, tp.W, device=self.dev, dtype=F32)
+            out.dx = self.fresh(B, cfg.in_channels, tp.H, tp.W)
             path = ctypes.c_int32(-1)
             self._prof("patch_embed_dgrad", 2.0 * B * T * D, lambda: hip.check(self.L.md_patch_embed_dgrad(
                 dtok_e.data_ptr(), D, self.S["x_embedder.proj.weight"].data_ptr(), _p(tp.in_scale), out.dx.data_ptr(), B, cfg.in_channels,
@@ -1798,7 +1829,7 @@ class DiTEngine:
         if "t" in want:
             dtfreq = self.empty(B, 512)
             self.lin_dgrad(dtpre, "t_embedder.mlp.0", dtfreq, B, D, 512)
-            out.dt = torch.empty(B, device=self.dev, dtype=F32)
+            out.dt = self.fresh(B)
             hip.check(L.md_timestep_embed_bwd(tp.t_f.data_ptr(), dtfreq.data_ptr(), out.dt.data_ptr(), B, 512, st), "md_timestep_embed_bwd")
             if self.input_grad_log is not None:
                 self.input_grad_log.append(("md_timestep_embed_bwd", None))
@@ -1846,7 +1877,7 @@ class DiTEngine:
         Dc = tp.ycap.shape[1]
         dycap = self._mlp_norm_bwd("y_embedder.y_proj", tp.yproj, dy, Mc, Dc, Lc, need_dx="y" in want)
         if "y" in want:
-            out.dy = torch.empty(Mc, Dc, device=self.dev, dtype=tp.y_dtype)
+            out.dy = self.fresh(Mc, Dc, dtype=tp.y_dtype)
             hip.check(L.md_cast_rows_from_bf16(dycap.data_ptr(), out.dy.data_ptr(), 0 if tp.y_dtype == torch.float16 else 1, Mc, Dc,
                                                _p(tp.y_rowscale), Lc, st), "md_cast_rows_from_bf16")
             if self.input_grad_log is not None:

@@ -325,11 +325,10 @@ def _edm_forward(model: LatentDiffusion, anchor, x, y, rnd, eps, mnoise, mask_ra
     st = torch.cuda.current_stream().cuda_stream
     ec = model.edm_config
     B, C, H, W = x.shape
-    dev = x.device
-    xn = torch.empty(x.shape, device=dev, dtype=torch.float32)
-    sigma, cin, cnoise = (torch.empty(B, device=dev) for _ in range(3))
+    xn = eng.fresh(*x.shape)
+    sigma, cin, cnoise = (eng.fresh(B) for _ in range(3))
     if x.dtype == torch.float16:
-        x0 = torch.empty(x.shape, device=dev, dtype=torch.float32)
+        x0 = eng.fresh(*x.shape)
         hip.check(L.md_edm_prepare_f16(x.data_ptr(), eps.data_ptr(), rnd.data_ptr(), xn.data_ptr(), x0.data_ptr(), sigma.data_ptr(),
                                        cin.data_ptr(), cnoise.data_ptr(), B, C * H * W, ec.P_mean, ec.P_std, ec.sigma_data, st),
                   "md_edm_prepare_f16")
@@ -339,13 +338,13 @@ def _edm_forward(model: LatentDiffusion, anchor, x, y, rnd, eps, mnoise, mask_ra
                                    cnoise.data_ptr(), B, C * H * W, ec.P_mean, ec.P_std, ec.sigma_data, st), "md_edm_prepare")
     tape = eng.forward(xn, cnoise, y, mask_ratio=mask_ratio, mask_noise=mnoise, in_scale=cin, y_rowscale=y_rowscale,
                        record_tape=record_tape or train is not None, arena=train is not None)
-    lps = torch.empty(B, device=dev)
-    loss = torch.empty(1, device=dev)
+    lps = eng.fresh(B)
+    loss = eng.fresh(1)
     keep = None if tape.keep_rows is None else tape.keep_rows.data_ptr()
     lw = model.loss_weighting if train is not None else None
     if train is not None:
         gscale, accum, aw = train
-        dtok = torch.empty(B * tape.Tk, dit.config.patch_vec, device=dev, dtype=torch.bfloat16)
+        dtok = eng.fresh(B * tape.Tk, dit.config.patch_vec, dtype=torch.bfloat16)
     if lw is not None:
         inv = lw.forward(cnoise)
         hip.check(L.md_edm_loss_train_weighted(tape.out_tok.data_ptr(), keep, xn.data_ptr(), x0.data_ptr(), sigma.data_ptr(), lps.data_ptr(),
@@ -358,7 +357,7 @@ def _edm_forward(model: LatentDiffusion, anchor, x, y, rnd, eps, mnoise, mask_ra
                                       loss.data_ptr(), dtok.data_ptr(), gscale, None if accum is None else accum.data_ptr(), aw, B,
                                       tape.Tk, C, H, W, dit.patch_size, ec.sigma_data, st), "md_edm_loss_train")
     else:
-        dtok = torch.empty(B * tape.Tk, dit.config.patch_vec, device=dev) if record_tape else None
+        dtok = eng.fresh(B * tape.Tk, dit.config.patch_vec) if record_tape else None
         hip.check(L.md_edm_loss(tape.out_tok.data_ptr(), keep, xn.data_ptr(), x0.data_ptr(), sigma.data_ptr(), lps.data_ptr(),
                                 loss.data_ptr(), None if dtok is None else dtok.data_ptr(), B, tape.Tk, C, H, W, dit.patch_size,
                                 ec.sigma_data, st), "md_edm_loss")
@@ -386,7 +385,7 @@ class _EDMLossFunction(torch.autograd.Function):
         if pgrad:
             dit.attach_grads()
         g = gloss.detach().to(torch.float32).contiguous()
-        dtb = torch.empty(dtok.shape, device=dtok.device, dtype=torch.bfloat16)
+        dtb = dit._engine.fresh(*dtok.shape, dtype=torch.bfloat16)
         hip.check(hip.lib().md_cast_f32_bf16(dtok.data_ptr(), dtb.data_ptr(), dtok.numel(), g.data_ptr(),
                                              torch.cuda.current_stream().cuda_stream), "md_cast_f32_bf16")
         ig = dit._engine.backward(tape, dtb, on_segment=getattr(dit, "_on_segment", None),
