@@ -801,6 +801,63 @@ int md_step_probe_ws_doubles(int64_t B, int64_t per_sample, int64_t* out);
 int md_step_probe(const void* x, void* ref, int64_t B, int64_t per_sample, double* ws, hipStream_t stream);
 int md_step_probe_finish(const double* ws, int64_t B, float* rel, float* rel_max, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------- Muon */
+/* (symbols added, MD_ABI_VERSION stays 6.)  Orthogonalised momentum for the hidden matrices of the DiT blocks (Jordan et
+ * al. 2024, "Muon"; Liu et al. 2025, "Muon is Scalable for LLM Training"; no reference counterpart: the reference knows AdamW only).  For a
+ * targeted matrix W [rows, cols] of the flat buffers, with the accumulated gradient g and the momentum m (the `m` buffer of the optimiser):
+ *
+ * md_muon_momentum   per element, fp32, every operation rounded once, in this order:
+ *     coef   as md_adamw_step forms it: grad_scale, times min(1, max_norm / (sqrtf(*sumsq) * grad_scale + 1e-6f)) with sumsq non-NULL and
+ *            max_norm > 0
+ *     gc = coef * g        m' = fmaf(mu, m, gc)        u = nesterov ? fmaf(mu, m', gc) : m'        m' is stored
+ *   per item:  norms[item] = sum u^2 in fp64 (squares exact), in an order that is a function of the table alone: MD_MUON_NORM_PARTS
+ *     workgroups per item, each thread its float4s in ascending order, a fixed tree over the 256 threads, the partials in ascending
+ *     order;  inv = (float)(1.0 / (sqrt(norms[item]) + 1e-7));  X = bf16(u * inv), row-major [rows, cols], at ws + ws_off.
+ *   g: the fp32 accumulators: read (g_bf16 == NULL) and, with zero_grad, zeroed on the items and nowhere else.  g_bf16 (optional): a
+ *     flat bf16 gradient buffer (the data-parallel exchange buffer) read INSTEAD at the same flat index; it is only read.
+ *   guard (NULL = none) with *guard == 0: m, ws and norms stay untouched bit for bit, the accumulators are still zeroed.
+ *   partials: MD_MUON_NORM_PARTS * n_items doubles of scratch, written before they are read.
+ * md_muon_newton_schulz   on every item, in place, `steps` (1 .. 8) iterations of  A = X X^T,  B = b A + c A A,  X <- a X + B X  for
+ *   rows <= cols, and of  A = X^T X,  X <- a X + X B  for rows > cols (X keeps the parameter's orientation; the operand-layout flags of
+ *   md_gemm_bf16 pick the side).  bf16 operands, fp32 accumulation, ksplit = 1, and a rounding to bf16 at three points per iteration:
+ *   A = bf16(X X^T) (MD_EPI_STORE_BF16);  T = A A as an fp32 store into the shared scratch, B = bf16(b A + c T);  U = B X as an fp32
+ *   store, X = bf16(a X + U) -- the two sums by md_muon_axpby.  Two calls on the same data give identical bits.  Five launches per
+ *   iteration and item; the Gram products of up to 16 consecutive items of one shape (the experts of one tensor) go out as one batched
+ *   launch.  Host loop, no synchronisation; gemm_launches (optional HOST pointer) receives the number of md_gemm_bf16 launches.
+ * md_muon_axpby   out[i] = bf16(a * (float)x[i] + b * y[i]), x / out bf16, y fp32, n elements: the two products and the sum are rounded
+ *   once each (no fused multiply-add), then once to bf16.  out == x is allowed.  n > 0, n % 8 == 0, 16-byte aligned pointers; anything
+ *   else MD_BAD_ARG, nothing launched.
+ * md_muon_apply   per element:  q = p * decay, decay = 1.f - lr * weight_decay as md_adamw_step forms it;
+ *     p' = fmaf(-(lr * scale_item), (float)O, q), O read at ws + ws_off (where md_muon_newton_schulz leaves it);  shadow = bf16(p') at the flat index;
+ *     ema_mode 0: ema not touched; 1: ema = p'; 2: ema = fmaf(ema_smoothing, ema, (1.f - ema_smoothing) * p').
+ *   *guard == 0: p and a live EMA stay untouched bit for bit, shadow = bf16(p), mode 1 still copies p.  Nothing outside the items is
+ *   written.
+ * Work table (the convention of md_lora_*): `items` is the DEVICE copy the kernels read, `items_host` the caller's HOST copy of the same
+ * entries, on which shapes, alignment and workspace offsets are checked and from which the grids are sized.  md_muon_ws_bytes checks
+ * the host table, writes every ws_off into it (upload the table afterwards) and returns the workspace size in BYTES.  Workspace of an
+ * item, in bf16 elements from ws_off: [X: rows * cols | A: s * s | B: s * s], s = min(rows, cols); items follow each other without a
+ * gap; behind the last one, max(rows * cols) floats of fp32 scratch shared by all items (the launches of one stream run in order).
+ * Supported: 1 <= n_items <= 65535; rows and cols multiples of 64; flat_off >= 0 and a multiple of 8; every pointer 16-byte aligned
+ * (partials / norms 8); 0 <= mu < 1; a, b, c finite.  Anything else, a NULL pointer (g_bf16, sumsq, guard, gemm_launches and, in mode
+ * 0, ema excepted) or a ws_off that is not what md_muon_ws_bytes wrote: MD_BAD_ARG, nothing launched. */
+#define MD_MUON_NORM_PARTS 16
+typedef struct md_muon_item {
+    int64_t flat_off; /* first element of W inside p / g / m / shadow / ema */
+    int32_t rows, cols;
+    int64_t ws_off;   /* first bf16 element of the item's workspace: written by md_muon_ws_bytes */
+    float scale;      /* md_muon_apply: the update is lr * scale * O (the shape factor) */
+    int32_t reserved;
+} md_muon_item;
+int md_muon_ws_bytes(md_muon_item* items_host, int32_t n_items, int64_t* out);
+int md_muon_momentum(float* g, const void* g_bf16, float* m, const md_muon_item* items, const md_muon_item* items_host, int32_t n_items,
+                     float mu, int32_t nesterov, float grad_scale, const float* sumsq, float max_norm, int32_t zero_grad,
+                     const int32_t* guard, void* ws, double* partials, double* norms, hipStream_t stream);
+int md_muon_newton_schulz(const md_muon_item* items_host, int32_t n_items, int32_t steps, float a, float b, float c, void* ws,
+                          int32_t* gemm_launches, hipStream_t stream);
+int md_muon_apply(float* p, void* shadow, float* ema, const md_muon_item* items, const md_muon_item* items_host, int32_t n_items, float lr,
+                  float weight_decay, int32_t ema_mode, float ema_smoothing, const int32_t* guard, const void* ws, hipStream_t stream);
+int md_muon_axpby(const void* x, const float* y, void* out, float a, float b, int64_t n, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

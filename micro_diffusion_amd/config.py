@@ -272,6 +272,57 @@ def lora_options(cfg: Dict[str, Any], world: Any = None) -> Dict[str, Any]:
     return {"enabled": True, "rank": rank, "alpha": alpha, "targets": targets, "weight_decay": float(wd), "load_path": path}
 
 
+def muon_options(cfg: Dict[str, Any]) -> Dict[str, Any]:
+    """The Muon switches of the `misc` section, off unless the config sets them: misc.muon (bool), misc.muon_momentum
+    (default 0.95), misc.muon_nesterov (default true), misc.muon_ns_steps (1 .. 8, default 5), misc.muon_adjust ("rms" | "spectral"),
+    misc.muon_targets (regular expressions on parameter names; default: the hidden projections of every block) and misc.muon_adamw_lr
+    (learning rate of the AdamW part; default: the optimiser's lr).
+    Returns {"enabled", "momentum", "nesterov", "ns_steps", "adjust", "targets", "adamw_lr"}.  Raises ValueError on values the optimiser
+    cannot honour, on the other keys given without misc.muon=true, and with misc.lora_rank (the adapter assumes a frozen base)."""
+    import re
+    from .muon import DEFAULT_TARGETS, check_hyper
+    misc = cfg.get("misc") or {}
+    on = misc.get("muon", False)
+    if on is None:
+        on = False
+    if not isinstance(on, bool):
+        raise ValueError(f"misc.muon must be true or false, got {on!r}")
+    keys = ("muon_momentum", "muon_nesterov", "muon_ns_steps", "muon_adjust", "muon_targets", "muon_adamw_lr")
+    off = {"enabled": False, "momentum": 0.95, "nesterov": True, "ns_steps": 5, "adjust": "rms", "targets": list(DEFAULT_TARGETS),
+           "adamw_lr": None}
+    if not on:
+        for k in keys:
+            if misc.get(k) is not None:
+                raise ValueError(f"misc.{k} needs misc.muon=true")
+        return off
+    if misc.get("lora_rank"):
+        raise ValueError("misc.muon with misc.lora_rank: the adapter is trained on a frozen base, which Muon would update")
+    out = dict(off, enabled=True)
+    for k in ("momentum", "nesterov", "ns_steps", "adjust", "adamw_lr"):
+        if misc.get("muon_" + k) is not None:
+            out[k] = misc["muon_" + k]
+    try:
+        check_hyper(out["momentum"], out["nesterov"], out["ns_steps"], out["adjust"], out["adamw_lr"])
+    except ValueError as e:
+        raise ValueError("misc.muon_*: " + str(e)) from None
+    out["momentum"] = float(out["momentum"])
+    if out["adamw_lr"] is not None:
+        out["adamw_lr"] = float(out["adamw_lr"])
+    targets = misc.get("muon_targets")
+    if targets is not None:
+        if isinstance(targets, str):
+            targets = [targets]
+        elif not (isinstance(targets, (list, tuple)) and targets and all(isinstance(t, str) for t in targets)):
+            raise ValueError(f"misc.muon_targets must be a non-empty list of regular expressions, got {targets!r}")
+        for t in targets:
+            try:
+                re.compile(t)
+            except re.error as e:
+                raise ValueError(f"misc.muon_targets: {t!r} is not a regular expression ({e})") from None
+        out["targets"] = list(targets)
+    return out
+
+
 def locate(target: str):
     native = TARGETS.get(target, target)
     if native is None:

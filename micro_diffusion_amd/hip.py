@@ -179,6 +179,12 @@ class LoraItem(Structure):
     _fields_ = [("w_off", c_int64), ("a_off", c_int64), ("b_off", c_int64), ("ws_off", c_int64), ("rows", c_int32), ("cols", c_int32)]
 
 
+class MuonItem(Structure):
+    """md_muon_item: one targeted matrix W [rows, cols] of the flat buffers under Muon; ws_off is written by md_muon_ws_bytes, scale is
+    the shape factor of the update."""
+    _fields_ = [("flat_off", c_int64), ("rows", c_int32), ("cols", c_int32), ("ws_off", c_int64), ("scale", c_float), ("reserved", c_int32)]
+
+
 _sig("md_gemm_bf16", POINTER(GemmArgs), P)
 _sig("md_splitk_reduce_flat", P, P, I64, I64, I32, I32, P)
 _sig("md_splitk_reduce", P, P, I64, I64, I64, I64, I32, I32, I32, P)
@@ -307,6 +313,13 @@ _sig("md_residual_delta", P, P, P, I64, P)
 _sig("md_step_probe_ws_doubles", I64, I64, POINTER(c_int64))
 _sig("md_step_probe", P, P, I64, I64, P, P)
 _sig("md_step_probe_finish", P, I64, P, P, P)
+# Muon (muon.py): workspace layout, momentum + normalise, the Newton-Schulz driver (a C loop over md_gemm_bf16), apply
+_sig("md_muon_ws_bytes", P, I32, POINTER(c_int64))
+_sig("md_muon_momentum", P, P, P, P, P, I32, F32, I32, F32, P, F32, I32, P, P, P, P, P)
+_sig("md_muon_newton_schulz", P, I32, I32, F32, F32, F32, P, P, P)
+_sig("md_muon_apply", P, P, P, P, P, I32, F32, F32, I32, F32, P, P, P)
+_sig("md_muon_axpby", P, P, P, F32, F32, I64, P)
+MUON_NORM_PARTS = 16            # MD_MUON_NORM_PARTS
 STEP_DELTA_MAX_BLOCKS = 2048    # MD_STEP_DELTA_MAX_BLOCKS
 STEP_PROBE_CHUNKS = 1024        # MD_STEP_PROBE_CHUNKS
 DISPERSE_MAX_B = 4096    # MD_DISPERSE_MAX_B

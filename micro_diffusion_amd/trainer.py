@@ -31,7 +31,10 @@ configs/*.yaml), re-designed for one process per GPU with RCCL over xGMI:
     one C-element AdamW launch behind the main optimiser pass;
   * dispersive loss (opt-in): `Trainer(disperse=DisperseLoss())` adds a batch-repulsion term on one backbone block's output to every
     microbatch's objective (disperse.py, Wang & He 2025): a Gram, md_disperse_pairs and one injection GEMM per microbatch, no
-    parameters, no collective on the step path.
+    parameters, no collective on the step path;
+  * Muon (opt-in): `Trainer(model, muon.Muon(model.dit, ...))` steps orthogonalised momentum on the hidden matrices of the blocks and
+    the unchanged AdamW kernel on everything else through the same `opt.step(...)` call (muon.py); the exchange
+    keeps the all-reduce form (`shardable = False`).
 """
 from __future__ import annotations
 
@@ -915,6 +918,11 @@ class Trainer:
             exchange = os.environ["MD_DP_EXCHANGE"]
         if transport == "auto":                # MD_COMM=native: the exchange through libmicrodit_comm.so instead of torch.distributed
             transport = os.environ.get("MD_COMM", "torch")
+        if not getattr(optimizer, "shardable", True):      # muon.Muon: orthogonalises whole matrices, a rank of the sharded step owns slices
+            if dp_mode == "sharded":
+                raise NotImplementedError(f"{type(optimizer).__name__} does not run under dp_mode='sharded' (a rank owns slices of "
+                                          "buckets, not whole matrices); use dp_mode='allreduce'")
+            dp_mode = "allreduce"
         model.dit._ensure_flat()
         self.sync = GradSync(model.dit, process_group, exchange=exchange, single_rank_exchange=single_rank_exchange, mode=dp_mode,
                              transport=transport)

@@ -30,6 +30,7 @@ def train(cfg: dict):
     lwopt = mdcfg.loss_weighting_options(cfg)    #  likewise: channels / lr checked here
     dsp = mdcfg.disperse_options(cfg)            #  likewise: weight / tau / block checked here
     lora = mdcfg.lora_options(cfg)               #  likewise: rank / targets checked, unsupported combinations refused
+    muon = mdcfg.muon_options(cfg)               #  likewise: momentum / steps / adjust / targets checked here
     if lora["enabled"] and not cfg["trainer"].get("load_path"):
         raise ValueError("misc.lora_rank needs trainer.load_path: the adapter is trained on a frozen, trained base")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -103,6 +104,13 @@ def train(cfg: dict):
         adapter.attach()
         opt = LoRAAdamW(adapter, lr=ocfg["lr"], betas=tuple(ocfg.get("betas", (0.9, 0.999))), eps=ocfg.get("eps", 1e-8),
                         weight_decay=lora["weight_decay"], **guard_kw)
+    elif muon["enabled"]:
+        # Muon: orthogonalised momentum on the hidden matrices of the blocks at the optimiser block's lr / weight_decay,
+        # AdamW (its betas / eps) on everything else; the data-parallel exchange keeps the all-reduce form
+        from micro_diffusion_amd.muon import Muon
+        opt = Muon(model.dit, lr=ocfg["lr"], momentum=muon["momentum"], nesterov=muon["nesterov"], ns_steps=muon["ns_steps"],
+                   adjust=muon["adjust"], targets=muon["targets"], adamw_lr=muon["adamw_lr"], betas=tuple(ocfg.get("betas", (0.9, 0.999))),
+                   eps=ocfg.get("eps", 1e-8), weight_decay=ocfg.get("weight_decay", 0.0), **ema_kw, **guard_kw, **posthoc_kw)
     else:
         opt = FusedAdamW(model.dit, lr=ocfg["lr"], betas=tuple(ocfg.get("betas", (0.9, 0.999))), eps=ocfg.get("eps", 1e-8),
                          weight_decay=ocfg.get("weight_decay", 0.0), **ema_kw, **guard_kw, **posthoc_kw)
