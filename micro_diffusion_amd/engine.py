@@ -23,11 +23,12 @@ import math
 import os
 import time
 from ctypes import byref
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import torch
 
-from . import hip
+from . import hip, splitk
 from .arch import BlockPlan, DiTConfig, caption_ffn_hidden, plan_blocks
 
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
@@ -36,7 +37,11 @@ TAIL_WS_BYTES = 256 * 256 * 256 * 4     # md_gemm_args.tail_ws: one raw 256 x 25
 
 class Tape:
     """Activations saved by one forward pass (plain attribute bag)."""
-    pass
+
+
+def launch(lib, stream, symbol, *args):
+    """One call into the native library, return code checked (hip.py: every launch function returns int and takes the stream last)."""
+    hip.check(getattr(lib, symbol)(*args, stream), symbol)
 
 
 def poison_(t: torch.Tensor) -> torch.Tensor:
@@ -177,8 +182,8 @@ class ResidualCache:
         """delta <- bf16(x_out - x_in): one launch."""
         if self.delta is None or self.delta.shape != x_in.shape or self.delta.device != x_in.device:
             self.delta = self._new(x_in.shape, x_in)
-        hip.check(hip.lib().md_residual_delta(x_out.data_ptr(), x_in.data_ptr(), self.delta.data_ptr(), x_in.numel(),
-                                              torch.cuda.current_stream().cuda_stream), "md_residual_delta")
+        launch(hip.lib(), torch.cuda.current_stream().cuda_stream, "md_residual_delta", x_out.data_ptr(), x_in.data_ptr(), self.delta.data_ptr(),
+               x_in.numel())
         self.B, self.T, self.version = B, T, version
 
     def probe(self, x: torch.Tensor, B: int, version=None):
@@ -202,8 +207,8 @@ class ResidualCache:
         if self._rel is None or self._rel.numel() != B or self._rel.device != x.device:
             self._rel = self._new(B, x, F32)
             self._rel_max = self._new(1, x, F32)
-        hip.check(L.md_step_probe(x.data_ptr(), self.ref.data_ptr(), B, per, self._ws.data_ptr(), st), "md_step_probe")
-        hip.check(L.md_step_probe_finish(self._ws.data_ptr(), B, self._rel.data_ptr(), self._rel_max.data_ptr(), st), "md_step_probe_finish")
+        launch(L, st, "md_step_probe", x.data_ptr(), self.ref.data_ptr(), B, per, self._ws.data_ptr())
+        launch(L, st, "md_step_probe_finish", self._ws.data_ptr(), B, self._rel.data_ptr(), self._rel_max.data_ptr())
         return self._rel_max
 
     @property
@@ -213,6 +218,12 @@ class ResidualCache:
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+def _Deferred(buf):
+    """What the blocks of one stack leave for ONE grouped launch behind the stack's backward: the bf16 matrix of the i-th block run in
+    buf[i] (the next free one: buf[len(w)]), the address of the weight it is contracted with in w[i]."""
+    return SimpleNamespace(buf=buf, w=[])
 
 
 class InputGrads:
@@ -377,7 +388,7 @@ class DiTEngine:
 
     def zeros(self, *shape, dtype=F32):
         t = self.empty(*shape, dtype=dtype)
-        hip.check(self.L.md_fill_zero(t.data_ptr(), t.numel() * t.element_size(), self._st()), "md_fill_zero")
+        self._launch("md_fill_zero", t.data_ptr(), t.numel() * t.element_size())
         return t
 
     def _prof(self, name, nbytes, launch):
@@ -391,6 +402,18 @@ class DiTEngine:
         e1.record()
         kp.setdefault(name, []).append((e0, e1, float(nbytes)))
 
+    def _launch(self, symbol, *args, prof=None, nbytes=0.0):
+        """self.L.<symbol>(*args, launch stream), checked; prof / nbytes: its kernel_profile class and algorithmic bytes (bench.py)."""
+        if prof is None or self.kernel_profile is None:
+            return launch(self.L, self._st(), symbol, *args)
+        self._prof(prof, nbytes, lambda: launch(self.L, self._st(), symbol, *args))
+
+    def _launch_det(self, symbol, ws_key, *args, prof, nbytes):
+        """`symbol`, or -- deterministic mode -- `symbol`_det, which takes the workspace of _det_ws(*ws_key) and its size as well."""
+        if self.deterministic:
+            symbol, args = symbol + "_det", args + self._det_ws(*ws_key)
+        self._launch(symbol, *args, prof=prof, nbytes=nbytes)
+
     def _det_ws(self, kind, rows, rps, rpb, C):
         """(pointer, floats) of the workspace a deterministic reduction of this shape needs ((None, 0): none).  The size is asked once
         per shape; the buffer comes from the current arena (or the allocator) and is dead when the launch has run."""
@@ -400,52 +423,39 @@ class DiTEngine:
             out = ctypes.c_int64(0)
             hip.check(self.L.md_det_ws_floats(kind, rows, rps, rpb, C, byref(out)), "md_det_ws_floats")
             n = self._det_ws_floats[key] = int(out.value)
-        if n == 0:
-            return None, 0
-        return self.empty(n, dtype=F32).data_ptr(), n
+        return (self.empty(n, dtype=F32).data_ptr(), n) if n else (None, 0)
 
     def _colsum(self, src_ptr, is_f32, ld, out_ptr, rows, C):
         """out[c] += column sums (bias gradients)."""
-        nbytes = (4.0 if is_f32 else 2.0) * rows * C
-        if not self.deterministic:
-            return self._prof("colsum", nbytes, lambda: hip.check(self.L.md_colsum(src_ptr, is_f32, ld, out_ptr, rows, C, self._st()), "colsum"))
-        ws, n = self._det_ws(hip.DET_COLSUM, rows, 0, 0, C)
-        self._prof("colsum", nbytes,
-                   lambda: hip.check(self.L.md_colsum_det(src_ptr, is_f32, ld, out_ptr, rows, C, ws, n, self._st()), "colsum_det"))
+        self._launch_det("md_colsum", (hip.DET_COLSUM, rows, 0, 0, C), src_ptr, is_f32, ld, out_ptr, rows, C, prof="colsum",
+                         nbytes=(4.0 if is_f32 else 2.0) * rows * C)
 
     def _gate_bwd(self, dx, br, gate_ptr, ldgate, dbr, dgate_ptr, lddg, M, d, S, rpb):
         """adaLN-Zero gate backward: dbr = gate * dx, dgate += per-sample column sums of dx * br."""
-        if not self.deterministic:
-            return self._prof("gate_bwd", 6.0 * M * d, lambda: hip.check(self.L.md_gate_bwd(
-                dx.data_ptr(), br.data_ptr(), gate_ptr, ldgate, dbr.data_ptr(), dgate_ptr, lddg, M, d, S, rpb, self._st()), "gate_bwd"))
-        ws, n = self._det_ws(hip.DET_GATE_BWD, M, S, rpb, d)
-        self._prof("gate_bwd", 6.0 * M * d, lambda: hip.check(self.L.md_gate_bwd_det(
-            dx.data_ptr(), br.data_ptr(), gate_ptr, ldgate, dbr.data_ptr(), dgate_ptr, lddg, M, d, S, rpb, ws, n, self._st()), "gate_bwd_det"))
+        self._launch_det("md_gate_bwd", (hip.DET_GATE_BWD, M, S, rpb, d), dx.data_ptr(), br.data_ptr(), gate_ptr, ldgate, dbr.data_ptr(), dgate_ptr,
+                         lddg, M, d, S, rpb, prof="gate_bwd", nbytes=6.0 * M * d)
 
     def _qkln_fwd(self, ptr, rows, ld, off, width, rstd_ptr, nseg=1):
         """nseg = 2: the q and the k half (adjacent, `width` apart) of a packed qkv row in one launch; rstd [nseg][rows]."""
-        self._prof("qk_layernorm", 4.0 * rows * width * nseg, lambda: hip.check(
-            self.L.md_qkln_fwd(ptr, rows, ld, off, width, nseg, width, rstd_ptr, self.cfg.norm_eps, self._st()), "md_qkln_fwd"))
+        self._launch("md_qkln_fwd", ptr, rows, ld, off, width, nseg, width, rstd_ptr, self.cfg.norm_eps, prof="qk_layernorm",
+                     nbytes=4.0 * rows * width * nseg)
 
     def _qkln_bwd(self, dptr, ldd, doff, yptr, ldy, yoff, rows, width, rstd_ptr, nseg=1):
-        self._prof("qk_layernorm", 6.0 * rows * width * nseg, lambda: hip.check(
-            self.L.md_qkln_bwd(dptr, ldd, doff, yptr, ldy, yoff, rows, width, nseg, width, width, rstd_ptr, self._st()), "md_qkln_bwd"))
+        self._launch("md_qkln_bwd", dptr, ldd, doff, yptr, ldy, yoff, rows, width, nseg, width, width, rstd_ptr, prof="qk_layernorm",
+                     nbytes=6.0 * rows * width * nseg)
 
     def _qkln_fwd_hm(self, ptr, rows, ld, off, width, out, S, rstd_ptr, nseg=1):
         """As _qkln_fwd, the normalised values going head-major to out [nseg][B, H, S, hd]; the input stays as it is."""
-        self._prof("qk_layernorm", 4.0 * rows * width * nseg, lambda: hip.check(
-            self.L.md_qkln_fwd_hm(ptr, rows, ld, off, width, nseg, width, out.data_ptr(), rows * width, S, self.cfg.head_dim, rstd_ptr,
-                                  self.cfg.norm_eps, self._st()), "md_qkln_fwd_hm"))
+        self._launch("md_qkln_fwd_hm", ptr, rows, ld, off, width, nseg, width, out.data_ptr(), rows * width, S, self.cfg.head_dim, rstd_ptr,
+                     self.cfg.norm_eps, prof="qk_layernorm", nbytes=4.0 * rows * width * nseg)
 
     def _qkln_bwd_hm(self, dy, y, dptr, ldd, doff, rows, width, S, rstd_ptr, nseg=1):
         """dy, y: head-major [nseg][B, H, S, hd]; dL/dx goes row-major to dptr (segments `width` apart, as in _qkln_bwd)."""
-        self._prof("qk_layernorm", 6.0 * rows * width * nseg, lambda: hip.check(
-            self.L.md_qkln_bwd_hm(dy.data_ptr(), rows * width, y.data_ptr(), rows * width, dptr, ldd, doff, width, rows, width, nseg, S,
-                                  self.cfg.head_dim, rstd_ptr, self._st()), "md_qkln_bwd_hm"))
+        self._launch("md_qkln_bwd_hm", dy.data_ptr(), rows * width, y.data_ptr(), rows * width, dptr, ldd, doff, width, rows, width, nseg, S,
+                     self.cfg.head_dim, rstd_ptr, prof="qk_layernorm", nbytes=6.0 * rows * width * nseg)
 
     def _attn_fwd(self, a):
-        nb = 2.0 * a.hd * (2 * a.Sq + 2 * a.Skv) * a.B * a.H
-        self._prof("attention", nb, lambda: hip.check(self.L.md_attn_fwd(byref(a), self._st()), "md_attn_fwd"))
+        self._launch("md_attn_fwd", byref(a), prof="attention", nbytes=2.0 * a.hd * (2 * a.Sq + 2 * a.Skv) * a.B * a.H)
 
     def _gemm(self, **kw):
         a = hip.GemmArgs()
@@ -527,39 +537,56 @@ class DiTEngine:
         return (w2.data_ptr() == w1.data_ptr() + w1.numel() * 2 and
                 self.G[pre + ".w2.weight"].data_ptr() == self.G[pre + ".w1.weight"].data_ptr() + w1.numel() * 4)
 
-    def _ksplit(self, out_rows, out_cols, contraction, batch=1):
-        """Split-K factor for GEMMs whose output is too small to fill the chip (weight gradients, skinny dgrads).
+    def _swiglu_ffn_fwd(self, pre, xin, rows, d, f, t, *, res, out=None, gate=None, ldg=0, rps=0, C2=None):
+        """res + [gate *] w3(silu(w1 x) * w2 x) for xin [rows, d] (FeedForward, dit.py:88-89); saves h12 = [w1 x | w2 x] and a on tape t.
+        out: the caller's buffer (the DiT block allocates it in front of the tape's), else allocated here, behind a."""
+        t.h12 = self.empty(rows, 2 * f)
+        if self._fused12(pre):
+            self.lin_fwd(xin, pre + ".w1", t.h12, rows, 2 * f, d)          # [w1; w2] as one [2f, d] weight
+        else:
+            self.lin_fwd(xin, pre + ".w1", t.h12, rows, f, d, ldc=2 * f)
+            self.lin_fwd(xin, pre + ".w2", t.h12, rows, f, d, ldc=2 * f, ooff=f)
+        t.a = self.empty(rows, f)
+        self._launch("md_swiglu_fwd", t.h12.data_ptr(), 2 * f, t.a.data_ptr(), f, rows, f, prof="swiglu", nbytes=6.0 * rows * f)
+        if out is None:
+            out = self.empty(rows, d)
+        self.lin_fwd(t.a, pre + ".w3", out, rows, d, f, mode=hip.EPI_RESIDUAL, res=res, gate=gate, ldg=ldg, rps=rps, C2=C2)
+        return out
 
-        Preferred: a factor the persistent 256 x 256 kernel (pp256) accepts — the contraction per split a multiple of 128 —
-        chosen by a small cost model of that kernel (profiles/r2_wgrad_splitk_pp256.txt): the tiles x splits work items
-        are dealt out to the 256 CUs, a workgroup needs ~1.9 us per 64-deep k-tile plus ~5 us to write a 256 x 256 fp32
-        slice, and the slice reduction moves (ks + 2) x the output once at ~4 TB/s.  Otherwise (ragged contraction,
-        tiny outputs) the round-1 rule for the 2-stage kernels: ~3 workgroups of 128 x 128 per CU, >= 512 k per split."""
-        ws_cap = max(1, self.ws.numel() // (out_rows * out_cols * batch))
-        t256 = ((out_rows + 255) // 256) * ((out_cols + 255) // 256) * batch
-        if getattr(self, "short_k_accum", True) and contraction <= 512 and t256 >= 64:
-            return 1        # a short contraction into a large output (the adaLN weight gradients: 256 tokens into 6144 x 1024) is
-            #                 pure output traffic: accumulate in place (one read + one write) instead of slices + a reduction pass
-        if contraction % 128 == 0 and out_cols % 8 == 0:
-            units = contraction // 128
-            out_us = out_rows * out_cols * batch * 4 / 4e6
-            best, best_cost = None, None
-            # ks = 1 is a candidate too: a launch with enough tiles of its own (the 8-expert weight gradients) writes ONE fp32
-            # slice to the workspace and the reduction pass adds it to the accumulator -- 3 passes over the output instead of the
-            # 2 slices + 4 passes the smallest split costs, on the persistent kernel instead of the 2-stage accumulate epilogue
-            for ks in range(1, min(64, ws_cap, units) + 1):
-                if units % ks or t256 * ks < getattr(self, "ksplit_min_items", 192):   # md_gemm_bf16's AUTO rule sends
-                    continue                                                           # < 192 tiles to the 2-stage kernels
-                per_wg = -(-t256 * ks // 256)
-                cost = per_wg * (contraction / ks / 64 * 1.9 + 5.0) + (ks + 2) * out_us
-                if best_cost is None or cost < best_cost:
-                    best, best_cost = ks, cost
-            if best is not None:
-                return best if best > 1 else -1          # -1: one slice through the workspace (pp256), not the accumulate epilogue
-        tiles = ((out_rows + 127) // 128) * ((out_cols + 127) // 128) * batch
-        ks = max(1, self.wgrad_target_blocks // tiles)
-        ks = min(ks, max(1, contraction // 512))
-        return max(1, min(ks, ws_cap))
+    def _swiglu_ffn_bwd(self, pre, t, dout, xin, rows, d, f, *, defer, try_fused, dxin=None):
+        """dout [rows, d], the gradient of the w3 output -> the gradient of xin (dxin: the caller's buffer, else allocated here), taking the
+        weight gradients of w3 and [w1; w2] (defer: into the open group).  try_fused: first try da = dout @ W3 with the SwiGLU backward in
+        the GEMM epilogue (EPI_SWIGLU_BWD; da never exists in memory); the library refuses ragged tiles or a CU hold: then two launches."""
+        self.lin_wgrad(dout, t.a, pre + ".w3", rows, d, f, defer=defer)
+        fused = False
+        if try_fused:                      # (the two callers allocate in their own order: the arenas are bump allocators)
+            dh12 = self.empty(rows, 2 * f)
+            fused = self.fuse_swiglu_bwd and self._gemm(
+                A=dout.data_ptr(), B=self.S[pre + ".w3.weight"].data_ptr(), C=dh12.data_ptr(), aux=t.h12.data_ptr(), M=rows, N=f, K=d, lda=d,
+                ldb=f, ldc=2 * f, ldaux=2 * f, batch=1, ksplit=1, a_kcontig=1, b_kcontig=0, mode=hip.EPI_SWIGLU_BWD, act=0, alpha=1.0, _try=True)
+        if not fused:
+            da = self.empty(rows, f)
+            self.lin_dgrad(dout, pre + ".w3", da, rows, d, f)
+            if not try_fused:
+                dh12 = self.empty(rows, 2 * f)
+            self._launch("md_swiglu_bwd", da.data_ptr(), f, t.h12.data_ptr(), 2 * f, dh12.data_ptr(), 2 * f, rows, f, prof="swiglu",
+                         nbytes=10.0 * rows * f)
+        if dxin is None:
+            dxin = self.empty(rows, d)
+        if self._fused12(pre):
+            self.lin_wgrad(dh12, xin, pre + ".w1", rows, 2 * f, d, defer=defer)
+            self.lin_dgrad(dh12, pre + ".w1", dxin, rows, 2 * f, d)
+        else:
+            self.lin_wgrad(dh12, xin, pre + ".w1", rows, f, d, lddy=2 * f, defer=defer)
+            self.lin_wgrad(dh12, xin, pre + ".w2", rows, f, d, lddy=2 * f, dyoff=f, defer=defer)
+            self.lin_dgrad(dh12, pre + ".w1", dxin, rows, f, d, lddy=2 * f)
+            self.lin_dgrad(dh12, pre + ".w2", dxin, rows, f, d, lddy=2 * f, dyoff=f, mode=hip.EPI_RESIDUAL, res=dxin)
+        return dxin
+
+    def _ksplit(self, out_rows, out_cols, contraction, batch=1):
+        """Split-K factor of a GEMM too small to fill the chip: splitk.choose_ksplit with this engine's workspace and A/B switches."""
+        return splitk.choose_ksplit(out_rows, out_cols, contraction, batch, ws_floats=self.ws.numel(), target_blocks=self.wgrad_target_blocks,
+                                    min_items=self.ksplit_min_items, short_k_accum=self.short_k_accum)
 
     def gemm_f32_acc(self, *, out_ptr, M, N, K, ldo, batch=1, sOut=0, accumulate=True, **operands):
         """fp32 C (+)= A B^T with automatic split-K: partial products go to a workspace as dense fp32 slices and are
@@ -572,30 +599,26 @@ class DiTEngine:
         if bf_ptr is not None and not via_ws and ldo % 8:
             via_ws = True                 # a bf16 row pitch the GEMM epilogue cannot store (16-byte pieces): one slice + the reduction
         if not via_ws:
-            if bf_ptr is not None:
-                self._gemm(C=bf_ptr, M=M, N=N, K=K, ldc=ldo, sC=sOut, batch=batch, ksplit=1, mode=hip.EPI_STORE_BF16, act=0, alpha=1.0,
-                           **operands)
-                return
-            self._gemm(C=out_ptr, M=M, N=N, K=K, ldc=ldo, sC=sOut, batch=batch, ksplit=1,
-                       mode=hip.EPI_ACCUM_F32 if accumulate else hip.EPI_STORE_F32, act=0, alpha=1.0, **operands)
+            mode = hip.EPI_STORE_BF16 if bf_ptr is not None else hip.EPI_ACCUM_F32 if accumulate else hip.EPI_STORE_F32
+            self._gemm(C=bf_ptr or out_ptr, M=M, N=N, K=K, ldc=ldo, sC=sOut, batch=batch, ksplit=1, mode=mode, act=0, alpha=1.0, **operands)
             return
         if self.splitk_force_pp and self.gemm_prefer == hip.GEMM_AUTO:
             operands = dict(operands, variant=hip.GEMM_PP256)
         self._gemm(C=self.ws.data_ptr(), M=M, N=N, K=K, ldc=N, sC=ks * M * N, sSplit=M * N, batch=batch, ksplit=ks,
                    mode=hip.EPI_STORE_F32, act=0, alpha=1.0, **operands)
-        if bf_ptr is not None:
-            self._prof("splitk_reduce", M * N * batch * (4.0 * ks + 2), lambda: hip.check(
-                self.L.md_splitk_reduce(self.ws.data_ptr(), bf_ptr, M, N, ldo, sOut, ks, batch, 2, self._st()), "md_splitk_reduce"))
-            return
-        self._prof("splitk_reduce", 4.0 * M * N * batch * (ks + (2 if accumulate else 1)), lambda: hip.check(
-            self.L.md_splitk_reduce(self.ws.data_ptr(), out_ptr, M, N, ldo, sOut, ks, batch, 1 if accumulate else 0, self._st()),
-            "md_splitk_reduce"))
+        mode, nbytes = (2, M * N * batch * (4.0 * ks + 2)) if bf_ptr is not None else (int(accumulate), 4.0 * M * N * batch * (ks + 1 + int(accumulate)))
+        self._launch("md_splitk_reduce", self.ws.data_ptr(), bf_ptr or out_ptr, M, N, ldo, sOut, ks, batch, mode, prof="splitk_reduce", nbytes=nbytes)
+
+    def _acc_each(self, out_ptr, M, N, K, pairs, *, lda, ldb, a_kcontig):
+        """out[M, N] += A_i B_i^T, one gemm_f32_acc per (A, B) pair with B K-strided: what a grouped launch falls back to."""
+        for A, B in pairs:
+            self.gemm_f32_acc(out_ptr=out_ptr, M=M, N=N, K=K, ldo=N, A=A, B=B, lda=lda, ldb=ldb, a_kcontig=a_kcontig, b_kcontig=0)
 
     def _wgrad_bf16_target(self, out_ptr, numel):
         """Address in the bf16 exchange buffer a weight gradient of this step is stored at, or None (not a one-microbatch step, the
         output is not a gradient accumulator, or the tensor is not dense).  A second gradient for the same tensor within one backward
         would have to be ADDED: no layer of the model does that; it raises instead of silently dropping the first."""
-        t = getattr(self, "wgrad_bf16", None)      # (host-logic tests build the engine without __init__)
+        t = self.wgrad_bf16
         if t is None or numel is None or not (t["g_lo"] <= out_ptr < t["g_hi"]):
             return None
         if out_ptr in t["written"]:
@@ -620,9 +643,8 @@ class DiTEngine:
             grp.append(dict(tokens=M, A=dy.data_ptr() + 2 * dyoff, lda=lddy or N, B=x.data_ptr() + 2 * xoff, ldb=ldx or K, M=N, N=K,
                             out=self.G[wname + ".weight"].data_ptr(), keep=(dy, x)))
             return
-        self.gemm_f32_acc(out_ptr=self.G[wname + ".weight"].data_ptr(), M=N, N=K, K=M, ldo=K,
-                          A=dy.data_ptr() + 2 * dyoff, B=x.data_ptr() + 2 * xoff, lda=lddy or N, ldb=ldx or K,
-                          a_kcontig=0, b_kcontig=0)
+        self._acc_each(self.G[wname + ".weight"].data_ptr(), N, K, M, [(dy.data_ptr() + 2 * dyoff, x.data_ptr() + 2 * xoff)],
+                       lda=lddy or N, ldb=ldx or K, a_kcontig=0)
 
     def _param_acc(self, **kw):
         """gemm_f32_acc into a tensor of self.G (the weight gradients that are not a Linear's: experts, patch embedding)."""
@@ -643,65 +665,27 @@ class DiTEngine:
         grp, self._wgroup = self._wgroup, ([] if self._wgroup is not None else None)
         if not grp:
             return
-        if len(grp) == 1:
-            g = grp[0]
-            self.gemm_f32_acc(out_ptr=g["out"], M=g["M"], N=g["N"], K=g["tokens"], ldo=g["N"], A=g["A"], B=g["B"], lda=g["lda"],
-                              ldb=g["ldb"], a_kcontig=0, b_kcontig=0)
-            return
         grp.sort(key=lambda g: g["out"])
-        base = grp[0]["out"]
-        span = max(g["out"] + 4 * g["M"] * g["N"] for g in grp) - base
-        span_el = span // 4
-        tokens = grp[0]["tokens"]
-        units = tokens // 128
-        t256 = sum(((g["M"] + 255) // 256) * ((g["N"] + 255) // 256) for g in grp)
-        out_us = sum(g["M"] * g["N"] for g in grp) * 4 / 4e6
-        ws_cap = self.ws.numel() // span_el
-        best, best_cost = None, None
-        for ks in range(1, min(64, ws_cap, units) + 1):
-            if units % ks:
-                continue
-            per_wg = -(-t256 * ks // 256)
-            cost = per_wg * (tokens / ks / 64 * 1.9 + 5.0) + (ks + 2) * out_us
-            if t256 * ks < 192:
-                cost *= 192.0 / (t256 * ks)            # an under-filled chip: the round costs the same with fewer tiles done
-            if best_cost is None or cost < best_cost:
-                best, best_cost = ks, cost
-        if best is None:                                # does not fit the workspace: one by one
+        plan = splitk.plan_wgrad_group([(g["out"], g["M"], g["N"]) for g in grp], grp[0]["tokens"], self.ws.numel())
+        if plan is None:                                # a single problem, or the slices do not fit the workspace: one by one
             for g in grp:
-                self.gemm_f32_acc(out_ptr=g["out"], M=g["M"], N=g["N"], K=g["tokens"], ldo=g["N"], A=g["A"], B=g["B"], lda=g["lda"],
-                                  ldb=g["ldb"], a_kcontig=0, b_kcontig=0)
+                self._acc_each(g["out"], g["M"], g["N"], g["tokens"], [(g["A"], g["B"])], lda=g["lda"], ldb=g["ldb"], a_kcontig=0)
             return
-        ks = best
-        probs = (hip.GemmProblem * len(grp))()
-        for i, g in enumerate(grp):
-            probs[i] = hip.GemmProblem(g["A"], g["B"], g["lda"], g["ldb"], g["M"], g["N"], (g["out"] - base) // 4)
+        ks, base = plan.ks, grp[0]["out"]
+        probs = (hip.GemmProblem * len(grp))(*(hip.GemmProblem(g["A"], g["B"], g["lda"], g["ldb"], g["M"], g["N"], off)
+                                               for g, off in zip(grp, plan.offsets)))
         g0 = grp[0]
-        self._gemm(A=g0["A"], B=g0["B"], C=self.ws.data_ptr(), M=g0["M"], N=g0["N"], K=tokens, lda=g0["lda"], ldb=g0["ldb"], ldc=g0["N"],
-                   sSplit=span_el, batch=1, ksplit=ks, a_kcontig=0, b_kcontig=0, mode=hip.EPI_STORE_F32, act=0, alpha=1.0,
+        self._gemm(A=g0["A"], B=g0["B"], C=self.ws.data_ptr(), M=g0["M"], N=g0["N"], K=g0["tokens"], lda=g0["lda"], ldb=g0["ldb"], ldc=g0["N"],
+                   sSplit=plan.span, batch=1, ksplit=ks, a_kcontig=0, b_kcontig=0, mode=hip.EPI_STORE_F32, act=0, alpha=1.0,
                    problems=ctypes.addressof(probs), n_problems=len(grp), _problems=grp)
-        # contiguous runs of gradient tensors -> one flat reduction each
-        runs, cur = [], [grp[0]["out"], grp[0]["out"] + 4 * grp[0]["M"] * grp[0]["N"]]
-        for g in grp[1:]:
-            if g["out"] == cur[1]:
-                cur[1] = g["out"] + 4 * g["M"] * g["N"]
-            else:
-                runs.append(cur)
-                cur = [g["out"], g["out"] + 4 * g["M"] * g["N"]]
-        runs.append(cur)
         bf = [self._wgrad_bf16_target(g["out"], g["M"] * g["N"]) for g in grp]
         to_bf16 = all(b is not None for b in bf)
         assert to_bf16 or not any(b is not None for b in bf)        # a group lies in the gradient buffer as a whole, or not at all
-        for lo, hi in runs:
-            n = (hi - lo) // 4
-            if to_bf16:
-                t = self.wgrad_bf16
-                dst = t["gbf"] + (lo - t["g_lo"]) // 2
-                self._prof("splitk_reduce", n * (4.0 * ks + 2), lambda lo=lo, n=n, dst=dst: hip.check(
-                    self.L.md_splitk_reduce_flat(self.ws.data_ptr() + (lo - base), dst, n, span_el, ks, 2, self._st()), "md_splitk_reduce_flat"))
-                continue
-            self._prof("splitk_reduce", 4.0 * n * (ks + 2), lambda lo=lo, n=n: hip.check(
-                self.L.md_splitk_reduce_flat(self.ws.data_ptr() + (lo - base), lo, n, span_el, ks, 1, self._st()), "md_splitk_reduce_flat"))
+        t = self.wgrad_bf16
+        for off, n in plan.runs:                                    # one flat reduction per contiguous run of gradient tensors
+            lo = base + 4 * off
+            dst, mode, nbytes = (t["gbf"] + (lo - t["g_lo"]) // 2, 2, n * (4.0 * ks + 2)) if to_bf16 else (lo, 1, 4.0 * n * (ks + 2))
+            self._launch("md_splitk_reduce_flat", self.ws.data_ptr() + 4 * off, dst, n, plan.span, ks, mode, prof="splitk_reduce", nbytes=nbytes)
 
     def ln_args(self, x, wname, out, rows, C, *, shift=None, scale=None, ldmod=0, rps=0, mean=None, rstd=None, act=0,
                 pos=None, pos_rows=0):
@@ -709,7 +693,7 @@ class DiTEngine:
                           _p(mean), _p(rstd), rows, C, C, C, ldmod, rps, pos_rows, self.cfg.norm_eps, act)
 
     def ln_fwd(self, a):
-        self._prof("layernorm", 4.0 * a.rows * a.C, lambda: hip.check(self.L.md_ln_fwd(byref(a), self._st()), "md_ln_fwd"))
+        self._launch("md_ln_fwd", byref(a), prof="layernorm", nbytes=4.0 * a.rows * a.C)
 
     @staticmethod
     def _rows_per_block(rows, rps, min_blocks=2048):
@@ -736,13 +720,8 @@ class DiTEngine:
             dscale, ldg = scratch.data_ptr(), a.C
         b = hip.LnBwdArgs(dz.data_ptr(), _p(dx), dscale, dshift, _p(self.G[wname + ".weight"]) if wname else None,
                           a.C, a.C, ldg, rpb, 1 if accumulate else 0, is_out)
-        if self.deterministic:
-            ws, n = self._det_ws(hip.DET_LN_BWD, a.rows, rps, rpb, a.C)
-            self._prof("layernorm", (8.0 if accumulate else 6.0) * a.rows * a.C,
-                       lambda: hip.check(self.L.md_ln_bwd_det(byref(a), byref(b), ws, n, self._st()), "md_ln_bwd_det"))
-            return
-        self._prof("layernorm", (8.0 if accumulate else 6.0) * a.rows * a.C,
-                   lambda: hip.check(self.L.md_ln_bwd(byref(a), byref(b), self._st()), "md_ln_bwd"))
+        self._launch_det("md_ln_bwd", (hip.DET_LN_BWD, a.rows, rps, rpb, a.C), byref(a), byref(b), prof="layernorm",
+                         nbytes=(8.0 if accumulate else 6.0) * a.rows * a.C)
 
     def attn_args(self, q, k, v, o, lse, B, H, Sq, Skv, ldq, ldk, ldv, hid, *, do=None, dq=None, dk=None, dv=None,
                   delta=None, lddq=0, lddk=0, lddv=0, hm_qk=False):
@@ -775,7 +754,7 @@ class DiTEngine:
     # ------------------------------------------------------------------------------------------ attention layers
     def _self_attn_fwd(self, pre, xin, B, S, dim, hid, heads, t):
         """xin [B*S, dim] -> o [B*S, hid]; saves qkv (post-LN), rstd, lse on tape t."""
-        M, L, st = B * S, self.L, self._st()
+        M = B * S
         qkv = self.empty(M, 3 * hid)
         self.lin_fwd(xin, pre + ".qkv", qkv, M, 3 * hid, dim)
         rq = self.empty(2, M, dtype=F32)
@@ -797,7 +776,7 @@ class DiTEngine:
 
     def _self_attn_bwd(self, pre, xin, do, B, S, dim, hid, heads, t, defer=False):
         """do [M, hid] -> returns d_xin [M, dim]; accumulates the qkv weight grad."""
-        M, L, st = B * S, self.L, self._st()
+        M = B * S
         dqkv = self.empty(M, 3 * hid)
         delta = self.empty(B, heads, S, dtype=F32)
         qkv = t.qkv
@@ -841,7 +820,7 @@ class DiTEngine:
         read; inference only: the tape holds no K rstd for a backward).
         keep: (ids_restore [B, S] int32, Tk) when only the tokens with ids_restore < Tk of this block's output are ever read (the
         last patch-mixer block under masking): a MoE block then runs its experts on the routed rows of those tokens alone."""
-        L, st, cfg = self.L, self._st(), self.cfg
+        cfg = self.cfg
         d, h, hx, f = bp.dim, bp.attn_hidden, bp.xattn_hidden, bp.ffn_hidden
         M, Mc, D = B * S, B * Lc, cfg.dim
         n = bp.name
@@ -909,16 +888,7 @@ class DiTEngine:
         t.br3 = self.empty(M, d)
         gate_mlp = mp + 2 * 5 * d
         if not bp.moe:
-            t.h12 = self.empty(M, 2 * f)
-            if self._fused12(n + ".mlp"):
-                self.lin_fwd(t.xm3, n + ".mlp.w1", t.h12, M, 2 * f, d)          # [w1; w2] as one [2f, d] weight
-            else:
-                self.lin_fwd(t.xm3, n + ".mlp.w1", t.h12, M, f, d, ldc=2 * f)
-                self.lin_fwd(t.xm3, n + ".mlp.w2", t.h12, M, f, d, ldc=2 * f, ooff=f)
-            t.a = self.empty(M, f)
-            self._prof("swiglu", 6.0 * M * f, lambda: hip.check(L.md_swiglu_fwd(t.h12.data_ptr(), 2 * f, t.a.data_ptr(), f, M, f, st), "swiglu"))
-            self.lin_fwd(t.a, n + ".mlp.w3", x3, M, d, f, mode=hip.EPI_RESIDUAL, res=x2, gate=gate_mlp, ldg=ldm, rps=S,
-                         C2=t.br3)
+            self._swiglu_ffn_fwd(n + ".mlp", t.xm3, M, d, f, t, out=x3, res=x2, gate=gate_mlp, ldg=ldm, rps=S, C2=t.br3)
         else:
             E = cfg.num_experts
             k = int(cfg.expert_capacity * S / E)
@@ -931,8 +901,8 @@ class DiTEngine:
             t.rowidx = self.empty(E, Bk, dtype=I32)
             t.gval = self.empty(E, Bk, dtype=F32)
             t.slot = self.empty(M, E, dtype=I32)
-            hip.check(L.md_moe_route(logits.data_ptr(), t.probs.data_ptr(), ldl, B, S, E, k, t.rowidx.data_ptr(),
-                                     t.gval.data_ptr(), t.slot.data_ptr(), st), "moe_route")
+            self._launch("md_moe_route", logits.data_ptr(), t.probs.data_ptr(), ldl, B, S, E, k, t.rowidx.data_ptr(), t.gval.data_ptr(),
+                         t.slot.data_ptr())
             if self.route_override is not None and n in self.route_override:
                 self._override_routing(t, self.route_override[n], B, S, E, k)
             if self.route_stats is not None:    # after the injection: the statistics describe the routing the layer runs with
@@ -943,10 +913,9 @@ class DiTEngine:
             rows = t.cap or Bk
             t.xin = self.empty(E, Bk, d)
             if t.cap is None:
-                hip.check(L.md_gather_rows(t.xm3.data_ptr(), d, t.rowidx.data_ptr(), t.xin.data_ptr(), d, E * Bk, d, st), "gather")
+                self._launch("md_gather_rows", t.xm3.data_ptr(), d, t.rowidx.data_ptr(), t.xin.data_ptr(), d, E * Bk, d)
             else:
-                hip.check(L.md_moe_gather_compact(t.xm3.data_ptr(), d, t.rowidx_c.data_ptr(), t.xin.data_ptr(), E, rows, Bk, d, st),
-                          "gather_compact")
+                self._launch("md_moe_gather_compact", t.xm3.data_ptr(), d, t.rowidx_c.data_ptr(), t.xin.data_ptr(), E, rows, Bk, d)
             t.hpre = self.empty(E, Bk, f)         # the pre-activation -- or, with moe_cache_dact, gelu'(pre-activation): nothing but
             t.hact = self.empty(E, Bk, f)         # the backward's activation derivative ever reads it (md_gemm_args.dact_cached)
             t.hpre_is_dact = 1 if self.moe_cache_dact else 0
@@ -959,11 +928,11 @@ class DiTEngine:
                        sA=Bk * f, sB=f * d, sC=Bk * d, batch=E, ksplit=1, a_kcontig=1, b_kcontig=0, mode=hip.EPI_STORE_BF16,
                        act=0, alpha=1.0)
             if t.cap is None:
-                hip.check(L.md_moe_combine(t.h2.data_ptr(), t.gval.data_ptr(), t.slot.data_ptr(), x2.data_ptr(), gate_mlp, ldm,
-                                           t.br3.data_ptr(), x3.data_ptr(), B, S, E, k, d, st), "moe_combine")
+                self._launch("md_moe_combine", t.h2.data_ptr(), t.gval.data_ptr(), t.slot.data_ptr(), x2.data_ptr(), gate_mlp, ldm, t.br3.data_ptr(),
+                             x3.data_ptr(), B, S, E, k, d)
             else:       # every token row is written: a dropped token gets br3 = 0 and x3 = x2
-                hip.check(L.md_moe_combine_abs(t.h2.data_ptr(), t.gval_c.data_ptr(), t.slot_c.data_ptr(), x2.data_ptr(), gate_mlp, ldm,
-                                               t.br3.data_ptr(), x3.data_ptr(), B, S, E, Bk, d, st), "moe_combine_abs")
+                self._launch("md_moe_combine_abs", t.h2.data_ptr(), t.gval_c.data_ptr(), t.slot_c.data_ptr(), x2.data_ptr(), gate_mlp, ldm,
+                             t.br3.data_ptr(), x3.data_ptr(), B, S, E, Bk, d)
             if self.route_log is not None:
                 self.route_log += ["moe_route", "gather" if t.cap is None else "gather_compact", "combine" if t.cap is None else "combine_abs"]
         return x3, t
@@ -980,9 +949,8 @@ class DiTEngine:
         t.slot_c = self.empty(B * S, E, dtype=I32)
         count = self.empty(16, dtype=I32)
         ws = self.empty(E * ((Bk + 1023) // 1024), dtype=I32)
-        hip.check(self.L.md_moe_compact_kept(t.rowidx.data_ptr(), t.gval.data_ptr(), ids_restore.data_ptr(), Tk, B, S, E, k,
-                                             t.rowidx_c.data_ptr(), t.gval_c.data_ptr(), count.data_ptr(), t.slot_c.data_ptr(),
-                                             ws.data_ptr(), ws.numel(), self._st()), "moe_compact_kept")
+        self._launch("md_moe_compact_kept", t.rowidx.data_ptr(), t.gval.data_ptr(), ids_restore.data_ptr(), Tk, B, S, E, k, t.rowidx_c.data_ptr(),
+                     t.gval_c.data_ptr(), count.data_ptr(), t.slot_c.data_ptr(), ws.data_ptr(), ws.numel())
         if self.route_log is not None:
             self.route_log.append("compact_kept")
         if self._prune_host is None:
@@ -1012,7 +980,7 @@ class DiTEngine:
 
     def _block_bwd(self, bp: BlockPlan, t: Tape, dx, ycond, dycond_f32, B, S, Lc, gc, dgc_f32, group=None, kvgroup=None):
         """dx: grad w.r.t. the block output [M, d] (bf16), updated IN PLACE to the grad w.r.t. the block input."""
-        L, st, cfg = self.L, self._st(), self.cfg
+        cfg = self.cfg
         d, h, hx, f = bp.dim, bp.attn_hidden, bp.xattn_hidden, bp.ffn_hidden
         M, Mc, D = B * S, B * Lc, cfg.dim
         n = bp.name
@@ -1026,26 +994,7 @@ class DiTEngine:
         self._gate_bwd(dx, t.br3, mp + 2 * 5 * d, ldm, dbr3, dmp + 4 * 5 * d, 6 * d, M, d, S, rpb)
         dxm3 = self.empty(M, d)
         if not bp.moe:
-            self.lin_wgrad(dbr3, t.a, n + ".mlp.w3", M, d, f, defer=True)
-            dh12 = self.empty(M, 2 * f)
-            # da = dbr3 @ W3 with the SwiGLU backward in the GEMM epilogue (MD_EPI_SWIGLU_BWD: h12 read, dh12 written by the launch
-            # that forms da -- da never exists in memory, md_swiglu_bwd's pass over 10 bytes per element is gone); the library
-            # refuses what its 4-wave kernel does not cover (ragged tiles, a CU hold): then the two separate launches
-            fused = self.fuse_swiglu_bwd and self._gemm(
-                A=dbr3.data_ptr(), B=self.S[n + ".mlp.w3.weight"].data_ptr(), C=dh12.data_ptr(), aux=t.h12.data_ptr(), M=M, N=f, K=d, lda=d,
-                ldb=f, ldc=2 * f, ldaux=2 * f, batch=1, ksplit=1, a_kcontig=1, b_kcontig=0, mode=hip.EPI_SWIGLU_BWD, act=0, alpha=1.0, _try=True)
-            if not fused:
-                da = self.empty(M, f)
-                self.lin_dgrad(dbr3, n + ".mlp.w3", da, M, d, f)
-                self._prof("swiglu", 10.0 * M * f, lambda: hip.check(L.md_swiglu_bwd(da.data_ptr(), f, t.h12.data_ptr(), 2 * f, dh12.data_ptr(), 2 * f, M, f, st), "swiglu_bwd"))
-            if self._fused12(n + ".mlp"):
-                self.lin_wgrad(dh12, t.xm3, n + ".mlp.w1", M, 2 * f, d, defer=True)
-                self.lin_dgrad(dh12, n + ".mlp.w1", dxm3, M, 2 * f, d)
-            else:
-                self.lin_wgrad(dh12, t.xm3, n + ".mlp.w1", M, f, d, lddy=2 * f, defer=True)
-                self.lin_wgrad(dh12, t.xm3, n + ".mlp.w2", M, f, d, lddy=2 * f, dyoff=f, defer=True)
-                self.lin_dgrad(dh12, n + ".mlp.w1", dxm3, M, f, d, lddy=2 * f)
-                self.lin_dgrad(dh12, n + ".mlp.w2", dxm3, M, f, d, lddy=2 * f, dyoff=f, mode=hip.EPI_RESIDUAL, res=dxm3)
+            self._swiglu_ffn_bwd(n + ".mlp", t, dbr3, t.xm3, M, d, f, defer=True, try_fused=True, dxin=dxm3)
         else:
             E, k, ldl = cfg.num_experts, t.k, t.ldl
             Bk = B * k
@@ -1057,11 +1006,11 @@ class DiTEngine:
             # their dh2 -- and with it their dhpre, dxin and weight-gradient contributions -- is exactly 0; their dgval is never read.
             rows = t.cap or Bk
             if t.cap is None:
-                hip.check(L.md_moe_combine_bwd(dbr3.data_ptr(), t.h2.data_ptr(), t.rowidx.data_ptr(), t.gval.data_ptr(),
-                                               dh2.data_ptr(), dgval.data_ptr(), E * Bk, d, st), "combine_bwd")
+                self._launch("md_moe_combine_bwd", dbr3.data_ptr(), t.h2.data_ptr(), t.rowidx.data_ptr(), t.gval.data_ptr(), dh2.data_ptr(),
+                             dgval.data_ptr(), E * Bk, d)
             else:
-                hip.check(L.md_moe_combine_bwd_compact(dbr3.data_ptr(), t.h2.data_ptr(), t.rowidx_c.data_ptr(), t.gval_c.data_ptr(),
-                                                       dh2.data_ptr(), dgval.data_ptr(), E, rows, Bk, d, st), "combine_bwd_compact")
+                self._launch("md_moe_combine_bwd_compact", dbr3.data_ptr(), t.h2.data_ptr(), t.rowidx_c.data_ptr(), t.gval_c.data_ptr(),
+                             dh2.data_ptr(), dgval.data_ptr(), E, rows, Bk, d)
             # dW2[e][f, d] += hact[e]^T dh2[e]
             self._param_acc(out_ptr=g2.data_ptr(), M=f, N=d, K=rows, ldo=d, batch=E, sOut=f * d, A=t.hact.data_ptr(),
                             B=dh2.data_ptr(), lda=f, ldb=d, sA=Bk * f, sB=Bk * d, a_kcontig=0, b_kcontig=0)
@@ -1079,11 +1028,11 @@ class DiTEngine:
                        sB=d * f, sC=Bk * d, batch=E, ksplit=1, a_kcontig=1, b_kcontig=1, mode=hip.EPI_STORE_BF16, act=0, alpha=1.0)
             dlog = self.empty(M, ldl)
             if t.cap is None:
-                hip.check(L.md_moe_dispatch_bwd(dxin.data_ptr(), t.slot.data_ptr(), dxm3.data_ptr(), t.probs.data_ptr(), ldl,
-                                                dgval.data_ptr(), dlog.data_ptr(), ldl, B, S, E, k, d, st), "dispatch_bwd")
+                self._launch("md_moe_dispatch_bwd", dxin.data_ptr(), t.slot.data_ptr(), dxm3.data_ptr(), t.probs.data_ptr(), ldl, dgval.data_ptr(),
+                             dlog.data_ptr(), ldl, B, S, E, k, d)
             else:       # every token row is written: a dropped token gets dxm3 = 0 and dlog = 0
-                hip.check(L.md_moe_dispatch_bwd_abs(dxin.data_ptr(), t.slot_c.data_ptr(), dxm3.data_ptr(), t.probs.data_ptr(), ldl,
-                                                    dgval.data_ptr(), dlog.data_ptr(), ldl, B, S, E, Bk, d, st), "dispatch_bwd_abs")
+                self._launch("md_moe_dispatch_bwd_abs", dxin.data_ptr(), t.slot_c.data_ptr(), dxm3.data_ptr(), t.probs.data_ptr(), ldl,
+                             dgval.data_ptr(), dlog.data_ptr(), ldl, B, S, E, Bk, d)
             if self.route_log is not None:
                 self.route_log += ["combine_bwd", "dispatch_bwd"] if t.cap is None else ["combine_bwd_compact", "dispatch_bwd_abs"]
             # gate: dWg[E, d] += dlog^T xm3 ; dxm3 += dlog @ Wg
@@ -1096,7 +1045,7 @@ class DiTEngine:
         do2 = self.empty(M, hx)
         self.lin_dgrad(dx, n + ".cross_attn.proj", do2, M, d, hx)
         dq2 = self.empty(M, hx)
-        dkv = self.empty(Mc, 2 * hx) if kvgroup is None else kvgroup["buf"][len(kvgroup["w"])]
+        dkv = self.empty(Mc, 2 * hx) if kvgroup is None else kvgroup.buf[len(kvgroup.w)]
         delta = self.empty(B, bp.xheads, S, dtype=F32)
         if t.q2n is not None:
             dq2n, dk2n = self.empty(M, hx), self.empty(Mc, hx)          # head-major like t.q2n / t.k2n
@@ -1126,10 +1075,10 @@ class DiTEngine:
         if self._x_only:
             pass
         elif kvgroup is None:
-            self.gemm_f32_acc(out_ptr=dycond_f32.data_ptr(), M=Mc, N=d, K=2 * hx, ldo=d, A=dkv.data_ptr(),
-                              B=self.S[n + ".cross_attn.kv_linear.weight"].data_ptr(), lda=2 * hx, ldb=d, a_kcontig=1, b_kcontig=0)
+            self._acc_each(dycond_f32.data_ptr(), Mc, d, 2 * hx, [(dkv.data_ptr(), self.S[n + ".cross_attn.kv_linear.weight"].data_ptr())],
+                           lda=2 * hx, ldb=d, a_kcontig=1)
         else:
-            kvgroup["w"].append(self.S[n + ".cross_attn.kv_linear.weight"].data_ptr())
+            kvgroup.w.append(self.S[n + ".cross_attn.kv_linear.weight"].data_ptr())
         dxn2 = self.empty(M, d)
         self.lin_dgrad(dq2, n + ".cross_attn.q_linear", dxn2, M, hx, d)
         self._wgrad_flush()                  # w3, [w1; w2], cross_attn.proj, q_linear -- before dx (cross_attn.proj's dy) is updated
@@ -1157,50 +1106,36 @@ class DiTEngine:
         given: the bf16 dmod goes to the group's slot and ALL layers of the group are contracted by one launch over operand
         lists at the end of the backward (_adaln_dgrad_grouped)."""
         D = self.cfg.dim
-        if group is not None:
-            i = len(group["w"])
-            dmod = group["buf"][i]
-        else:
-            dmod = self.empty(B, N)
-        hip.check(self.L.md_cast_f32_bf16(dmod_f32.data_ptr(), dmod.data_ptr(), B * N, None, self._st()), "cast")
+        dmod = self.empty(B, N) if group is None else group.buf[len(group.w)]
+        self._launch("md_cast_f32_bf16", dmod_f32.data_ptr(), dmod.data_ptr(), B * N, None)
         self.lin_wgrad(dmod, gc, wname, B, N, D, bias_from=dmod_f32)
         if group is not None:
-            group["w"].append(self.S[wname + ".weight"].data_ptr())
+            group.w.append(self.S[wname + ".weight"].data_ptr())
             return
-        self.gemm_f32_acc(out_ptr=dgc_f32.data_ptr(), M=B, N=D, K=N, ldo=D, A=dmod.data_ptr(),
-                          B=self.S[wname + ".weight"].data_ptr(), lda=N, ldb=D, a_kcontig=1, b_kcontig=0)
+        self._acc_each(dgc_f32.data_ptr(), B, D, N, [(dmod.data_ptr(), self.S[wname + ".weight"].data_ptr())], lda=N, ldb=D, a_kcontig=1)
 
     def _dycond_grouped(self, group, Mc, d, K, out_f32):
         """out[Mc, d] += sum_l dkv_l[Mc, K] @ Wkv_l[K, d] over the G blocks of a group: ONE pp256 launch whose items walk the
         operand lists segment by segment (md_gemm_args.list_segments) and keep the sum in their accumulators; split over
         `ks` groups of segments only as far as whole rounds of the 256 CUs need it (a handful of fp32 slices instead of
         2 x 28)."""
-        G = len(group["w"])
+        G = len(group.w)
         if G == 0:
             return
-        t256 = ((Mc + 255) // 256) * ((d + 255) // 256)
-        if K % 128 or d % 8 or Mc * d > self.ws.numel():
-            for i in range(G):
-                self.gemm_f32_acc(out_ptr=out_f32.data_ptr(), M=Mc, N=d, K=K, ldo=d, A=group["buf"][i].data_ptr(), B=group["w"][i],
-                                  lda=K, ldb=d, a_kcontig=1, b_kcontig=0)
-            return
-        out_us = Mc * d * 4 / 4e6
-        best, best_cost = 1, None
-        for ks in range(1, G + 1):
-            if G % ks or ks * Mc * d > self.ws.numel():
-                continue
-            rounds = -(-t256 * ks // 256)
-            cost = rounds * ((G // ks) * K / 64 * 1.9 + 5.0) + (ks + 2) * out_us
-            if best_cost is None or cost < best_cost:
-                best, best_cost = ks, cost
-        ks, S = best, G // best
-        base = group["buf"].data_ptr()
-        al = self._ptr_list([base + 2 * i * Mc * K for i in range(G)])
-        bl = self._ptr_list(group["w"])
-        self._gemm(A=base, B=group["w"][0], A_list=al.data_ptr(), B_list=bl.data_ptr(), list_segments=S, C=self.ws.data_ptr(), M=Mc, N=d,
-                   K=K * G, lda=K, ldb=d, ldc=d, sC=ks * Mc * d, sSplit=Mc * d, batch=1, ksplit=ks, a_kcontig=1, b_kcontig=0,
-                   mode=hip.EPI_STORE_F32, act=0, alpha=1.0)
-        hip.check(self.L.md_splitk_reduce(self.ws.data_ptr(), out_f32.data_ptr(), Mc, d, d, 0, ks, 1, 1, self._st()), "md_splitk_reduce")
+        base = group.buf.data_ptr()
+        plan = splitk.plan_dycond(G, Mc, d, K, self.ws.numel())
+        if plan is None:
+            return self._acc_each(out_f32.data_ptr(), Mc, d, K, [(group.buf[i].data_ptr(), w) for i, w in enumerate(group.w)],
+                                  lda=K, ldb=d, a_kcontig=1)
+        ks, segments = plan
+        self._gemm_lists([base + 2 * i * Mc * K for i in range(G)], group.w, out_f32.data_ptr(), Mc, d, K * G, K, ks, list_segments=segments)
+
+    def _gemm_lists(self, a_ptrs, b_ptrs, out_ptr, M, N, K, lda, ks, **kw):
+        """out[M, N] += A B, the contraction walking the operand lists (md_gemm_args.A_list / B_list): ks fp32 slices, then their reduction."""
+        al, bl = self._ptr_list(a_ptrs), self._ptr_list(b_ptrs)
+        self._gemm(A=a_ptrs[0], B=b_ptrs[0], A_list=al.data_ptr(), B_list=bl.data_ptr(), C=self.ws.data_ptr(), M=M, N=N, K=K, lda=lda, ldb=N,
+                   ldc=N, sC=ks * M * N, sSplit=M * N, batch=1, ksplit=ks, a_kcontig=1, b_kcontig=0, mode=hip.EPI_STORE_F32, act=0, alpha=1.0, **kw)
+        self._launch("md_splitk_reduce", self.ws.data_ptr(), out_ptr, M, N, N, 0, ks, 1, 1)
 
     def _ptr_list(self, ptrs):
         """Device array of device pointers (md_gemm_args.A_list / B_list); cached by value: with the fixed-address arenas the
@@ -1217,30 +1152,17 @@ class DiTEngine:
     def _adaln_dgrad_grouped(self, group, B, N, dgc_f32):
         """dgc[B, D] += sum_l dmod_l[B, N] @ W_l[N, D] over the G layers of a group as ONE pp256 launch: every (layer, k-part)
         is an item with its own operand pair (md_gemm_args.A_list / B_list) writing an fp32 slice, then one md_splitk_reduce."""
-        D, G = self.cfg.dim, len(group["w"])
+        D, G = self.cfg.dim, len(group.w)
         if G == 0:
             return
-        t256 = ((B + 255) // 256) * ((D + 255) // 256)
-        parts = 1
-        for c in (1, 2, 3, 4, 6, 8, 12):                      # k-parts per layer: enough items to fill the chip
-            if N % c == 0 and (N // c) % 128 == 0 and (N // c) >= 128:
-                parts = c
-                if t256 * G * c >= 192:
-                    break
-        kspan = N // parts
-        ks = G * parts
-        if ks * B * D > self.ws.numel() or (N // parts) % 128:
-            for i in range(G):                                 # does not fit the workspace / the kernel: layer by layer
-                self.gemm_f32_acc(out_ptr=dgc_f32.data_ptr(), M=B, N=D, K=N, ldo=D, A=group["buf"][i].data_ptr(), B=group["w"][i],
-                                  lda=N, ldb=D, a_kcontig=1, b_kcontig=0)
-            return
-        base = group["buf"].data_ptr()
-        al = self._ptr_list([base + 2 * (i * B * N + c * kspan) for i in range(G) for c in range(parts)])
-        bl = self._ptr_list([w + 2 * (c * kspan * D) for w in group["w"] for c in range(parts)])
-        self._gemm(A=base, B=group["w"][0], A_list=al.data_ptr(), B_list=bl.data_ptr(), C=self.ws.data_ptr(), M=B, N=D, K=kspan * ks,
-                   lda=N, ldb=D, ldc=D, sC=ks * B * D, sSplit=B * D, batch=1, ksplit=ks, a_kcontig=1, b_kcontig=0,
-                   mode=hip.EPI_STORE_F32, act=0, alpha=1.0)
-        hip.check(self.L.md_splitk_reduce(self.ws.data_ptr(), dgc_f32.data_ptr(), B, D, D, 0, ks, 1, 1, self._st()), "md_splitk_reduce")
+        base = group.buf.data_ptr()
+        plan = splitk.plan_adaln_dgrad(G, B, N, D, self.ws.numel())
+        if plan is None:                                       # does not fit the workspace / the kernel: layer by layer
+            return self._acc_each(dgc_f32.data_ptr(), B, D, N, [(group.buf[i].data_ptr(), w) for i, w in enumerate(group.w)],
+                                  lda=N, ldb=D, a_kcontig=1)
+        parts, kspan, ks = plan
+        self._gemm_lists([base + 2 * (i * B * N + c * kspan) for i in range(G) for c in range(parts)],
+                         [w + 2 * (c * kspan * D) for w in group.w for c in range(parts)], dgc_f32.data_ptr(), B, D, kspan * ks, N, ks)
 
     # ------------------------------------------------------------------------------------------ small MLPs (Mlp with norm)
     def _mlp_norm_hidden(self, pre, xin, rows, cin, rps):
@@ -1259,10 +1181,7 @@ class DiTEngine:
         """The second half: fc2(hn), optional residual add in the epilogue."""
         D = self.cfg.dim
         out = self.empty(rows, D)
-        if res is None:
-            self.lin_fwd(hn, pre + ".fc2", out, rows, D, D)
-        else:
-            self.lin_fwd(hn, pre + ".fc2", out, rows, D, D, mode=hip.EPI_RESIDUAL, res=res)
+        self.lin_fwd(hn, pre + ".fc2", out, rows, D, D, mode=hip.EPI_STORE_BF16 if res is None else hip.EPI_RESIDUAL, res=res)
         return out
 
     def _mlp_norm_fwd(self, pre, xin, rows, cin, rps, res=None):
@@ -1385,13 +1304,12 @@ class DiTEngine:
     def _caption_fwd(self, y, y_rowscale, B, Lc, tp) -> torch.Tensor:
         """Caption projection + caption block (dit.py:482-483) and the token mean the pooled MLP reads: everything that depends on
         the captions alone up to there.  Activations go to tp (ycap, yproj, y0, cb, y2, ymean); returns y2 [B*Lc, D]."""
-        cfg, L, st = self.cfg, self.L, self._st()
+        cfg = self.cfg
         D, Dc = cfg.dim, y.shape[-1]
         Mc = B * Lc
         tp.y_dtype, tp.y_rowscale = y.dtype, y_rowscale
         tp.ycap = self.empty(Mc, Dc)
-        hip.check(L.md_cast_rows_bf16(y.data_ptr(), 0 if y.dtype == torch.float16 else 1, tp.ycap.data_ptr(), Mc, Dc,
-                                      _p(y_rowscale), Lc, st), "cast_rows")
+        self._launch("md_cast_rows_bf16", y.data_ptr(), 0 if y.dtype == torch.float16 else 1, tp.ycap.data_ptr(), Mc, Dc, _p(y_rowscale), Lc)
         y0, tp.yproj = self._mlp_norm_fwd("y_embedder.y_proj", tp.ycap, Mc, Dc, Lc)
         tp.y0 = y0
         cb = Tape()
@@ -1407,20 +1325,10 @@ class DiTEngine:
         cb.xn2 = self.empty(Mc, D)
         cb.st2 = self.empty(2, Mc, dtype=F32)
         self.ln_fwd(self.ln_args(y1, "y_emb_preprocess.norm2", cb.xn2, Mc, D, mean=cb.st2[0], rstd=cb.st2[1], rps=Lc))
-        fc = caption_ffn_hidden(cfg)
-        cb.h12 = self.empty(Mc, 2 * fc)
-        if self._fused12("y_emb_preprocess.mlp"):
-            self.lin_fwd(cb.xn2, "y_emb_preprocess.mlp.w1", cb.h12, Mc, 2 * fc, D)
-        else:
-            self.lin_fwd(cb.xn2, "y_emb_preprocess.mlp.w1", cb.h12, Mc, fc, D, ldc=2 * fc)
-            self.lin_fwd(cb.xn2, "y_emb_preprocess.mlp.w2", cb.h12, Mc, fc, D, ldc=2 * fc, ooff=fc)
-        cb.a = self.empty(Mc, fc)
-        self._prof("swiglu", 6.0 * Mc * fc, lambda: hip.check(L.md_swiglu_fwd(cb.h12.data_ptr(), 2 * fc, cb.a.data_ptr(), fc, Mc, fc, st), "swiglu"))
-        y2 = self.empty(Mc, D)
-        self.lin_fwd(cb.a, "y_emb_preprocess.mlp.w3", y2, Mc, D, fc, mode=hip.EPI_RESIDUAL, res=y1)
+        y2 = self._swiglu_ffn_fwd("y_emb_preprocess.mlp", cb.xn2, Mc, D, caption_ffn_hidden(cfg), cb, res=y1)
         tp.cb, tp.y2 = cb, y2
         tp.ymean = self.empty(B, D)
-        hip.check(L.md_mean_tokens(y2.data_ptr(), tp.ymean.data_ptr(), B, Lc, D, st), "mean_tokens")
+        self._launch("md_mean_tokens", y2.data_ptr(), tp.ymean.data_ptr(), B, Lc, D)
         return y2
 
     def _map_y_fwd(self, y2, Mc, tp) -> torch.Tensor:
@@ -1458,7 +1366,7 @@ class DiTEngine:
         return Conditioning(B, Lc, self.qk_head_major, self.weights_version, pooled, kv)
 
     def _forward(self, x_img, t_in, y, mask_ratio, mask_noise, in_scale, y_rowscale, cond, patches, B, H, W, Lc, sc=None, reuse=False) -> Tape:
-        cfg, L, st = self.cfg, self.L, self._st()
+        cfg = self.cfg
         C, p = cfg.in_channels, cfg.patch_size
         T, D, Dm = (H // p) * (W // p), cfg.dim, cfg.patch_mixer_dim
         seg = self.before_segment if self.before_segment is not None else (lambda key: None)
@@ -1470,7 +1378,7 @@ class DiTEngine:
         tp.in_scale, tp.from_patches = in_scale, patches is not None      # (the image gradient multiplies by the same per-sample factor)
         if patches is None:
             tp.patches = self.empty(B * T, cfg.patch_vec)
-            hip.check(L.md_patchify(x_img.data_ptr(), _p(in_scale), tp.patches.data_ptr(), B, C, H, W, p, st), "patchify")
+            self._launch("md_patchify", x_img.data_ptr(), _p(in_scale), tp.patches.data_ptr(), B, C, H, W, p)
         else:
             tp.patches = patches
         tok = self.empty(B * T, D)
@@ -1481,7 +1389,7 @@ class DiTEngine:
         # ---- timestep embedding, dit.py:480
         tp.tfreq = self.empty(B, 512)
         t_f = t_in if (t_in.dtype == F32 and t_in.numel() == B and t_in.is_contiguous()) else t_in.to(F32).expand(B).contiguous()
-        hip.check(L.md_timestep_embed(t_f.data_ptr(), tp.tfreq.data_ptr(), B, 512, st), "timestep_embed")
+        self._launch("md_timestep_embed", t_f.data_ptr(), tp.tfreq.data_ptr(), B, 512)
         tp.t_f = t_f
         tp.t_pre = self.empty(B, D)
         tp.t_h = self.empty(B, D)
@@ -1501,7 +1409,7 @@ class DiTEngine:
         c = self._mlp_norm_out("pooled_y_emb_process", pooled, B, res=temb)
         tp.c = c
         gc = self.empty(B, D)
-        hip.check(L.md_act_fwd(c.data_ptr(), gc.data_ptr(), B * D, hip.ACT_GELU_TANH, st), "act_fwd")
+        self._launch("md_act_fwd", c.data_ptr(), gc.data_ptr(), B * D, hip.ACT_GELU_TANH)
         tp.gc = gc
         # ---- patch mixer, dit.py:489-493
         pos = self.buf["pos_embed"]
@@ -1519,7 +1427,7 @@ class DiTEngine:
             if self._posb is None or self._posb.shape[0] != B:          # constant table: built once per batch size
                 self._posb = pos.to(BF16).expand(B, T, D).contiguous()
             posb = self._posb
-            hip.check(L.md_add_bf16(tok.data_ptr(), posb.data_ptr(), x.data_ptr(), B * T * D, st), "add")
+            self._launch("md_add_bf16", tok.data_ptr(), posb.data_ptr(), x.data_ptr(), B * T * D)
             ym = y2
         tp.ym = ym
         # ---- the modulation vectors of every block (mixer + backbone) from one GEMM on gelu(c), dit.py:222-225
@@ -1534,8 +1442,8 @@ class DiTEngine:
             tp.keep_rows = self.empty(B * Tk, dtype=I32)
             tp.ids_restore = self.empty(B, T, dtype=I32)
             tp.mask = self.empty(B, T, dtype=F32)
-            hip.check(L.md_get_mask(mask_noise.contiguous().data_ptr(), B, T, Tk, tp.keep_rows.data_ptr(),
-                                    tp.ids_restore.data_ptr(), tp.mask.data_ptr(), st), "get_mask")
+            self._launch("md_get_mask", mask_noise.contiguous().data_ptr(), B, T, Tk, tp.keep_rows.data_ptr(), tp.ids_restore.data_ptr(),
+                         tp.mask.data_ptr())
 
         # masked-expert pruning: the mask depends on the noise alone, so it is drawn before the last mixer block instead of behind it
         prune = mask_ratio > 0 and self.prune_masked_experts and bool(self.mixer) and self.mixer[-1].moe
@@ -1554,7 +1462,7 @@ class DiTEngine:
             if not prune:
                 get_mask()
             xk = self.empty(B * Tk, Wd)
-            hip.check(L.md_gather_rows(x.data_ptr(), Wd, tp.keep_rows.data_ptr(), xk.data_ptr(), Wd, B * Tk, Wd, st), "gather")
+            self._launch("md_gather_rows", x.data_ptr(), Wd, tp.keep_rows.data_ptr(), xk.data_ptr(), Wd, B * Tk, Wd)
             x = xk
         else:
             tp.keep_rows = tp.ids_restore = tp.mask = None
@@ -1586,7 +1494,7 @@ class DiTEngine:
             if lo <= i < hi and reuse:
                 if i == lo:                         # blocks [lo, hi) are not launched: their input plus what they added last time
                     xr = self.empty(B * Tk, D)
-                    hip.check(L.md_add_bf16(x.data_ptr(), sc.delta.data_ptr(), xr.data_ptr(), B * Tk * D, st), "add")
+                    self._launch("md_add_bf16", x.data_ptr(), sc.delta.data_ptr(), xr.data_ptr(), B * Tk * D)
                     x = xr
                 continue
             if i == lo:
@@ -1626,7 +1534,7 @@ class DiTEngine:
                               a_kcontig=1, b_kcontig=1)
             path = "gemm"
         else:
-            hip.check(self.L.md_disperse_gram_small(z.data_ptr(), K, B, K, G.data_ptr(), ldg, self._st()), "md_disperse_gram_small")
+            self._launch("md_disperse_gram_small", z.data_ptr(), K, B, K, G.data_ptr(), ldg)
             path = "small"
         if self.disperse_log is not None:
             self.disperse_log.append(("gram", path, B, K))
@@ -1644,8 +1552,8 @@ class DiTEngine:
 
     def disperse_pairs(self, G, ldg, B, K, tau, coef, W, ldw, result, loss_accum=None, dist_accum=None, accum_weight=0.0):
         ws = self.empty(2 * B, dtype=torch.float64)
-        hip.check(self.L.md_disperse_pairs(G.data_ptr(), ldg, B, K, tau, coef, W.data_ptr(), ldw, result.data_ptr(), ws.data_ptr(), 2 * B,
-                                           _p(loss_accum), _p(dist_accum), accum_weight, self._st()), "md_disperse_pairs")
+        self._launch("md_disperse_pairs", G.data_ptr(), ldg, B, K, tau, coef, W.data_ptr(), ldw, result.data_ptr(), ws.data_ptr(), 2 * B,
+                     _p(loss_accum), _p(dist_accum), accum_weight)
 
     def _disperse_fwd(self, x, B, K):
         """Behind backbone block k: Gram of its output x [B * Tk, D] seen as Z [B, K], then md_disperse_pairs.  Z is not copied: x is the
@@ -1671,8 +1579,8 @@ class DiTEngine:
         cfg = self.cfg
         img = self.empty(tp.B, cfg.in_channels, tp.H, tp.W, dtype=F32)
         mt = self.buf["mask_token"]
-        hip.check(self.L.md_unpatchify(tp.out_tok.data_ptr(), _p(tp.ids_restore), tp.Tk, mt.data_ptr(), img.data_ptr(), tp.B,
-                                       cfg.in_channels, tp.H, tp.W, cfg.patch_size, self._st()), "unpatchify")
+        self._launch("md_unpatchify", tp.out_tok.data_ptr(), _p(tp.ids_restore), tp.Tk, mt.data_ptr(), img.data_ptr(), tp.B, cfg.in_channels, tp.H,
+                     tp.W, cfg.patch_size)
         return img
 
     def backward(self, tp: Tape, dtok: torch.Tensor, on_segment=None, *, input_grads=(), param_grads: bool = True) -> InputGrads:
@@ -1720,7 +1628,7 @@ class DiTEngine:
         self._arena.release(m)
 
     def _backward(self, tp: Tape, dtok: torch.Tensor, on_segment=None, want=frozenset()) -> InputGrads:
-        cfg, L, st = self.cfg, self.L, self._st()
+        cfg = self.cfg
         out = InputGrads()
         seg = on_segment if on_segment is not None else (lambda name: None)
         B, T, Tk, Lc = tp.B, tp.T, tp.Tk, tp.Lc
@@ -1730,18 +1638,15 @@ class DiTEngine:
         x_only = self._x_only                       # stop at the image: no condition-vector or caption-token gradient is formed
         dgc = None if x_only else self.zeros(B, D)          # fp32: sums the adaLN dgrads of all 6+28+1 layers
         dy2_f32 = None if x_only else self.zeros(Mc, D)     # fp32: caption-token grads from the 28 backbone kv_linears + pooling
-        grp_b = grp_m = None
-        if self.group_adaln and not x_only:                    # bf16 dmod of every layer, kept until the grouped contraction below
-            if self.backbone:
-                grp_b = {"buf": self.empty(len(self.backbone), B, 6 * self.backbone[0].dim), "w": []}
-            if self.mixer:
-                grp_m = {"buf": self.empty(len(self.mixer), B, 6 * self.mixer[0].dim), "w": []}
-        kv_b = kv_m = None
-        if self.group_dycond and not x_only:        # dkv of every block, kept until the concatenated contraction
-            if self.backbone:
-                kv_b = {"buf": self.empty(len(self.backbone), Mc, 2 * self.backbone[0].xattn_hidden), "w": []}
-            if self.mixer:
-                kv_m = {"buf": self.empty(len(self.mixer), Mc, 2 * self.mixer[0].xattn_hidden), "w": []}
+        # per stack, None where not grouped: adaln (-> the condition vector, _adaln_dgrad_grouped), kv (-> the caption tokens, _dycond_grouped)
+        stacks = [(SimpleNamespace(adaln=None, kv=None), blocks) for blocks in (self.backbone, self.mixer)]
+        (sg_b, _), (sg_m, _) = stacks
+        for sg, blocks in stacks:                   # bf16 dmod of every layer, kept until the grouped contraction below
+            if self.group_adaln and not x_only and blocks:
+                sg.adaln = _Deferred(self.empty(len(blocks), B, 6 * blocks[0].dim))
+        for sg, blocks in stacks:                   # dkv of every block, kept until the concatenated contraction
+            if self.group_dycond and not x_only and blocks:
+                sg.kv = _Deferred(self.empty(len(blocks), Mc, 2 * blocks[0].xattn_hidden))
         # ---- final layer
         self.lin_wgrad(dtok, tp.xf, "final_layer.linear", B * Tk, pv, D)
         dxf = self.empty(B * Tk, D)
@@ -1761,10 +1666,10 @@ class DiTEngine:
         for i, bp, bt in zip(reversed(range(len(self.backbone))), reversed(self.backbone), reversed(tp.blocks)):
             if dsp is not None and i == dsp.k:
                 self.disperse_apply(dsp.W, dsp.ldw, dsp.z, dx, dsp.B, dsp.K)       # dx is dL/d(output of block k) here
-            self._block_bwd_scoped(bp, bt, dx, tp.y2, dy2_f32, B, Tk, Lc, gc, dgc, grp_b, kv_b)
+            self._block_bwd_scoped(bp, bt, dx, tp.y2, dy2_f32, B, Tk, Lc, gc, dgc, sg_b.adaln, sg_b.kv)
             seg(bp.name)
-        if kv_b is not None:
-            self._dycond_grouped(kv_b, Mc, self.backbone[0].dim, 2 * self.backbone[0].xattn_hidden, dy2_f32)
+        if sg_b.kv is not None:
+            self._dycond_grouped(sg_b.kv, Mc, self.backbone[0].dim, 2 * self.backbone[0].xattn_hidden, dy2_f32)
         # ---- mixer -> backbone projection
         if cfg.use_patch_mixer and cfg.has_maps:
             self.lin_wgrad(dx, tp.xout_ln, "patch_mixer_map_xout.1", B * Tk, D, Dm)
@@ -1778,16 +1683,16 @@ class DiTEngine:
         # ---- un-mask: scatter kept-token grads back to all T positions (zeros elsewhere)
         if tp.keep_rows is not None:
             dfull = self.zeros(B * T, Wd, dtype=BF16)
-            hip.check(L.md_scatter_rows(dx.data_ptr(), Wd, tp.keep_rows.data_ptr(), dfull.data_ptr(), Wd, B * Tk, Wd, st), "scatter")
+            self._launch("md_scatter_rows", dx.data_ptr(), Wd, tp.keep_rows.data_ptr(), dfull.data_ptr(), Wd, B * Tk, Wd)
             dx = dfull
         # ---- patch mixer
         has_maps = cfg.use_patch_mixer and cfg.has_maps
         dym_f32 = self.zeros(Mc, Dm) if has_maps and not x_only else dy2_f32
         for bp, bt in zip(reversed(self.mixer), reversed(tp.mixer)):
-            self._block_bwd_scoped(bp, bt, dx, tp.ym, dym_f32, B, T, Lc, gc, dgc, grp_m, kv_m)
+            self._block_bwd_scoped(bp, bt, dx, tp.ym, dym_f32, B, T, Lc, gc, dgc, sg_m.adaln, sg_m.kv)
             seg(bp.name)
-        if kv_m is not None:
-            self._dycond_grouped(kv_m, Mc, self.mixer[0].dim, 2 * self.mixer[0].xattn_hidden, dym_f32)
+        if sg_m.kv is not None:
+            self._dycond_grouped(sg_m.kv, Mc, self.mixer[0].dim, 2 * self.mixer[0].xattn_hidden, dym_f32)
         # ---- map_xin / patch embedding
         if has_maps:
             self.lin_wgrad(dx, tp.xin_ln, "patch_mixer_map_xin.1", B * T, Dm, D)
@@ -1807,20 +1712,19 @@ class DiTEngine:
             # (a forward that read patches= has no in_scale: dx is then the gradient of the un-patchified network input)
             out.dx = self.fresh(B, cfg.in_channels, tp.H, tp.W)
             path = ctypes.c_int32(-1)
-            self._prof("patch_embed_dgrad", 2.0 * B * T * D, lambda: hip.check(self.L.md_patch_embed_dgrad(
-                dtok_e.data_ptr(), D, self.S["x_embedder.proj.weight"].data_ptr(), _p(tp.in_scale), out.dx.data_ptr(), B, cfg.in_channels,
-                tp.H, tp.W, cfg.patch_size, D, byref(path), st), "md_patch_embed_dgrad"))
+            self._launch("md_patch_embed_dgrad", dtok_e.data_ptr(), D, self.S["x_embedder.proj.weight"].data_ptr(), _p(tp.in_scale),
+                         out.dx.data_ptr(), B, cfg.in_channels, tp.H, tp.W, cfg.patch_size, D, byref(path), prof="patch_embed_dgrad",
+                         nbytes=2.0 * B * T * D)
             if self.input_grad_log is not None:
                 self.input_grad_log.append(("md_patch_embed_dgrad", path.value))
         if x_only:
             return out
         # ---- condition vector: c = temb + pooled ; gc = gelu(c)
-        if grp_b is not None:
-            self._adaln_dgrad_grouped(grp_b, B, 6 * self.backbone[0].dim, dgc)
-        if grp_m is not None:
-            self._adaln_dgrad_grouped(grp_m, B, 6 * self.mixer[0].dim, dgc)
+        for sg, blocks in stacks:
+            if sg.adaln is not None:
+                self._adaln_dgrad_grouped(sg.adaln, B, 6 * blocks[0].dim, dgc)
         dc = self.empty(B, D)
-        hip.check(L.md_act_bwd(dgc.data_ptr(), tp.c.data_ptr(), dc.data_ptr(), B * D, hip.ACT_GELU_TANH, st), "act_bwd")
+        self._launch("md_act_bwd", dgc.data_ptr(), tp.c.data_ptr(), dc.data_ptr(), B * D, hip.ACT_GELU_TANH)
         # timestep embedder
         self.lin_wgrad(dc, tp.t_h, "t_embedder.mlp.2", B, D, D)
         dtpre = self.empty(B, D)
@@ -1830,18 +1734,18 @@ class DiTEngine:
             dtfreq = self.empty(B, 512)
             self.lin_dgrad(dtpre, "t_embedder.mlp.0", dtfreq, B, D, 512)
             out.dt = self.fresh(B)
-            hip.check(L.md_timestep_embed_bwd(tp.t_f.data_ptr(), dtfreq.data_ptr(), out.dt.data_ptr(), B, 512, st), "md_timestep_embed_bwd")
+            self._launch("md_timestep_embed_bwd", tp.t_f.data_ptr(), dtfreq.data_ptr(), out.dt.data_ptr(), B, 512)
             if self.input_grad_log is not None:
                 self.input_grad_log.append(("md_timestep_embed_bwd", None))
         # pooled-caption MLP -> mean over tokens
         dymean = self._mlp_norm_bwd("pooled_y_emb_process", tp.pool, dc, B, D, 1, need_dx=True)
-        hip.check(L.md_mean_tokens_bwd(dymean.data_ptr(), dy2_f32.data_ptr(), B, Lc, D, st), "mean_bwd")
+        self._launch("md_mean_tokens_bwd", dymean.data_ptr(), dy2_f32.data_ptr(), B, Lc, D)
         # ---- caption tokens: total grad w.r.t. y2
         dy = self.empty(Mc, D)
-        hip.check(L.md_cast_f32_bf16(dy2_f32.data_ptr(), dy.data_ptr(), Mc * D, None, st), "cast")
+        self._launch("md_cast_f32_bf16", dy2_f32.data_ptr(), dy.data_ptr(), Mc * D, None)
         if has_maps:
             dym = self.empty(Mc, Dm)
-            hip.check(L.md_cast_f32_bf16(dym_f32.data_ptr(), dym.data_ptr(), Mc * Dm, None, st), "cast")
+            self._launch("md_cast_f32_bf16", dym_f32.data_ptr(), dym.data_ptr(), Mc * Dm, None)
             self.lin_wgrad(dym, tp.y_ln, "patch_mixer_map_y.1", Mc, Dm, D)
             dyl = self.empty(Mc, D)
             self.lin_dgrad(dym, "patch_mixer_map_y.1", dyl, Mc, Dm, D)
@@ -1849,21 +1753,7 @@ class DiTEngine:
             self.ln_bwd(a, dyl, dy, accumulate=True, wname="patch_mixer_map_y.0")
         # ---- caption block (y2 = y1 + ffn(LN2(y1)); y1 = y0 + attn(LN1(y0)))
         cb = tp.cb
-        fc = caption_ffn_hidden(cfg)
-        self.lin_wgrad(dy, cb.a, "y_emb_preprocess.mlp.w3", Mc, D, fc)
-        da = self.empty(Mc, fc)
-        self.lin_dgrad(dy, "y_emb_preprocess.mlp.w3", da, Mc, D, fc)
-        dh12 = self.empty(Mc, 2 * fc)
-        self._prof("swiglu", 10.0 * Mc * fc, lambda: hip.check(L.md_swiglu_bwd(da.data_ptr(), fc, cb.h12.data_ptr(), 2 * fc, dh12.data_ptr(), 2 * fc, Mc, fc, st), "swiglu_bwd"))
-        dxn2 = self.empty(Mc, D)
-        if self._fused12("y_emb_preprocess.mlp"):
-            self.lin_wgrad(dh12, cb.xn2, "y_emb_preprocess.mlp.w1", Mc, 2 * fc, D)
-            self.lin_dgrad(dh12, "y_emb_preprocess.mlp.w1", dxn2, Mc, 2 * fc, D)
-        else:
-            self.lin_wgrad(dh12, cb.xn2, "y_emb_preprocess.mlp.w1", Mc, fc, D, lddy=2 * fc)
-            self.lin_wgrad(dh12, cb.xn2, "y_emb_preprocess.mlp.w2", Mc, fc, D, lddy=2 * fc, dyoff=fc)
-            self.lin_dgrad(dh12, "y_emb_preprocess.mlp.w1", dxn2, Mc, fc, D, lddy=2 * fc)
-            self.lin_dgrad(dh12, "y_emb_preprocess.mlp.w2", dxn2, Mc, fc, D, lddy=2 * fc, dyoff=fc, mode=hip.EPI_RESIDUAL, res=dxn2)
+        dxn2 = self._swiglu_ffn_bwd("y_emb_preprocess.mlp", cb, dy, cb.xn2, Mc, D, caption_ffn_hidden(cfg), defer=False, try_fused=False)
         a = self.ln_args(cb.y1, "y_emb_preprocess.norm2", None, Mc, D, mean=cb.st2[0], rstd=cb.st2[1], rps=Lc)
         self.ln_bwd(a, dxn2, dy, accumulate=True, wname="y_emb_preprocess.norm2")
         heads_c = D // cfg.head_dim
@@ -1878,8 +1768,8 @@ class DiTEngine:
         dycap = self._mlp_norm_bwd("y_embedder.y_proj", tp.yproj, dy, Mc, Dc, Lc, need_dx="y" in want)
         if "y" in want:
             out.dy = self.fresh(Mc, Dc, dtype=tp.y_dtype)
-            hip.check(L.md_cast_rows_from_bf16(dycap.data_ptr(), out.dy.data_ptr(), 0 if tp.y_dtype == torch.float16 else 1, Mc, Dc,
-                                               _p(tp.y_rowscale), Lc, st), "md_cast_rows_from_bf16")
+            self._launch("md_cast_rows_from_bf16", dycap.data_ptr(), out.dy.data_ptr(), 0 if tp.y_dtype == torch.float16 else 1, Mc, Dc,
+                         _p(tp.y_rowscale), Lc)
             if self.input_grad_log is not None:
                 self.input_grad_log.append(("md_cast_rows_from_bf16", None))
         seg("rest")

@@ -14,7 +14,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch                                    # noqa: E402
-from micro_diffusion_amd import hip             # noqa: E402
+from micro_diffusion_amd import hip, splitk     # noqa: E402
 
 # (rows per 256-image microbatch, N, K, layout, launches per microbatch): profiles/r3_gemm_shapes_mb256.txt, single-problem launches
 SHAPES = [
@@ -45,22 +45,6 @@ def time_us(fn, iters):
     return best
 
 
-def ksplit_like_engine(out_rows, out_cols, contraction):
-    """DiTEngine._ksplit's rule for pp256-eligible weight gradients (contraction % 128 == 0)."""
-    t256 = ((out_rows + 255) // 256) * ((out_cols + 255) // 256)
-    units = contraction // 128
-    out_us = out_rows * out_cols * 4 / 4e6
-    best, best_cost = 1, None
-    for ks in range(1, min(64, units) + 1):
-        if units % ks or t256 * ks < 192:
-            continue
-        per_wg = -(-t256 * ks // 256)
-        cost = per_wg * (contraction / ks / 64 * 1.9 + 5.0) + (ks + 2) * out_us
-        if best_cost is None or cost < best_cost:
-            best, best_cost = ks, cost
-    return best
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
@@ -81,7 +65,7 @@ def main():
                 A = torch.randn(Kk, M, device=dev).to(torch.bfloat16)
                 B = torch.randn(Kk, Nn, device=dev).to(torch.bfloat16)
                 out = torch.zeros(M, Nn, device=dev)
-                ks = ksplit_like_engine(M, Nn, Kk)
+                ks = abs(splitk.choose_ksplit(M, Nn, Kk, ws_floats=ws.numel()))     # the engine's rule (-1: one slice through the workspace)
 
                 def ours():
                     hip.gemm(A, B, ws, M, Nn, Kk, lda=M, ldb=Nn, ldc=Nn, a_kcontig=0, b_kcontig=0, mode=hip.EPI_STORE_F32, sC=ks * M * Nn,

@@ -113,14 +113,8 @@ def test_splitk_factor_fills_whole_rounds():
     accepts (contraction per split a multiple of 128) that deals at least 192 work items (the AUTO rule's pp256 threshold) to the 256 CUs and
     fits the workspace; the two heaviest XL/2 weight-gradient shapes keep the factors measured best on MI355X
     (profiles/r2_gemm_variants_mb1024_call1.txt); ragged contractions fall back to the 128 x 128 rule (>= 512 k per split)."""
-    import types
-    from micro_diffusion_amd.engine import DiTEngine
-
-    class _WS:
-        def numel(self):
-            return 128 << 20
-    eng = types.SimpleNamespace(ws=_WS(), wgrad_target_blocks=768)
-    pick = lambda *a: DiTEngine._ksplit(eng, *a)   # noqa: E731
+    from micro_diffusion_amd import splitk
+    pick = lambda *a: splitk.choose_ksplit(*a, ws_floats=128 << 20)   # noqa: E731  (what DiTEngine._ksplit asks with its defaults)
     assert pick(1024, 1024, 65536, 1) == 16        # 16 tiles x 16 = 256 work items, one per CU
     assert pick(2048, 1024, 78848, 1) == 8         # 32 tiles x 8 = 256
     assert pick(1024, 1024, 16384, 1) == 16        # microbatch 256 (the per-rank shape of an 8-GPU run)
@@ -402,7 +396,7 @@ def test_grouped_wgrad_host_logic():
         def data_ptr(self):
             return 1 << 40
     eng = DiTEngine.__new__(DiTEngine)
-    eng.ws, eng.L, eng.kernel_profile, eng.group_wgrad, eng._wgroup = WS(), L, None, True, None
+    eng.ws, eng.L, eng.kernel_profile, eng.group_wgrad, eng._wgroup, eng.wgrad_bf16 = WS(), L, None, True, None, None
     eng._st = lambda: 0
     eng._gemm = lambda **kw: calls["gemm"].append(kw)
     base = 1 << 30
