@@ -184,9 +184,67 @@ __device__ __forceinline__ void bh_of(int64_t lin, int64_t H, int64_t B, int64_t
     h = lin - b * H;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Result stores (O, dQ, dK, dV).  Straight out of the MFMA a lane owns 4 consecutive columns per 8-column group g of ONE row
+// (lane <-> row), so the plain form -- an 8-byte store per group -- touches 32 rows x 16 bytes per instruction and completes the
+// 128-byte head slice of a row only after 8 of them.  Two other routes for the same bf16 values to the same addresses:
+//   WIDE   the two half-waves (same row, columns 4 apart) trade groups (g, g + 1) with v_permlane32_swap: lanes 0-31 then own columns
+//          8 g .. 8 g + 7, lanes 32-63 columns 8 g + 8 .. 8 g + 15, one 16-byte store per pair.  Half the instructions and requests.
+//   LINES  where the LDS image is dead: the wave parks its 32 rows in its own 32-row part of the image (pitch PK) and reads them
+//          back row-contiguously, 16 bytes per lane, HD / 8 lanes per row: a store instruction covers whole head slices of 8 (16) rows.
+// One switch per form and kernel family (bits of MD_ATTN_STORE_FORMS; -DMD_ATTN_STORE_FORMS=0 builds the plain form everywhere, for
+// A/B runs); the default is what measured faster, profiles/attn_row_stores.txt.  16-byte stores need every row piece of the tensor on
+// a 16-byte boundary and the interface promises 8 (attn_ok), so the kernels ask per tensor (rows16: wave-uniform, scalar) and keep the
+// plain form otherwise.
+// ---------------------------------------------------------------------------------------------------------------------
+enum : unsigned {
+    SF_FWD_WIDE = 1u, SF_FWD_LINES = 2u,            // attn_fwd_kernel (LINES: workgroups of <= 2 waves, the K / V staging tiles)
+    SF_FWDS_WIDE = 4u,                              // attn_fwd_stream_kernel
+    SF_FUSED_WIDE = 8u, SF_FUSED_LINES = 16u,       // attn_bwd_fused_kernel (WIDE: dQ, dK, dV; LINES: dK, dV)
+    SF_FUSED2_LINES = 32u,                          // attn_bwd_fused2_kernel<.., false> (dK, dV; dQ stays plain, see the kernel)
+    SF_SPLIT2_WIDE = 64u,                           // attn_bwd_fused2_kernel<.., true> (dV leaves while the image is live: no LINES)
+    SF_STREAM_WIDE = 128u, SF_STREAM_LINES = 256u,  // the streaming backward pair (LINES: dK, dV)
+};
+#ifndef MD_ATTN_STORE_FORMS
+#define MD_ATTN_STORE_FORMS 0x1ffu
+#endif
+constexpr bool sf(unsigned bit) { return (MD_ATTN_STORE_FORMS & bit) != 0; }
+
+// {lo, hi} -> packed bf16 pair (round to nearest even), one instruction: the rounding of f2bf
+__device__ __forceinline__ unsigned cvt_pk_bf16(float lo, float hi) {
+    unsigned r;
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+    return r;
+}
+// v_permlane32_swap: the upper half-wave of a and the lower half-wave of b change places
+__device__ __forceinline__ void half_swap(unsigned& a, unsigned& b) {
+    const auto sw = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    a = sw[0];
+    b = sw[1];
+}
+__device__ __forceinline__ bool rows16(const void* base, int64_t ld, int64_t s, int64_t hs) {
+    return ((reinterpret_cast<uintptr_t>(base) | (uintptr_t)((ld | s | hs) * 2)) & 15) == 0;
+}
+
+// dst_row: this lane's row.  Both lanes of a row are inside or outside the caller's row guard together (the swap needs its partner).
 template <int HD>
-__device__ __forceinline__ void store_rows(bf16* dst_row, const f32x16 (&acc)[HD / 32], float mul, int lane) {
+__device__ __forceinline__ void store_rows(bf16* dst_row, const f32x16 (&acc)[HD / 32], float mul, int lane, bool wide) {
     const int hh = lane >> 5;
+    if (wide) {
+#pragma unroll
+        for (int di = 0; di < HD / 32; ++di)
+#pragma unroll
+            for (int g = 0; g < 4; g += 2) {
+                unsigned a0 = cvt_pk_bf16(acc[di][4 * g] * mul, acc[di][4 * g + 1] * mul);
+                unsigned a1 = cvt_pk_bf16(acc[di][4 * g + 2] * mul, acc[di][4 * g + 3] * mul);
+                unsigned b0 = cvt_pk_bf16(acc[di][4 * g + 4] * mul, acc[di][4 * g + 5] * mul);
+                unsigned b1 = cvt_pk_bf16(acc[di][4 * g + 6] * mul, acc[di][4 * g + 7] * mul);
+                half_swap(a0, b0);
+                half_swap(a1, b1);
+                *reinterpret_cast<uint4*>(dst_row + di * 32 + 8 * g + 8 * hh) = make_uint4(a0, a1, b0, b1);
+            }
+        return;
+    }
 #pragma unroll
     for (int di = 0; di < HD / 32; ++di)
 #pragma unroll
@@ -196,6 +254,31 @@ __device__ __forceinline__ void store_rows(bf16* dst_row, const f32x16 (&acc)[HD
             for (int e = 0; e < 4; ++e) o[e] = f2bf(acc[di][4 * g + e] * mul);
             st_bf16x4(dst_row + di * 32 + 8 * g + 4 * hh, o);
         }
+}
+
+// LINES: tile = the wave's own 32 rows of a dead LDS image (pitch bytes a row), dst0 = row 0 of those 32 in memory, nvalid of them
+// inside the sequence.  Wave-local: the caller's barrier only has to say that nobody READS the image any more.
+template <int HD>
+__device__ __forceinline__ void store_lines(unsigned char* tile, int pitch, bf16* dst0, int64_t ld, int nvalid, const f32x16 (&acc)[HD / 32],
+                                            float mul, int lane) {
+    const int hh = lane >> 5;
+#pragma unroll
+    for (int di = 0; di < HD / 32; ++di)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            *reinterpret_cast<uint2*>(tile + (lane & 31) * pitch + (di * 32 + 8 * g + 4 * hh) * 2) =
+                make_uint2(cvt_pk_bf16(acc[di][4 * g] * mul, acc[di][4 * g + 1] * mul), cvt_pk_bf16(acc[di][4 * g + 2] * mul, acc[di][4 * g + 3] * mul));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the wave's LDS operations execute in order: this pins the compiler's order
+    __builtin_amdgcn_wave_barrier();
+    constexpr int CPR = HD / 8, RPI = 64 / CPR;                  // 16-byte pieces per row; rows per instruction
+#pragma unroll
+    for (int it = 0; it < 32 / RPI; ++it) {
+        const int r = it * RPI + lane / CPR, c = lane % CPR;
+        const uint4 v = *reinterpret_cast<const uint4*>(tile + r * pitch + c * 16);
+        if (r < nvalid) *reinterpret_cast<uint4*>(dst0 + r * ld + c * 8) = v;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");      // a second matrix may go through the same tile
+    __builtin_amdgcn_wave_barrier();
 }
 
 // (Measured and dropped: capping this kernel at 128 VGPRs -- 117 without a spill at head_dim 64, 4 waves / SIMD instead of 3 --
@@ -283,11 +366,21 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(md_attn_args p) {
         }
       }
     }
-    if (qvalid) {
+    // (head_dim 64 in four-wave workgroups, the 256-row shapes: either form costs this instantiation a wave per SIMD, 92 -> 108-112 VGPRs)
+    constexpr bool PLAIN = HD == 64 && MAXIT == 1;
+    const bool o16 = rows16(p.o, p.ldo, p.so, p.hso);
+    if (sf(SF_FWD_LINES) && !PLAIN && nw <= 2 && o16) {
+        // the K / V staging tiles (2 x STG rows) are dead after the last key phase: 32 rows of them per wave
+        __syncthreads();
+        const int64_t q0 = ((int64_t)blockIdx.x * nw + wave) * 32;
+        const int nvalid = p.Sq - q0 >= 32 ? 32 : (p.Sq > q0 ? (int)(p.Sq - q0) : 0);
+        store_lines<HD>(smem + wave * 32 * PK, PK, reinterpret_cast<bf16*>(p.o) + b * p.so + h * p.hso + q0 * p.ldo, p.ldo, nvalid, oacc,
+                        1.f / l, lane);
+    } else if (qvalid) {
         bf16* O = reinterpret_cast<bf16*>(p.o) + b * p.so + h * p.hso + q * p.ldo;
-        store_rows<HD>(O, oacc, 1.f / l, lane);
-        if (lane < 32 && p.lse) reinterpret_cast<float*>(p.lse)[(b * p.H + h) * p.Sq + q] = (m + __log2f(l)) * 0.6931471805599453f;   // natural log
+        store_rows<HD>(O, oacc, 1.f / l, lane, sf(SF_FWD_WIDE) && !PLAIN && o16);
     }
+    if (qvalid && lane < 32 && p.lse) reinterpret_cast<float*>(p.lse)[(b * p.H + h) * p.Sq + q] = (m + __log2f(l)) * 0.6931471805599453f;   // natural log
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -428,7 +521,7 @@ __global__ __launch_bounds__(512) void attn_fwd_stream_kernel(md_attn_args p) { 
     }
     if (qvalid) {
         bf16* O = reinterpret_cast<bf16*>(p.o) + b * p.so + h * p.hso + q * p.ldo;
-        store_rows<HD>(O, oacc, 1.f / l, lane);
+        store_rows<HD>(O, oacc, 1.f / l, lane, sf(SF_FWDS_WIDE) && rows16(p.o, p.ldo, p.so, p.hso));
         if (lane < 32 && p.lse) reinterpret_cast<float*>(p.lse)[(b * p.H + h) * p.Sq + q] = (m + __log2f(l)) * 0.6931471805599453f;   // natural log
     }
 }
@@ -527,7 +620,7 @@ void attn_bwd_dq_stream_kernel(md_attn_args p) {
     }
     if (qvalid) {
         bf16* dQ = reinterpret_cast<bf16*>(p.dq) + b * p.sdq + h * p.hsdq + q * p.lddq;
-        store_rows<HD>(dQ, dqacc, p.scale, lane);
+        store_rows<HD>(dQ, dqacc, p.scale, lane, sf(SF_STREAM_WIDE) && rows16(p.dq, p.lddq, p.sdq, p.hsdq));
     }
 }
 
@@ -632,11 +725,20 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_stream_kernel(md_attn_args p
         // pushes this kernel -- four accumulators -- past the 256-register budget: 8-126 spilled registers.)
         for (int sub = 0; sub < SCH / 32 && qbase + sub * 32 < p.Sq; ++sub) tile(sub, (int)(p.Sq - qbase - sub * 32));
     }
-    if (kvalid) {
+    const bool dk16 = rows16(p.dk, p.lddk, p.sdk, p.hsdk), dv16 = rows16(p.dv, p.lddv, p.sdv, p.hsdv);
+    if (sf(SF_STREAM_LINES) && dk16 && dv16) {
+        // the Q / dO chunk tiles are dead: 2 x SCH rows >= 32 per wave (8 waves walk 128-row chunks, 3-4 waves 64-row chunks); dK, then dV
+        __syncthreads();
+        const int64_t key0 = ((int64_t)blockIdx.x * nw + wave) * 32;
+        const int nvalid = p.Skv - key0 >= 32 ? 32 : (p.Skv > key0 ? (int)(p.Skv - key0) : 0);
+        unsigned char* mine = smem + wave * 32 * PK;
+        store_lines<HD>(mine, PK, reinterpret_cast<bf16*>(p.dk) + b * p.sdk + h * p.hsdk + key0 * p.lddk, p.lddk, nvalid, dkacc, p.scale, lane);
+        store_lines<HD>(mine, PK, reinterpret_cast<bf16*>(p.dv) + b * p.sdv + h * p.hsdv + key0 * p.lddv, p.lddv, nvalid, dvacc, 1.f, lane);
+    } else if (kvalid) {
         bf16* dK = reinterpret_cast<bf16*>(p.dk) + b * p.sdk + h * p.hsdk + key * p.lddk;
         bf16* dV = reinterpret_cast<bf16*>(p.dv) + b * p.sdv + h * p.hsdv + key * p.lddv;
-        store_rows<HD>(dK, dkacc, p.scale, lane);
-        store_rows<HD>(dV, dvacc, 1.f, lane);
+        store_rows<HD>(dK, dkacc, p.scale, lane, sf(SF_STREAM_WIDE) && !sf(SF_STREAM_LINES) && dk16);
+        store_rows<HD>(dV, dvacc, 1.f, lane, sf(SF_STREAM_WIDE) && !sf(SF_STREAM_LINES) && dv16);
     }
 }
 
@@ -770,28 +872,27 @@ __global__ __launch_bounds__((SQP > SKP ? SQP : SKP) * 2) void attn_bwd_fused_ke
         }
         if (q < p.Sq) {
             bf16* dQ = reinterpret_cast<bf16*>(p.dq) + b * p.sdq + h * p.hsdq + q * p.lddq;
-            store_rows<HD>(dQ, dqacc, p.scale, lane);
+            store_rows<HD>(dQ, dqacc, p.scale, lane, sf(SF_FUSED_WIDE) && rows16(p.dq, p.lddq, p.sdq, p.hsdq));
         }
     }
     // ---------------- role 2: dK, dV for key rows wave * 32 ..
+    f32x16 dkacc[HD / 32], dvacc[HD / 32];
+#pragma unroll
+    for (int di = 0; di < HD / 32; ++di)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            dkacc[di][r] = 0.f;
+            dvacc[di][r] = 0.f;
+        }
     if (wave < nk32) {
         const unsigned char* myK = sK + wave * 32 * PK;
         const unsigned char* myV = sV + wave * 32 * PK;
-        const int64_t key = (int64_t)wave * 32 + (lane & 31);
         bf16x8 kf[HD / 16], vf[HD / 16];
 #pragma unroll
         for (int s = 0; s < HD / 16; ++s) {
             kf[s] = row_frag(myK, PK, s * 16, lane);
             vf[s] = row_frag(myV, PK, s * 16, lane);
         }
-        f32x16 dkacc[HD / 32], dvacc[HD / 32];
-#pragma unroll
-        for (int di = 0; di < HD / 32; ++di)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                dkacc[di][r] = 0.f;
-                dvacc[di][r] = 0.f;
-            }
         for (int i = 0; i < nq32; ++i) {
             const unsigned char* tQ = sQ + i * 32 * PK;
             const unsigned char* tdO = sdO + i * 32 * PK;
@@ -822,11 +923,25 @@ __global__ __launch_bounds__((SQP > SKP ? SQP : SKP) * 2) void attn_bwd_fused_ke
                 }
             }
         }
+    }
+    const bool dk16 = rows16(p.dk, p.lddk, p.sdk, p.hsdk), dv16 = rows16(p.dv, p.lddv, p.sdv, p.hsdv);
+    if (sf(SF_FUSED_LINES) && dk16 && dv16) {
+        // the image is dead once every wave has left both roles: dK through this wave's 32 rows of the K tile, dV through those of the V tile
+        __syncthreads();
+        if (wave < nk32) {
+            const int nvalid = p.Skv - wave * 32 >= 32 ? 32 : (int)(p.Skv - wave * 32);
+            store_lines<HD>(sK + wave * 32 * PK, PK, reinterpret_cast<bf16*>(p.dk) + b * p.sdk + h * p.hsdk + (int64_t)wave * 32 * p.lddk,
+                            p.lddk, nvalid, dkacc, p.scale, lane);
+            store_lines<HD>(sV + wave * 32 * PK, PK, reinterpret_cast<bf16*>(p.dv) + b * p.sdv + h * p.hsdv + (int64_t)wave * 32 * p.lddv,
+                            p.lddv, nvalid, dvacc, 1.f, lane);
+        }
+    } else if (wave < nk32) {
+        const int64_t key = (int64_t)wave * 32 + (lane & 31);
         if (key < p.Skv) {
             bf16* dK = reinterpret_cast<bf16*>(p.dk) + b * p.sdk + h * p.hsdk + key * p.lddk;
             bf16* dV = reinterpret_cast<bf16*>(p.dv) + b * p.sdv + h * p.hsdv + key * p.lddv;
-            store_rows<HD>(dK, dkacc, p.scale, lane);
-            store_rows<HD>(dV, dvacc, 1.f, lane);
+            store_rows<HD>(dK, dkacc, p.scale, lane, sf(SF_FUSED_WIDE) && !sf(SF_FUSED_LINES) && dk16);
+            store_rows<HD>(dV, dvacc, 1.f, lane, sf(SF_FUSED_WIDE) && !sf(SF_FUSED_LINES) && dv16);
         }
     }
 }
@@ -858,6 +973,8 @@ void attn_bwd_fused2_kernel(md_attn_args p) {
     constexpr int PK = (HD + 8) * 2;
     constexpr int RMAX = SQP > SKP ? SQP : SKP;
     constexpr int NT = RMAX * 2;                                       // = blockDim.x: one wave per 32 rows of the taller side
+    // (the one-pass form at head_dim 64 sits exactly on its 168 registers: WIDE for dQ or for dK / dV spills 2-3 of them, LINES does not)
+    constexpr bool WIDE = SPLIT2 && sf(SF_SPLIT2_WIDE);
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * RMAX * PK + 2 * SQP * 4];
     unsigned char* sA = smem;                     // Q, later K
     unsigned char* sB = smem + RMAX * PK;         // dO, later V
@@ -979,7 +1096,7 @@ void attn_bwd_fused2_kernel(md_attn_args p) {
         }
         if (q < p.Sq) {
             bf16* dQ = reinterpret_cast<bf16*>(p.dq) + b * p.sdq + h * p.hsdq + q * p.lddq;
-            store_rows<HD>(dQ, dqacc, p.scale, lane);
+            store_rows<HD>(dQ, dqacc, p.scale, lane, WIDE && rows16(p.dq, p.lddq, p.sdq, p.hsdq));
         }
     }
     // this wave's 32 key rows, while K and V are still in LDS
@@ -1002,11 +1119,20 @@ void attn_bwd_fused2_kernel(md_attn_args p) {
     }
     __syncthreads();
     // ---- P6 role 2: dK, dV for key rows wave * 32 ..
+    const bool dk16 = rows16(p.dk, p.lddk, p.sdk, p.hsdk), dv16 = rows16(p.dv, p.lddv, p.sdv, p.hsdv);
+    const int64_t key = (int64_t)wave * 32 + (lane & 31);
+    f32x16 dkacc[HD / 32], dvacc[HD / 32];        // (the one-pass form's)
+#pragma unroll
+    for (int di = 0; di < HD / 32; ++di)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            dkacc[di][r] = 0.f;
+            dvacc[di][r] = 0.f;
+        }
     if (krole) {
-        const int64_t key = (int64_t)wave * 32 + (lane & 31);
-        bf16* dK = reinterpret_cast<bf16*>(p.dk) + b * p.sdk + h * p.hsdk + key * p.lddk;
-        bf16* dV = reinterpret_cast<bf16*>(p.dv) + b * p.sdv + h * p.hsdv + key * p.lddv;
         if (SPLIT2) {
+            bf16* dK = reinterpret_cast<bf16*>(p.dk) + b * p.sdk + h * p.hsdk + key * p.lddk;
+            bf16* dV = reinterpret_cast<bf16*>(p.dv) + b * p.sdv + h * p.hsdv + key * p.lddv;
             f32x16 acc[HD / 32];
             // pass 1: dV = P^T dO
 #pragma unroll
@@ -1034,7 +1160,7 @@ void attn_bwd_fused2_kernel(md_attn_args p) {
                 }
             }
             if (key < p.Skv) {
-                store_rows<HD>(dV, acc, 1.f, lane);
+                store_rows<HD>(dV, acc, 1.f, lane, WIDE && dv16);
             }
             // pass 2: dK = dS^T Q
 #pragma unroll
@@ -1068,17 +1194,9 @@ void attn_bwd_fused2_kernel(md_attn_args p) {
                 }
             }
             if (key < p.Skv) {
-                store_rows<HD>(dK, acc, p.scale, lane);
+                store_rows<HD>(dK, acc, p.scale, lane, WIDE && dk16);
             }
         } else {
-            f32x16 dkacc[HD / 32], dvacc[HD / 32];
-#pragma unroll
-            for (int di = 0; di < HD / 32; ++di)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    dkacc[di][r] = 0.f;
-                    dvacc[di][r] = 0.f;
-                }
             for (int i = 0; i < nq32; ++i) {
                 const unsigned char* tQ = sA + i * 32 * PK;
                 const unsigned char* tdO = sB + i * 32 * PK;
@@ -1109,10 +1227,24 @@ void attn_bwd_fused2_kernel(md_attn_args p) {
                     }
                 }
             }
-            if (key < p.Skv) {
-                store_rows<HD>(dK, dkacc, p.scale, lane);
-                store_rows<HD>(dV, dvacc, 1.f, lane);
+        }
+    }
+    if (!SPLIT2) {
+        if (sf(SF_FUSED2_LINES) && dk16 && dv16) {
+            // Q and dO are dead once every wave has left role 2: dK through this wave's 32 rows of tile A, dV through those of tile B
+            __syncthreads();
+            if (krole) {
+                const int nvalid = p.Skv - wave * 32 >= 32 ? 32 : (int)(p.Skv - wave * 32);
+                store_lines<HD>(sA + wave * 32 * PK, PK, reinterpret_cast<bf16*>(p.dk) + b * p.sdk + h * p.hsdk + (int64_t)wave * 32 * p.lddk,
+                                p.lddk, nvalid, dkacc, p.scale, lane);
+                store_lines<HD>(sB + wave * 32 * PK, PK, reinterpret_cast<bf16*>(p.dv) + b * p.sdv + h * p.hsdv + (int64_t)wave * 32 * p.lddv,
+                                p.lddv, nvalid, dvacc, 1.f, lane);
             }
+        } else if (krole && key < p.Skv) {
+            bf16* dK = reinterpret_cast<bf16*>(p.dk) + b * p.sdk + h * p.hsdk + key * p.lddk;
+            bf16* dV = reinterpret_cast<bf16*>(p.dv) + b * p.sdv + h * p.hsdv + key * p.lddv;
+            store_rows<HD>(dK, dkacc, p.scale, lane, false);
+            store_rows<HD>(dV, dvacc, 1.f, lane, false);
         }
     }
 }
