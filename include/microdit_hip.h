@@ -694,6 +694,25 @@ int md_lora_grad_ws_floats(md_lora_item* items_host, int32_t n_items, int32_t ra
 int md_lora_grad(const float* g, const float* adapter, const md_lora_item* items, const md_lora_item* items_host, int32_t n_items,
                  int32_t rank, float scale, float grad_scale, float* d_adapter, float* ws, int64_t ws_floats, hipStream_t stream);
 
+/* (Added under ABI 6: new symbols only.)  The factored weight-gradient backward of one targeted linear y = x W_eff^T: the adapter's
+ * gradient from the backward's dy [M, N] and the saved input x [M, K] (bf16, row-major, leading dimensions lddy >= N, ldx >= K; the
+ * pointers already include any column offset), without forming G = dy^T x:
+ *     P = x A^T [M, r]    Q = dy B [M, r]    dB[n, j] += c * sum_m dy[m, n] P[m, j]    dA[j, k] += c * sum_m Q[m, j] x[m, k]
+ * A [rank, K], B [N, rank], dA, dB fp32 in the adapter's layout.  A, B, P and Q are rounded to bf16 (round to nearest even) as
+ * operands of v_mfma_f32_16x16x32_bf16 (ranks below 16 padded with zero rows); every sum is accumulated in fp32.  No buffer of N * K
+ * elements exists: the workspace holds the bf16 adapter operands [r, N + K], P^T and Q^T [2 r, M] as bf16 and `groups` fp32 shares
+ * [r, N + K] of row groups, which a finish launch of the same call adds in ascending order, multiplies by c and adds into dA / dB.
+ * Four launches (prep, projections, reductions, finish); no atomics, one writer per address, every order a function of (M, N, K,
+ * rank) alone: two calls on the same data give identical bits.  Rows >= M, columns >= N of dy and columns >= K of x are not read.
+ * ws needs no initialisation.  md_lora_wgrad_geometry reports the rows of one strip of the reduction and the number of row groups
+ * (workgroup g of a column block takes the strips g, g + groups, ...).
+ * Supported: rank in {4, 8, 16, 32, 64}; M >= 1, N >= 1 (nothing is assumed to divide them); K, lddy, ldx multiples of 8; every
+ * pointer 16-byte aligned.  Anything else, a NULL pointer, or ws_floats below md_lora_wgrad_ws_floats: MD_BAD_ARG, nothing launched. */
+int md_lora_wgrad_ws_floats(int32_t M, int32_t N, int32_t K, int32_t rank, int64_t* out);
+int md_lora_wgrad_geometry(int32_t M, int32_t N, int32_t K, int32_t rank, int32_t* strip_rows, int32_t* groups);
+int md_lora_wgrad(const void* dy, int32_t lddy, const void* x, int32_t ldx, int32_t M, int32_t N, int32_t K, const float* A,
+                  const float* B, int32_t rank, float c, float* dA, float* dB, float* ws, int64_t ws_floats, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------- dispersive loss */
 /* (Added under ABI 6: new symbols only.)  Batch-repulsion regulariser on one block's output (Wang & He 2025, "Diffuse and Disperse",
  * the InfoNCE-l2 form; no reference counterpart).  Z [B, K] bf16 is the block output of a microbatch, one row per sample:

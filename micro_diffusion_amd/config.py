@@ -217,7 +217,7 @@ def lora_options(cfg: Dict[str, Any], world: Any = None) -> Dict[str, Any]:
     attention projections of every block), misc.lora_weight_decay (default 0) and misc.lora_load_path (an adapter file to start from).
     Returns {"enabled", "rank", "alpha", "targets", "weight_decay", "load_path"}.  Raises ValueError on values the kernels cannot
     honour, on the other keys given without a rank, and on what LoRA training does not cover: more than one rank (`world`, default the
-    WORLD_SIZE environment variable), algorithms.ema, misc.posthoc_ema_* and misc.optimizer_monitor_interval > 0."""
+    WORLD_SIZE environment variable) unless misc.lora_backward is "factored" (lora_backward_option), algorithms.ema, misc.posthoc_ema_* and misc.optimizer_monitor_interval > 0."""
     import os
     from .lora import DEFAULT_TARGETS, RANKS
     misc = cfg.get("misc") or {}
@@ -260,8 +260,9 @@ def lora_options(cfg: Dict[str, Any], world: Any = None) -> Dict[str, Any]:
     if path is not None and not isinstance(path, str):
         raise ValueError(f"misc.lora_load_path must be a path, got {path!r}")
     world = int(os.environ.get("WORLD_SIZE", "1")) if world is None else int(world)
-    if world > 1:
-        raise ValueError(f"misc.lora_rank: LoRA training is single-GPU for now (WORLD_SIZE = {world}); data parallelism is a follow-up")
+    if world > 1 and lora_backward_option(cfg) != "factored":
+        raise ValueError(f"misc.lora_rank: LoRA training is single-GPU for now (WORLD_SIZE = {world}); data parallelism is a follow-up "
+                         "of the projected backward; misc.lora_backward: factored trains data-parallel")
     if (cfg.get("algorithms") or {}).get("ema"):
         raise ValueError("misc.lora_rank with algorithms.ema: the adapter is a few MB, an average of the frozen base is not kept")
     for k in ("posthoc_ema_sigma_rels", "posthoc_ema_snapshot_interval"):
@@ -270,6 +271,23 @@ def lora_options(cfg: Dict[str, Any], world: Any = None) -> Dict[str, Any]:
     if int(misc.get("optimizer_monitor_interval", 0) or 0) > 0:
         raise ValueError("misc.lora_rank with misc.optimizer_monitor_interval > 0: the monitor's tables cover the base's optimiser pass")
     return {"enabled": True, "rank": rank, "alpha": alpha, "targets": targets, "weight_decay": float(wd), "load_path": path}
+
+
+def lora_backward_option(cfg: Dict[str, Any]) -> str:
+    """misc.lora_backward: "projected" (default: dA, dB projected once per step from the base's accumulated gradient) or
+    "factored" (dA, dB straight from every targeted linear's dy and x; the base's gradient is never formed, data parallelism is
+    available).  Its own function: lora_options' dict stays what it was.  Raises ValueError on another value and on the key without
+    misc.lora_rank."""
+    from .lora import BACKWARDS
+    misc = cfg.get("misc") or {}
+    mode = misc.get("lora_backward")
+    if mode is None:
+        return "projected"
+    if not isinstance(mode, str) or mode not in BACKWARDS:
+        raise ValueError(f"misc.lora_backward must be one of {BACKWARDS}, got {mode!r}")
+    if not misc.get("lora_rank"):
+        raise ValueError("misc.lora_backward needs misc.lora_rank")
+    return mode
 
 
 def muon_options(cfg: Dict[str, Any]) -> Dict[str, Any]:

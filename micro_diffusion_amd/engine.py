@@ -239,6 +239,10 @@ class DiTEngine:
     # False inside a dgrad-only backward (backward(param_grads=False)): the helpers that write self.G -- lin_wgrad,
     # _param_acc, _param_colsum, ln_bwd's weight reduction -- launch nothing; every data-gradient launch is the one of a full backward
     _param_grads = True
+    # True inside backward(param_grads="lora") ("Factored backward"): a dgrad-only backward in which lin_wgrad hands the
+    # operands of every linear the attached adapter targets to md_lora_wgrad (lora.LoRA.wgrad); self.G is not touched
+    _lora_grads = False
+    lora = None                         # the attached lora.LoRA (LoRA.attach / detach; LatentDiffusion.train_microbatch)
     # True inside a backward that stops at the image (input_grads=("x",), param_grads=False): nothing that dx does not
     # depend on is launched -- the K side of the cross-attention QK-LayerNorm, the caption-token and condition-vector contractions
     _x_only = False
@@ -574,7 +578,11 @@ class DiTEngine:
         if dxin is None:
             dxin = self.empty(rows, d)
         if self._fused12(pre):
-            self.lin_wgrad(dh12, xin, pre + ".w1", rows, 2 * f, d, defer=defer)
+            if self._lora_grads:           # an adapter sits on w1 or w2, not on the stacked [w1; w2]: one call per half
+                self.lin_wgrad(dh12, xin, pre + ".w1", rows, f, d, lddy=2 * f)
+                self.lin_wgrad(dh12, xin, pre + ".w2", rows, f, d, lddy=2 * f, dyoff=f)
+            else:
+                self.lin_wgrad(dh12, xin, pre + ".w1", rows, 2 * f, d, defer=defer)
             self.lin_dgrad(dh12, pre + ".w1", dxin, rows, 2 * f, d)
         else:
             self.lin_wgrad(dh12, xin, pre + ".w1", rows, f, d, lddy=2 * f, defer=defer)
@@ -632,6 +640,8 @@ class DiTEngine:
         defer: with a weight-gradient group open (_wgrad_begin), only record the problem -- the whole group runs as ONE grouped
         launch at _wgrad_flush().  The caller guarantees that dy and x are not modified before the flush."""
         if not self._param_grads:
+            if self._lora_grads and self.lora.is_target(wname + ".weight"):      # at once: dy and x are valid at the call
+                self.lora.wgrad(wname + ".weight", dy.data_ptr() + 2 * dyoff, lddy or N, x.data_ptr() + 2 * xoff, ldx or K, M)
             return
         gb = self.G.get(wname + ".bias")
         if gb is not None:
@@ -1583,7 +1593,7 @@ class DiTEngine:
                      tp.W, cfg.patch_size)
         return img
 
-    def backward(self, tp: Tape, dtok: torch.Tensor, on_segment=None, *, input_grads=(), param_grads: bool = True) -> InputGrads:
+    def backward(self, tp: Tape, dtok: torch.Tensor, on_segment=None, *, input_grads=(), param_grads=True) -> InputGrads:
         """dtok: bf16 [B*Tk, p*p*C] grad of the network output for the kept tokens.  Accumulates every parameter
         gradient into the fp32 grad buffers (self.G).  `on_segment(prefix)` is called as soon as every kernel that
         writes the gradients of the parameters under `prefix` has been enqueued (data-parallel bucket hand-off).
@@ -1591,6 +1601,8 @@ class DiTEngine:
         4.17); they are fresh tensors of the torch allocator, never arena memory.  Empty: the launches of a backward without them.
         param_grads=False: the dgrad-only backward -- nothing under self.G is written or zeroed and no weight-gradient, bias or
         LayerNorm-weight reduction is launched; every data-gradient launch is the one of a full backward.
+        param_grads="lora": param_grads=False, plus one md_lora_wgrad per linear the attached factored adapter targets, into the
+        adapter's own gradient buffer; raises without an attached, active adapter built with backward="factored".
         input_grads=("x",) with param_grads=False stops at the image: it returns right after md_patch_embed_dgrad and
         launches nothing dx does not depend on; dx has the bits of the full dgrad-only backward.  It is the only backward of an
         input_tape (forward(..., input_tape=True)), whose conditioning is frozen; a tape of a forward that read patches= gives the
@@ -1598,7 +1610,14 @@ class DiTEngine:
         want = frozenset(input_grads)
         if not want <= {"x", "t", "y"}:
             raise ValueError(f"input_grads must be a subset of {{'x', 't', 'y'}}, got {sorted(want)}")
-        x_only = want == {"x"} and not param_grads
+        lora_grads = isinstance(param_grads, str)
+        if lora_grads:
+            if param_grads != "lora":
+                raise ValueError(f"param_grads must be True, False or 'lora', got {param_grads!r}")
+            if self.lora is None or not self.lora.factored:
+                raise RuntimeError("backward(param_grads='lora') needs an attached, active adapter built with LoRA(backward='factored')")
+            param_grads = False
+        x_only = want == {"x"} and not param_grads and not lora_grads
         if getattr(tp, "input_tape", False) and not x_only:
             raise RuntimeError("an input_tape holds a frozen conditioning: its backward takes input_grads=('x',) and param_grads=False, "
                                f"got input_grads={sorted(want)}, param_grads={bool(param_grads)}")
@@ -1608,13 +1627,13 @@ class DiTEngine:
             self._scratch_arena.begin((tp.B, tp.T, tp.Tk, tp.Lc, tp.H, tp.W))
             self._arena = self._scratch_arena
         ok = False
-        self._param_grads, self._x_only = bool(param_grads), x_only
+        self._param_grads, self._x_only, self._lora_grads = bool(param_grads), x_only, lora_grads
         try:
             out = self._backward(tp, dtok, on_segment, want)
             ok = True
             return out
         finally:
-            self._param_grads, self._x_only = True, False
+            self._param_grads, self._x_only, self._lora_grads = True, False, False
             if use:
                 self._scratch_arena.end(ok)
             self._arena = None

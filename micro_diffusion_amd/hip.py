@@ -290,6 +290,10 @@ _sig("md_ema_power_update_ranges", P, P, P, I32, P, P, I32, P, P)
 _sig("md_lora_merge", P, P, P, P, I32, I32, F32, P, I32, P)
 _sig("md_lora_grad_ws_floats", P, I32, I32, POINTER(c_int64))
 _sig("md_lora_grad", P, P, P, P, I32, I32, F32, F32, P, P, I64, P)
+# ... and the factored backward: dA, dB of one targeted linear straight from dy and x (lora.LoRA.wgrad)
+_sig("md_lora_wgrad_ws_floats", I32, I32, I32, I32, POINTER(c_int64))
+_sig("md_lora_wgrad_geometry", I32, I32, I32, I32, POINTER(c_int32), POINTER(c_int32))
+_sig("md_lora_wgrad", P, I32, P, I32, I32, I32, I32, P, P, I32, F32, P, P, P, I64, P)
 # dispersive loss (disperse.py): the pairwise stage between the Gram and the injection GEMM, and the bounds-checked Gram
 _sig("md_disperse_ws_doubles", I64, POINTER(c_int64))
 _sig("md_disperse_pairs", P, I64, I64, I64, F32, F64, P, I64, P, P, I64, P, P, F32, P)

@@ -10,7 +10,16 @@ no change to the forward / backward launch sequences.  For a targeted matrix W [
 with c = scale * grad_scale: the chain rule through W_eff = W + scale * B A, exact, and linear in G -- so it is applied to the sum over
 the microbatches.  The masters p never change.  LoRAAdamW is what the Trainer steps in place of FusedAdamW: projection, clear of g,
 norm / guard, AdamW on the adapter's few million values, merge.  The `ref_*` functions restate the two formulas in fp64 torch for the
-tests.  `device="cpu"` holds the state only (target resolution, state_dict round trips); the kernels need a GPU."""
+tests.
+
+`backward="factored"` (opt-in; the default "projected" is the above) never forms G_W: the engine's backward(param_grads="lora") hands
+every targeted linear's dy [M, N] and saved input x [M, K] to md_lora_wgrad, which adds
+
+    dB += c * dy^T (x A^T),   dA += c * (dy B)^T x          c = scale
+
+into the adapter's gradient buffer per microbatch (the same chain rule, linear in the microbatch); no other parameter gradient is
+launched, the base's accumulator is neither written nor cleared, and what a data-parallel step exchanges is the adapter's gradient: one
+fp32 all-reduce (Trainer).  `device="cpu"` holds the state only (target resolution, state_dict round trips); the kernels need a GPU."""
 from __future__ import annotations
 
 import math
@@ -23,7 +32,8 @@ import torch
 
 from .arch import ParamSpec
 
-RANKS = (4, 8, 16, 32, 64)                   # what md_lora_merge / md_lora_grad accept
+RANKS = (4, 8, 16, 32, 64)                   # what md_lora_merge / md_lora_grad / md_lora_wgrad accept
+BACKWARDS = ("projected", "factored")        # how the adapter's gradient is formed ("Factored backward")
 # the five attention projections of every mixer and backbone block (not the caption block's: y_emb_preprocess.attn.*)
 DEFAULT_TARGETS = tuple(r"^(patch_mixer|blocks)\.\d+\." + m + r"\.weight$"
                         for m in (r"attn\.qkv", r"attn\.proj", r"cross_attn\.q_linear", r"cross_attn\.kv_linear", r"cross_attn\.proj"))
@@ -93,16 +103,30 @@ def ref_grad(G, A, B, scale: float, grad_scale: float = 1.0):
     return c * (B.double().t() @ G.double()), c * (G.double() @ A.double().t())
 
 
+def ref_wgrad_factored(dy, x, A, B, c: float):
+    """(dA [r, K], dB [N, r]) in fp64 from one linear's dy [M, N] and x [M, K]: c * (dy B)^T x and c * dy^T (x A^T) -- ref_grad of
+    G = dy^T x, without G."""
+    dy, x, A, B = dy.double(), x.double(), A.double(), B.double()
+    return float(c) * ((dy @ B).t() @ x), float(c) * (dy.t() @ (x @ A.t()))
+
+
+def check_backward(backward) -> str:
+    if backward not in BACKWARDS:
+        raise ValueError(f"lora: backward must be one of {BACKWARDS}, got {backward!r}")
+    return backward
+
+
 class LoRA:
     """Adapters for the targeted matrices of one DiT: one flat fp32 buffer `w` for every A / B, one of the same layout `g` for their
     gradients, and the item table of the two kernels (a host copy and a device copy).  A is drawn on the CPU from `seed`
     (kaiming_uniform_(a=sqrt 5) per target, in table order: identical on every device), B = 0: a fresh adapter leaves the weights alone."""
 
     def __init__(self, dit, rank: int = 16, alpha: Optional[float] = None, targets: Sequence[str] = DEFAULT_TARGETS, seed: int = 0,
-                 device="cuda"):
+                 device="cuda", backward: str = "projected"):
         from .dit import flat_layout
         self.dit = dit
         self.rank = check_rank(rank)
+        self.backward = check_backward(backward)     # not part of state_dict(): an adapter file loads into either mode
         if alpha is not None and not (isinstance(alpha, (int, float)) and not isinstance(alpha, bool) and math.isfinite(alpha)):
             raise ValueError(f"lora: alpha must be a finite number, got {alpha!r}")
         self.alpha = float(rank if alpha is None else alpha)
@@ -129,6 +153,9 @@ class LoRA:
         self._items_dev = None
         self._ws = None
         self.ws_floats = 0
+        self._shape_of = {s.name: (int(s.shape[0]), int(s.shape[1])) for s in self.specs}
+        self._wgrad_ws = None                        # factored backward: the workspace of md_lora_wgrad, grown on demand
+        self._wgrad_need = {}                        # (M, N, K) -> md_lora_wgrad_ws_floats
 
     # -------------------------------------------------------------------------------------------- views
     def A(self, name: str) -> torch.Tensor:
@@ -201,6 +228,42 @@ class LoRA:
                   "md_lora_grad")
 
     @property
+    def factored(self) -> bool:
+        """The adapter's gradient comes from the engine's backward(param_grads="lora"), not from the base's accumulated gradient."""
+        return self.backward == "factored" and self.active
+
+    def is_target(self, name: str) -> bool:
+        return name in self._shape_of
+
+    def _wgrad_floats(self, M: int, N: int, K: int) -> int:
+        from . import hip
+        key = (M, N, K)
+        if key not in self._wgrad_need:
+            need = c_int64(0)
+            hip.check(hip.lib().md_lora_wgrad_ws_floats(M, N, K, self.rank, byref(need)), "md_lora_wgrad_ws_floats")
+            self._wgrad_need[key] = int(need.value)
+        return self._wgrad_need[key]
+
+    def wgrad_workspace(self, M: int) -> torch.Tensor:
+        """The workspace of md_lora_wgrad: the maximum over the targets at the largest M seen so far (the adapter's own buffer, not the
+        engine's split-K workspace: it lives across the launches of one call only, but its size follows the adapter's targets)."""
+        need = max(self._wgrad_floats(M, n, k) for n, k in set(self._shape_of.values()))
+        if self._wgrad_ws is None or self._wgrad_ws.numel() < need:
+            self._wgrad_ws = torch.empty(need, device=self.w.device, dtype=torch.float32)
+        return self._wgrad_ws
+
+    def wgrad(self, name: str, dy_ptr: int, lddy: int, x_ptr: int, ldx: int, M: int, c: Optional[float] = None) -> None:
+        """md_lora_wgrad: g += (dA, dB) of target `name` from one linear's dy [M, N] / x [M, K] (device addresses of bf16 rows,
+        column offsets included); c defaults to the adapter's scale."""
+        from . import hip
+        N, K = self._shape_of[name]
+        ws = self.wgrad_workspace(M)
+        a, b = self.offs[name]
+        hip.check(hip.lib().md_lora_wgrad(dy_ptr, lddy, x_ptr, ldx, M, N, K, self.w.data_ptr() + 4 * a, self.w.data_ptr() + 4 * b,
+                                          self.rank, float(self._scale if c is None else c), self.g.data_ptr() + 4 * a,
+                                          self.g.data_ptr() + 4 * b, ws.data_ptr(), ws.numel(), hip.stream_ptr()), "md_lora_wgrad")
+
+    @property
     def active(self) -> bool:
         """Whether the shadow carries the adapter: attached, enabled and scale != 0 (otherwise the shadow is the plain bf16(p))."""
         return self.attached and self._enabled and self._scale != 0.0
@@ -218,6 +281,7 @@ class LoRA:
             raise RuntimeError("lora: attach() needs the adapter on the GPU (the merge is a HIP kernel; there is no CPU fallback)")
         self.dit._ensure_flat()
         self.dit._lora = self
+        self.dit._engine.lora = self
         self.attached = True
         self.dit.refresh_shadow(force=True)
         return self
@@ -225,6 +289,8 @@ class LoRA:
     def detach(self) -> None:
         if self.attached:
             self.dit._lora = None
+            if self.dit._engine is not None:
+                self.dit._engine.lora = None
             self.attached = False
             self.dit.refresh_shadow(force=True)
 
@@ -291,10 +357,10 @@ class LoRA:
             self.dit.refresh_shadow(force=True)
 
     @classmethod
-    def from_state_dict(cls, dit, sd: dict, device="cuda") -> "LoRA":
+    def from_state_dict(cls, dit, sd: dict, device="cuda", backward: str = "projected") -> "LoRA":
         """An adapter built from a file (state_dict()): LoRA.from_state_dict(model.dit, torch.load(path)).attach()."""
         ad = cls(dit, rank=int(sd["rank"]), alpha=float(sd["alpha"]), targets=list(sd["targets"]), seed=int(sd.get("seed", 0)),
-                 device=device)
+                 device=device, backward=backward)
         ad.load_state_dict(sd)
         return ad
 
@@ -304,7 +370,10 @@ class LoRAAdamW:
     the base's size is allocated (no base moments, EMA or post-hoc averages); the gradient norm that is clipped and guarded is the
     adapter's, since the base is frozen.  A NaN / Inf in the gradient of a targeted matrix reaches the adapter's gradient through the
     projection, so `skip_nonfinite` guards the step as it does for FusedAdamW: the adapter and its moments stay untouched bit for bit,
-    both accumulators are still cleared, the step is counted."""
+    both accumulators are still cleared, the step is counted.
+    With a factored adapter (LoRA(backward="factored")) the adapter's gradient is already in adapter.g when step() runs: no projection
+    and no clear of the base's accumulator (nothing wrote it); grad_scale goes into the AdamW launch, which also scales the norm it
+    clips by and clears adapter.g -- on a guarded skipped step too."""
 
     def __init__(self, adapter: LoRA, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  skip_nonfinite: bool = False):
@@ -322,6 +391,7 @@ class LoRAAdamW:
         self.skip_nonfinite = bool(skip_nonfinite)
         self.guard_state = torch.zeros(4, device=dev, dtype=torch.int32) if self.skip_nonfinite else None
         self.last_grad_scale = 1.0
+        self._norm_unscaled = False                # the last step's sumsq was taken before grad_scale (the factored step)
         self.ema, self.posthoc = None, []          # what Trainer.consolidate / sync_replicas enumerate: nothing of the base's size
 
     def ensure_norm_slots(self, n: int) -> None:
@@ -338,7 +408,8 @@ class LoRAAdamW:
 
     def grad_norm(self) -> torch.Tensor:
         """||g||_2 of the adapter's gradient of the last step before clipping (valid after step() with max_norm > 0 or skip_nonfinite)."""
-        return self.sumsq.sqrt().reshape(())
+        n = self.sumsq.sqrt().reshape(())
+        return n * self.last_grad_scale if self._norm_unscaled else n
 
     def step(self, lr: Optional[float] = None, max_norm: float = 0.0, grad_scale: float = 1.0, g_bf16: Optional[torch.Tensor] = None,
              norm_partials: int = 0) -> None:
@@ -353,8 +424,11 @@ class LoRAAdamW:
         L, st = hip.lib(), hip.stream_ptr()
         self.step_count += 1
         self.last_grad_scale = grad_scale
-        ad.project_grad(grad_scale)                                                           # 1. dA, dB from the accumulated G
-        hip.check(L.md_fill_zero(f["g"].data_ptr(), 4 * f["total"], st), "md_fill_zero")      # 2. clear the accumulator
+        factored = ad.backward == "factored"
+        self._norm_unscaled = factored
+        if not factored:
+            ad.project_grad(grad_scale)                                                       # 1. dA, dB from the accumulated G
+            hip.check(L.md_fill_zero(f["g"].data_ptr(), 4 * f["total"], st), "md_fill_zero")  # 2. clear the accumulator
         ss = None
         if (max_norm and max_norm > 0) or self.skip_nonfinite:                                # 3. the adapter's gradient norm
             hip.check(L.md_sumsq(ad.g.data_ptr(), 0, ad.total, self.partials.data_ptr(), st), "md_sumsq")
@@ -363,10 +437,11 @@ class LoRAAdamW:
             if self.skip_nonfinite:                                                           # 4. the go flag
                 hip.check(L.md_step_guard(self.sumsq.data_ptr(), self.guard_state.data_ptr(), st), "md_step_guard")
         b1, b2 = self.betas
-        # 5. AdamW on the adapter (grad_scale went into the projection; no shadow: the merge below writes it)
+        # 5. AdamW on the adapter (grad_scale went into the projection -- factored: into this launch, which scales the norm it clips
+        #    by with it; no shadow: the merge below writes it); zero_grad clears adapter.g, on a guarded skipped step too
         a = hip.AdamWArgs(ad.w.data_ptr(), ad.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), None, ss, None, None, ad.total,
                           float(self.lr if lr is None else lr), b1, b2, self.eps, self.weight_decay, 1 - b1 ** self.step_count,
-                          1 - b2 ** self.step_count, max_norm or 0.0, 1.0, 0.0, 1, 0)
+                          1 - b2 ** self.step_count, max_norm or 0.0, float(grad_scale) if factored else 1.0, 0.0, 1, 0)
         if self.skip_nonfinite:
             hip.check(L.md_adamw_step_guarded(byref(a), self.guard_state.data_ptr(), st), "md_adamw_step_guarded")
         else:
@@ -392,4 +467,5 @@ def allocated_floats(opt: LoRAAdamW) -> int:
     """fp32 elements the adapter and its optimiser hold (weights, gradients, moments, workspace, norm partials)."""
     ad = opt.adapter
     ad._items()
-    return 2 * ad.total + 2 * opt.m.numel() + max(ad.ws_floats, 4) + opt.partials.numel() + 1
+    wgrad = 0 if ad._wgrad_ws is None else ad._wgrad_ws.numel()          # the factored backward's workspace, once a backward has run
+    return 2 * ad.total + 2 * opt.m.numel() + max(ad.ws_floats, 4) + wgrad + opt.partials.numel() + 1

@@ -221,8 +221,13 @@ class LatentDiffusion(nn.Module):
             eng.disperse = None
         if getattr(tape, "disperse", None) is not None:
             self._disperse_result = tape.disperse.result
-        dit.attach_grads()
-        dit._engine.backward(tape, dtb, on_segment=getattr(dit, "_on_segment", None))
+        ad = getattr(dit, "_lora", None)
+        if ad is not None and ad.factored:       # the adapter's gradient straight from dy and x (c = scale: the microbatch weight is in dy);
+            eng.lora = ad                        # the base's .grad views are neither created nor written
+            eng.backward(tape, dtb, on_segment=getattr(dit, "_on_segment", None), param_grads="lora")
+        else:
+            dit.attach_grads()
+            eng.backward(tape, dtb, on_segment=getattr(dit, "_on_segment", None))
         return loss
 
     def model_forward_wrapper(self, x, sigma, y, model_forward_fxn, mask_ratio: float, **kwargs) -> dict:

@@ -570,8 +570,11 @@ class GradSync:
     md_sumsq), so the clip coefficient needs no extra pass after the last bucket and is bit-identical on all ranks."""
 
     def __init__(self, dit, process_group=None, exchange: str = "auto", single_rank_exchange: bool = False, mode: str = "auto",
-                 transport: str = "torch"):
-        """`single_rank_exchange`: run the whole exchange path (staging cast, asynchronous collectives, side-stream norm) also on
+                 transport: str = "torch", grad_exchange: bool = True):
+        """`grad_exchange=False` (the Trainer under a factored LoRA adapter): the base's gradient is never formed, so
+        there is nothing of its size to exchange -- no gbf / gred / ssend, on_segment a no-op, finish() returns 0 slots, no bf16 store
+        path; the process group, rank / world, _all_reduce (all transports) and the Trainer's CU reservation work as always.
+        `single_rank_exchange`: run the whole exchange path (staging cast, asynchronous collectives, side-stream norm) also on
         a process group of ONE rank, where every collective is the identity — the only way to drive the RCCL code path on a box
         with a single GPU (tests/test_dp_gpu.py); never set in production.
         `transport`: "torch" — the collectives are torch.distributed calls (backend "nccl" = RCCL); "native" — they go through
@@ -582,6 +585,11 @@ class GradSync:
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
         self.enabled = self.world > 1 or (single_rank_exchange and dist.is_initialized())
+        self.grad_exchange = bool(grad_exchange)
+        if not self.grad_exchange:
+            if mode == "sharded":
+                raise ValueError("the sharded exchange needs the gradient exchange (grad_exchange=True)")
+            exchange, mode = "fp32", "allreduce"
         assert transport in ("torch", "native")
         self.transport = transport if self.enabled else "torch"
         self.comm = None
@@ -821,7 +829,7 @@ class GradSync:
             self.pending.append(self._track(work))
 
     def on_segment(self, name: str) -> None:
-        if not self.active or not self.enabled:
+        if not self.active or not self.enabled or not self.grad_exchange:
             return
         for lo, hi in self.ranges.get(name, []):
             self._exchange(lo, hi)
@@ -918,22 +926,26 @@ class Trainer:
             exchange = os.environ["MD_DP_EXCHANGE"]
         if transport == "auto":                # MD_COMM=native: the exchange through libmicrodit_comm.so instead of torch.distributed
             transport = os.environ.get("MD_COMM", "torch")
-        if not getattr(optimizer, "shardable", True):      # muon.Muon: orthogonalises whole matrices, a rank of the sharded step owns slices
+        adapter = getattr(optimizer, "adapter", None)
+        # a factored LoRA adapter: the base's gradient does not exist; what the ranks exchange is adapter.g, one all-reduce
+        self.lora_factored = adapter is not None and getattr(adapter, "backward", "projected") == "factored"
+        # muon.Muon: orthogonalises whole matrices, a rank of the sharded step owns slices; factored LoRA: nothing of the base's to shard
+        if not getattr(optimizer, "shardable", True) or self.lora_factored:
             if dp_mode == "sharded":
                 raise NotImplementedError(f"{type(optimizer).__name__} does not run under dp_mode='sharded' (a rank owns slices of "
                                           "buckets, not whole matrices); use dp_mode='allreduce'")
             dp_mode = "allreduce"
         model.dit._ensure_flat()
         self.sync = GradSync(model.dit, process_group, exchange=exchange, single_rank_exchange=single_rank_exchange, mode=dp_mode,
-                             transport=transport)
+                             transport=transport, grad_exchange=not self.lora_factored)
         optimizer.ensure_norm_slots(len(self.sync.bucket_list))     # one slot per bucket: the sharded norm has no other source
         self.sync.norm_partials = optimizer.partials
         if getattr(model.dit.engine, "deterministic", False):
             self.sync.deterministic = True
         self.world = self.sync.world
-        if getattr(optimizer, "adapter", None) is not None and self.world > 1:
-            raise NotImplementedError("LoRA training is single-GPU for now: data parallelism (project locally, then all-reduce the "
-                                      "adapter gradient) is not implemented")
+        if adapter is not None and not self.lora_factored and self.world > 1:
+            raise NotImplementedError("LoRA training with the projected backward is single-GPU: data parallelism needs "
+                                      "LoRA(backward='factored') (misc.lora_backward: factored), which all-reduces the adapter gradient")
         self.sharded = self.sync.enabled and self.sync.mode == "sharded"
         self.stale_foreign_chunks = False    # sharded: fp32 masters / moments of the other ranks' chunks are out of date
         self.shard_chunk_of = None           # measurement aid, see FusedAdamW.step_sharded
@@ -1016,6 +1028,8 @@ class Trainer:
             self._comm_events.append((e0, e1))
         if lw is not None and self.world > 1:
             self._reduce_loss_weighting_grad()
+        if self.lora_factored and self.world > 1:
+            self._reduce_adapter_grad()
         if self.monitor_interval > 0 and (self.batches_seen + 1) % self.monitor_interval == 0:
             self.collect_tensor_stats()                  # reads the gradients the optimiser pass is about to consume and clear
         fac = self.schedule.factor(self.batches_seen) if self.schedule is not None else 1.0
@@ -1044,6 +1058,14 @@ class Trainer:
         exchange modes; the 1 / world factor goes into the AdamW launch's grad_scale as for the other gradients.  A sum of `world`
         addends per element: every rank receives the same bits."""
         w = self.sync._all_reduce(self.loss_weighting.g)
+        if w is not None:
+            w.wait()
+
+    def _reduce_adapter_grad(self) -> None:
+        """Factored LoRA under data parallelism: one fp32 all-reduce (sum) of the adapter's gradient between the last backward and the
+        optimiser pass, the same in every transport; the 1 / world factor goes into the AdamW launch's grad_scale.  Every rank receives
+        the same bits, so replicas that start identical (A from the CPU seed, B = 0) stay identical."""
+        w = self.sync._all_reduce(self.opt.adapter.g)
         if w is not None:
             w.wait()
 
@@ -1240,6 +1262,8 @@ class Trainer:
         self.consolidate()          # after a sharded step rank 0's masters of foreign chunks are stale: make them whole first
         f = self.model.dit.flat_buffers()
         bufs = [f["p"], self.opt.m, self.opt.v] + ([self.opt.ema] if self.opt.ema is not None else []) + list(self.opt.posthoc)
+        if getattr(self.opt, "adapter", None) is not None:
+            bufs.append(self.opt.adapter.w)
         if self.loss_weighting is not None:
             lw = self.loss_weighting
             bufs += [lw.freq, lw.phase, lw.w, lw.m, lw.v]

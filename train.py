@@ -30,6 +30,7 @@ def train(cfg: dict):
     lwopt = mdcfg.loss_weighting_options(cfg)    #  likewise: channels / lr checked here
     dsp = mdcfg.disperse_options(cfg)            #  likewise: weight / tau / block checked here
     lora = mdcfg.lora_options(cfg)               #  likewise: rank / targets checked, unsupported combinations refused
+    lora_backward = mdcfg.lora_backward_option(cfg)     # "projected" | "factored" (the latter also trains data-parallel)
     muon = mdcfg.muon_options(cfg)               #  likewise: momentum / steps / adjust / targets checked here
     if lora["enabled"] and not cfg["trainer"].get("load_path"):
         raise ValueError("misc.lora_rank needs trainer.load_path: the adapter is trained on a frozen, trained base")
@@ -96,8 +97,11 @@ def train(cfg: dict):
     adapter = None
     if lora["enabled"]:
         # LoRA: the optimiser block's lr / betas / eps drive AdamW on the adapter alone; A is drawn on the CPU from
-        # the run's seed, B = 0 (or both come from misc.lora_load_path)
-        adapter = LoRA(model.dit, rank=lora["rank"], alpha=lora["alpha"], targets=lora["targets"], seed=cfg["seed"])
+        # the run's seed, B = 0 (or both come from misc.lora_load_path) -- the same on every rank.  misc.lora_backward: factored forms
+        # the adapter's gradient in the backward itself; under WORLD_SIZE > 1 the ranks all-reduce it, rank 0 writes the adapter
+        # checkpoints below and every rank loads them on autoresume
+        adapter = LoRA(model.dit, rank=lora["rank"], alpha=lora["alpha"], targets=lora["targets"], seed=cfg["seed"],
+                       backward=lora_backward)
         if lora["load_path"]:
             asd = torch.load(lora["load_path"], map_location="cuda")
             adapter.load_state_dict(asd.get("lora", asd))
