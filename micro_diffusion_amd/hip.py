@@ -335,20 +335,16 @@ ADAMW_MAX_RANGES = 64    # MD_ADAMW_MAX_RANGES
 def ema_power_update(p, emas, betas, n, guard=None, flat_off=None, count=None, stream=None, expect=0):
     """md_ema_power_update (or, with flat_off / count -- ctypes int64 arrays or sequences --, its _ranges form).  p / emas / guard:
     ints (device addresses) or torch tensors; betas: Python floats.  expect=None returns the code instead of raising."""
-    def ptr(x):
-        if x is None:
-            return None
-        return x if isinstance(x, int) else x.data_ptr()
     k = len(emas)
-    ev = (c_void_p * max(k, 1))(*[ptr(e) for e in emas])
+    ev = (c_void_p * max(k, 1))(*[_ptr(e) for e in emas])
     bv = (c_float * max(k, 1))(*[float(b) for b in betas])
     st = stream if stream is not None else stream_ptr()
     if flat_off is None:
-        rc = lib().md_ema_power_update(ptr(p), ev, bv, k, n, ptr(guard), st)
+        rc = lib().md_ema_power_update(_ptr(p), ev, bv, k, n, _ptr(guard), st)
     else:
         if not isinstance(flat_off, ctypes.Array):
             flat_off, count = (c_int64 * len(flat_off))(*flat_off), (c_int64 * len(count))(*count)
-        rc = lib().md_ema_power_update_ranges(ptr(p), ev, bv, k, flat_off, count, len(flat_off), ptr(guard), st)
+        rc = lib().md_ema_power_update_ranges(_ptr(p), ev, bv, k, flat_off, count, len(flat_off), _ptr(guard), st)
     if expect is None:
         return rc
     check(rc, "md_ema_power_update")
@@ -364,6 +360,39 @@ def stream_ptr():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _ptr(x):
+    """A device address from an int, a torch tensor or None."""
+    if x is None:
+        return None
+    return x if isinstance(x, int) else x.data_ptr()
+
+
+def adamw_step(w, g, m, v, n, *, lr, betas, eps, weight_decay, step, shadow=None, sumsq=None, g_bf16=None, ema=None, ema_smoothing=0.0,
+               max_norm=0.0, grad_scale=1.0, zero_grad=1, ema_mode=0, guard=None, ranges=None, stream=None):
+    """One AdamW launch: md_adamw_step, with `guard` (the md_step_guard state) its _guarded form, with `ranges` = (flat offsets,
+    counts) as ctypes int64 arrays its _ranges form (`n` is then unused), with both md_adamw_step_ranges_guarded.  The only place that
+    fills md_adamw_args.  w / g / m / v / shadow / sumsq / g_bf16 / ema / guard: ints (device addresses) or torch tensors; `step`
+    (counted from 1) gives the bias corrections 1 - beta ** step."""
+    b1, b2 = betas
+    a = AdamWArgs(p=_ptr(w), g=_ptr(g), m=_ptr(m), v=_ptr(v), shadow=_ptr(shadow), sumsq=_ptr(sumsq), g_bf16=_ptr(g_bf16), ema=_ptr(ema),
+                  n=n, lr=lr, beta1=b1, beta2=b2, eps=eps, weight_decay=weight_decay, bias_corr1=1 - b1 ** step, bias_corr2=1 - b2 ** step,
+                  max_norm=max_norm or 0.0, grad_scale=grad_scale, ema_smoothing=ema_smoothing or 0.0, zero_grad=zero_grad, ema_mode=ema_mode)
+    name = "md_adamw_step" + ("_ranges" if ranges is not None else "") + ("_guarded" if guard is not None else "")
+    args = [byref(a)] + ([ranges[0], ranges[1], len(ranges[0])] if ranges is not None else []) + ([_ptr(guard)] if guard is not None else [])
+    check(getattr(lib(), name)(*args, stream if stream is not None else stream_ptr()), name)
+
+
+def grad_sumsq(partials, out, *, src=None, src_is_bf16=False, n=0, count=SUMSQ_PARTIALS, guard=None, stream=None):
+    """The gradient-norm tail: md_sumsq of `src` (n elements, fp32 or bf16) into `partials` when `src` is given, md_sumsq_finish over
+    `count` partial sums into `out`, md_step_guard on `out` when `guard` (its state) is given."""
+    L, st = lib(), stream if stream is not None else stream_ptr()
+    if src is not None:
+        check(L.md_sumsq(_ptr(src), 1 if src_is_bf16 else 0, n, _ptr(partials), st), "md_sumsq")
+    check(L.md_sumsq_finish(_ptr(partials), count, _ptr(out), st), "md_sumsq_finish")
+    if guard is not None:
+        check(L.md_step_guard(_ptr(out), _ptr(guard), st), "md_step_guard")
+
+
 def gemm(A, B, C, M, N, K, *, lda, ldb, ldc, a_kcontig=True, b_kcontig=True, mode=EPI_STORE_BF16,
          act=ACT_NONE, alpha=1.0, bias=None, res=None, ldr=0, gate=None, ldg=0, rows_per_sample=0,
          aux=None, ldaux=0, C2=None, ldc2=0, batch=1, sA=0, sB=0, sC=0, sC2=0, sBias=0, sAux=0, sSplit=0, ksplit=1,
@@ -371,15 +400,11 @@ def gemm(A, B, C, M, N, K, *, lda, ldb, ldc, a_kcontig=True, b_kcontig=True, mod
          tail_ws=None, tail_mode=0, tail_used=None, dact_cached=0):
     """Raw-pointer GEMM launch.  A/B/C/... are ints (device addresses) or torch tensors.  tail_ws: a torch tensor used as the
     workspace of the whole-rounds + split-K-tail form (md_gemm_args.tail_ws); tail_used: list that receives the split it ran with (0 = not used)."""
-    def ptr(x):
-        if x is None:
-            return None
-        return x if isinstance(x, int) else x.data_ptr()
-    a = GemmArgs(ptr(A), ptr(B), ptr(C), ptr(C2), ptr(bias), ptr(res), ptr(gate), ptr(aux),
+    a = GemmArgs(_ptr(A), _ptr(B), _ptr(C), _ptr(C2), _ptr(bias), _ptr(res), _ptr(gate), _ptr(aux),
                  M, N, K, lda, ldb, ldc, ldc2, ldr, ldg, ldaux, sA, sB, sC, sC2, sBias, sAux, sSplit,
                  rows_per_sample, batch, ksplit, int(a_kcontig), int(b_kcontig), mode, act, alpha, variant, raster_group_n,
-                 ptr(timeline), None, ptr(A_list), ptr(B_list), list_segments, None, 0, cu_limit,
-                 ptr(tail_ws), (tail_ws.numel() * tail_ws.element_size()) if tail_ws is not None else 0, tail_mode, None, dact_cached)
+                 _ptr(timeline), None, _ptr(A_list), _ptr(B_list), list_segments, None, 0, cu_limit,
+                 _ptr(tail_ws), (tail_ws.numel() * tail_ws.element_size()) if tail_ws is not None else 0, tail_mode, None, dact_cached)
     ch, tu = ctypes.c_int32(-1), ctypes.c_int32(-1)
     a.chosen_variant = ctypes.addressof(ch)
     a.tail_used = ctypes.addressof(tu)

@@ -30,7 +30,9 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import hip
 from .arch import ParamSpec
+from .optim import Optimizer
 
 RANKS = (4, 8, 16, 32, 64)                   # what md_lora_merge / md_lora_grad / md_lora_wgrad accept
 BACKWARDS = ("projected", "factored")        # how the adapter's gradient is formed ("Factored backward")
@@ -191,7 +193,6 @@ class LoRA:
 
     def _items(self):
         """(host array, device tensor, n): built on first use; md_lora_grad_ws_floats checks the shapes and writes the workspace offsets."""
-        from . import hip
         if self._items_host is None:
             rows = self.item_rows()
             arr = (hip.LoraItem * len(rows))(*[hip.LoraItem(w, a, b, 0, n, k) for w, a, b, n, k in rows])
@@ -210,7 +211,6 @@ class LoRA:
 
     def merge_into(self, out: torch.Tensor, out_is_f32: bool) -> None:
         """md_lora_merge from the DiT's masters into `out` (the flat bf16 shadow, or a flat fp32 buffer: the masters themselves in fuse())."""
-        from . import hip
         host, dev, n = self._items()
         f = self._flat()
         hip.check(hip.lib().md_lora_merge(f["p"].data_ptr(), self.w.data_ptr(), dev.data_ptr(), host, n, self.rank, float(self._scale),
@@ -218,7 +218,6 @@ class LoRA:
 
     def project_grad(self, grad_scale: float = 1.0) -> None:
         """md_lora_grad: g += (dA, dB) of every target from the DiT's accumulated flat gradient."""
-        from . import hip
         host, dev, n = self._items()
         if self._ws is None:
             self._ws = torch.empty(max(self.ws_floats, 4), device=self.w.device, dtype=torch.float32)
@@ -236,7 +235,6 @@ class LoRA:
         return name in self._shape_of
 
     def _wgrad_floats(self, M: int, N: int, K: int) -> int:
-        from . import hip
         key = (M, N, K)
         if key not in self._wgrad_need:
             need = c_int64(0)
@@ -255,7 +253,6 @@ class LoRA:
     def wgrad(self, name: str, dy_ptr: int, lddy: int, x_ptr: int, ldx: int, M: int, c: Optional[float] = None) -> None:
         """md_lora_wgrad: g += (dA, dB) of target `name` from one linear's dy [M, N] / x [M, K] (device addresses of bf16 rows,
         column offsets included); c defaults to the adapter's scale."""
-        from . import hip
         N, K = self._shape_of[name]
         ws = self.wgrad_workspace(M)
         a, b = self.offs[name]
@@ -365,7 +362,7 @@ class LoRA:
         return ad
 
 
-class LoRAAdamW:
+class LoRAAdamW(Optimizer):
     """What the Trainer steps in place of FusedAdamW when an adapter is trained: AdamW on the adapter's flat buffer alone.  No buffer of
     the base's size is allocated (no base moments, EMA or post-hoc averages); the gradient norm that is clipped and guarded is the
     adapter's, since the base is frozen.  A NaN / Inf in the gradient of a targeted matrix reaches the adapter's gradient through the
@@ -377,34 +374,16 @@ class LoRAAdamW:
 
     def __init__(self, adapter: LoRA, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  skip_nonfinite: bool = False):
-        from . import hip
         self.adapter, self.dit = adapter, adapter.dit
         if not adapter.attached:
             adapter.attach()
-        self.lr, self.betas, self.eps, self.weight_decay = lr, tuple(betas), eps, weight_decay
-        dev = adapter.w.device
+        super().__init__(adapter.w.device, lr, betas, eps, weight_decay, skip_nonfinite)
         self.m = torch.zeros_like(adapter.w)
         self.v = torch.zeros_like(adapter.w)
-        self.sumsq = torch.zeros(1, device=dev)
-        self.partials = torch.zeros(hip.SUMSQ_PARTIALS, device=dev)
-        self.step_count = 0
-        self.skip_nonfinite = bool(skip_nonfinite)
-        self.guard_state = torch.zeros(4, device=dev, dtype=torch.int32) if self.skip_nonfinite else None
-        self.last_grad_scale = 1.0
         self._norm_unscaled = False                # the last step's sumsq was taken before grad_scale (the factored step)
-        self.ema, self.posthoc = None, []          # what Trainer.consolidate / sync_replicas enumerate: nothing of the base's size
 
-    def ensure_norm_slots(self, n: int) -> None:
-        """The per-bucket norm slots of the data-parallel exchange: unused (the norm is the adapter's, taken in step())."""
-
-    def skipped_steps(self) -> int:
-        return int(self.guard_state[1].item()) if self.guard_state is not None else 0
-
-    def swap_ema(self, profile=None):
-        return None
-
-    def ema_state_dict(self):
-        return None
+    def state_buffers(self) -> list:
+        return [self.m, self.v]
 
     def grad_norm(self) -> torch.Tensor:
         """||g||_2 of the adapter's gradient of the last step before clipping (valid after step() with max_norm > 0 or skip_nonfinite)."""
@@ -413,39 +392,27 @@ class LoRAAdamW:
 
     def step(self, lr: Optional[float] = None, max_norm: float = 0.0, grad_scale: float = 1.0, g_bf16: Optional[torch.Tensor] = None,
              norm_partials: int = 0) -> None:
-        from . import hip
         if g_bf16 is not None or norm_partials > 0:
-            raise NotImplementedError("LoRA training is single-GPU for now: data parallelism (project locally, then all-reduce the "
-                                      "adapter gradient) is not implemented, so there is no exchanged gradient buffer to step from")
+            raise NotImplementedError("LoRAAdamW steps from the adapter's own gradient, not from an exchanged gradient buffer: the "
+                                      "projected backward exchanges nothing, data parallelism needs LoRA(backward='factored'), which "
+                                      "all-reduces the adapter's gradient")
         ad = self.adapter
         if not ad.attached or self.dit._lora is not ad:
             raise RuntimeError("LoRAAdamW.step: the adapter is not attached to its DiT")
         f = ad._flat()
-        L, st = hip.lib(), hip.stream_ptr()
         self.step_count += 1
         self.last_grad_scale = grad_scale
         factored = ad.backward == "factored"
         self._norm_unscaled = factored
         if not factored:
             ad.project_grad(grad_scale)                                                       # 1. dA, dB from the accumulated G
-            hip.check(L.md_fill_zero(f["g"].data_ptr(), 4 * f["total"], st), "md_fill_zero")  # 2. clear the accumulator
-        ss = None
-        if (max_norm and max_norm > 0) or self.skip_nonfinite:                                # 3. the adapter's gradient norm
-            hip.check(L.md_sumsq(ad.g.data_ptr(), 0, ad.total, self.partials.data_ptr(), st), "md_sumsq")
-            hip.check(L.md_sumsq_finish(self.partials.data_ptr(), hip.SUMSQ_PARTIALS, self.sumsq.data_ptr(), st), "md_sumsq_finish")
-            ss = self.sumsq.data_ptr()
-            if self.skip_nonfinite:                                                           # 4. the go flag
-                hip.check(L.md_step_guard(self.sumsq.data_ptr(), self.guard_state.data_ptr(), st), "md_step_guard")
-        b1, b2 = self.betas
+            hip.check(hip.lib().md_fill_zero(f["g"].data_ptr(), 4 * f["total"], hip.stream_ptr()), "md_fill_zero")  # 2. clear the accumulator
+        ss = self._norm_and_guard(max_norm, src=ad.g, n=ad.total)                             # 3. the adapter's gradient norm, 4. the go flag
         # 5. AdamW on the adapter (grad_scale went into the projection -- factored: into this launch, which scales the norm it clips
         #    by with it; no shadow: the merge below writes it); zero_grad clears adapter.g, on a guarded skipped step too
-        a = hip.AdamWArgs(ad.w.data_ptr(), ad.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), None, ss, None, None, ad.total,
-                          float(self.lr if lr is None else lr), b1, b2, self.eps, self.weight_decay, 1 - b1 ** self.step_count,
-                          1 - b2 ** self.step_count, max_norm or 0.0, float(grad_scale) if factored else 1.0, 0.0, 1, 0)
-        if self.skip_nonfinite:
-            hip.check(L.md_adamw_step_guarded(byref(a), self.guard_state.data_ptr(), st), "md_adamw_step_guarded")
-        else:
-            hip.check(L.md_adamw_step(byref(a), st), "md_adamw_step")
+        hip.adamw_step(ad.w, ad.g, self.m, self.v, ad.total, lr=float(self.lr if lr is None else lr), betas=self.betas, eps=self.eps,
+                       weight_decay=self.weight_decay, step=self.step_count, sumsq=ss, max_norm=max_norm,
+                       grad_scale=float(grad_scale) if factored else 1.0, guard=self.guard_state)
         ad.apply_to_shadow()                                                                  # 6. shadow_W = bf16(p_W + scale B A)
         self.dit.mark_shadow_fresh()                                                          # 7.
 

@@ -19,10 +19,11 @@ from __future__ import annotations
 
 import math
 import warnings
-from ctypes import byref
 from typing import Optional
 
 import torch
+
+from . import hip
 
 CHANNEL_CHOICES = (64, 128, 192, 256)        # what md_logvar_fwd / md_logvar_bwd accept: a multiple of 64, 64 <= C <= 256
 BETAS, EPS = (0.9, 0.999), 1e-8              # AdamW on w: no weight decay, no clipping
@@ -105,7 +106,6 @@ class LossWeighting:
     # -------------------------------------------------------------------------------------------- step path (HIP)
     def forward(self, cnoise: torch.Tensor) -> torch.Tensor:
         """md_logvar_fwd: inv [B] = exp(-u(cnoise)), the per-sample factor of md_edm_loss_train_weighted; u is kept for backward()."""
-        from . import hip
         B = cnoise.numel()
         u, inv = torch.empty(B, device=cnoise.device), torch.empty(B, device=cnoise.device)
         hip.check(hip.lib().md_logvar_fwd(cnoise.data_ptr(), self.freq.data_ptr(), self.phase.data_ptr(), self.w.data_ptr(), u.data_ptr(),
@@ -117,7 +117,6 @@ class LossWeighting:
                  accum_weight: float = 0.0) -> torch.Tensor:
         """md_logvar_bwd on the u of the last forward(): g += dw, self.objective = the weighted objective of this microbatch,
         obj_accum (1-element f32 tensor, optional) += accum_weight * objective.  Returns self.objective."""
-        from . import hip
         if self._u is None or self._u.numel() != cnoise.numel():
             raise RuntimeError("LossWeighting.backward() needs the forward() of the same microbatch first")
         hip.check(hip.lib().md_logvar_bwd(cnoise.data_ptr(), self.freq.data_ptr(), self.phase.data_ptr(), self._u.data_ptr(),
@@ -131,16 +130,9 @@ class LossWeighting:
         """One md_adamw_step launch over the C weights: no weight decay, no clipping, the accumulator zeroed.  `guard_state`: the
         optimiser's md_step_guard state -- the guarded launch leaves w and the moments untouched on a skipped step (the accumulator
         is still zeroed; step_count advances as FusedAdamW's does)."""
-        from . import hip
         self.step_count += 1
-        b1, b2 = BETAS
-        a = hip.AdamWArgs(self.w.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), None, None, None, None,
-                          self.channels, float(lr), b1, b2, EPS, 0.0, 1 - b1 ** self.step_count, 1 - b2 ** self.step_count, 0.0,
-                          float(grad_scale), 0.0, 1, 0)
-        if guard_state is not None:
-            hip.check(hip.lib().md_adamw_step_guarded(byref(a), guard_state.data_ptr(), hip.stream_ptr()), "md_adamw_step_guarded")
-        else:
-            hip.check(hip.lib().md_adamw_step(byref(a), hip.stream_ptr()), "md_adamw_step")
+        hip.adamw_step(self.w, self.g, self.m, self.v, self.channels, lr=float(lr), betas=BETAS, eps=EPS, weight_decay=0.0,
+                       step=self.step_count, grad_scale=float(grad_scale), guard=guard_state)
 
     # -------------------------------------------------------------------------------------------- host side
     def u_at(self, ln_sigmas) -> list:

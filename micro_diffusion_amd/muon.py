@@ -19,14 +19,16 @@ from __future__ import annotations
 
 import math
 import re
+import warnings
 from ctypes import byref, c_int32, c_int64
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
+from . import hip
 from .arch import ParamSpec
-from .trainer import FusedAdamW
+from .optim import FusedAdamW
 
 _BLOCK = r"^(patch_mixer|blocks)\.\d+\."
 # the hidden projections of every mixer and backbone block: the five attention projections, the dense SwiGLU and the 3-D expert tensors
@@ -137,8 +139,8 @@ class Muon(FusedAdamW):
         from .dit import flat_layout
         # every refusal comes before anything is allocated or changed
         check_hyper(momentum, nesterov, ns_steps, adjust, adamw_lr)
-        if getattr(dit, "_lora", None) is not None:
-            raise NotImplementedError("Muon on a DiT with a LoRA adapter attached: the adapter assumes a frozen base; fuse() / detach() it first")
+        self.dit = dit
+        self._refuse_adapter()
         self.targets = [str(t) for t in targets] if not isinstance(targets, str) else targets
         self.specs = resolve_targets(dit._table, self.targets)
         self._offs, self._total = flat_layout(dit._table)
@@ -153,26 +155,10 @@ class Muon(FusedAdamW):
         self._items_host = self._items_dev = self._ws = self._partials = self.norms = None
         self.ws_bytes = 0
         self.last_gemm_launches = 0
-        if self.device.type == "cuda":
-            super().__init__(dit, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, ema_smoothing=ema_smoothing, ema_start=ema_start,
-                             skip_nonfinite=skip_nonfinite, posthoc_sigma_rels=posthoc_sigma_rels)
-        else:                # state only: what state_dict() / load_state_dict() touch
-            from . import hip, posthoc_ema
-            self.dit = dit
-            self.lr, self.betas, self.eps, self.weight_decay = lr, tuple(betas), eps, weight_decay
-            self.m = torch.zeros(self._total, dtype=torch.float32, device=self.device)
-            self.v = torch.zeros_like(self.m)
-            self.step_count = 0
-            self.ema_smoothing, self.ema_start = ema_smoothing, int(ema_start)
-            self.ema = torch.zeros_like(self.m) if ema_smoothing is not None else None
-            self.ema_live = False
-            self.last_grad_scale = 1.0
-            self.skip_nonfinite, self.guard_state = bool(skip_nonfinite), None
-            self.posthoc_sigma_rels = tuple(float(s) for s in (posthoc_sigma_rels or ()))
-            if len(self.posthoc_sigma_rels) > hip.EMA_MAX_PROFILES:
-                raise ValueError(f"at most {hip.EMA_MAX_PROFILES} post-hoc EMA profiles (MD_EMA_MAX_PROFILES), got {len(self.posthoc_sigma_rels)}")
-            self.posthoc_gammas = tuple(posthoc_ema.sigma_rel_to_gamma(s) for s in self.posthoc_sigma_rels)
-            self.posthoc = [torch.zeros_like(self.m) for _ in self.posthoc_sigma_rels]
+        # device="cpu": the state only -- what state_dict() / load_state_dict() touch
+        super().__init__(dit, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, ema_smoothing=ema_smoothing, ema_start=ema_start,
+                         skip_nonfinite=skip_nonfinite, posthoc_sigma_rels=posthoc_sigma_rels,
+                         device=None if self.device.type == "cuda" else self.device)
 
     # -------------------------------------------------------------------------------------------- the item table
     def item_scale(self, rows: int, cols: int) -> float:
@@ -181,7 +167,6 @@ class Muon(FusedAdamW):
 
     def _items(self):
         """(host array, device tensor, n): built on first use; md_muon_ws_bytes checks the shapes and writes the workspace offsets."""
-        from . import hip
         if self._items_host is None:
             rows = self.matrices
             arr = (hip.MuonItem * len(rows))(*[hip.MuonItem(o, r, c, 0, self.item_scale(r, c), 0) for o, r, c, _ in rows])
@@ -202,24 +187,15 @@ class Muon(FusedAdamW):
 
     def step(self, lr: Optional[float] = None, max_norm: float = 0.0, grad_scale: float = 1.0, g_bf16: Optional[torch.Tensor] = None,
              norm_partials: int = 0) -> None:
-        from . import hip
         self._refuse_adapter()
         if self.device.type != "cuda":
             raise RuntimeError("muon: step() needs the optimiser on the GPU (HIP kernels; there is no CPU fallback)")
         f = self.dit.flat_buffers()
-        L, st = hip.lib(), torch.cuda.current_stream().cuda_stream
+        L, st = hip.lib(), hip.stream_ptr()
         host, dev, n = self._items()
         ema_mode = self._begin_step(grad_scale)
-        ss = None
-        if (max_norm and max_norm > 0) or self.skip_nonfinite:           # the whole gradient, exactly as FusedAdamW.step
-            if norm_partials <= 0:
-                src = g_bf16 if g_bf16 is not None else f["g"]
-                hip.check(L.md_sumsq(src.data_ptr(), 1 if g_bf16 is not None else 0, f["total"], self.partials.data_ptr(), st), "md_sumsq")
-                norm_partials = hip.SUMSQ_PARTIALS
-            hip.check(L.md_sumsq_finish(self.partials.data_ptr(), norm_partials, self.sumsq.data_ptr(), st), "md_sumsq_finish")
-            ss = self.sumsq.data_ptr()
-            if self.skip_nonfinite:
-                self._guard(st)
+        ss = self._norm_and_guard(max_norm, src=g_bf16 if g_bf16 is not None else f["g"], src_is_bf16=g_bf16 is not None, n=f["total"],
+                                  have=norm_partials)                    # the whole gradient, as FusedAdamW.step
         lr_muon = self.lr if lr is None else lr
         lr_adamw = lr_muon if self.adamw_lr is None else (self.adamw_lr * (lr_muon / self.lr) if self.lr else 0.0)
         guard = self.guard_state.data_ptr() if self.skip_nonfinite else None
@@ -246,10 +222,6 @@ class Muon(FusedAdamW):
                                   "Newton-Schulz is a follow-up); use dp_mode='allreduce'")
 
     # -------------------------------------------------------------------------------------------- state
-    def _by_name(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return {s.name: flat[self._offs[s.name]:self._offs[s.name] + int(np.prod(s.shape))].view(s.shape)
-                for s in self.dit._table if not s.buffer}
-
     def hyper(self) -> dict:
         return {"momentum": self.momentum, "nesterov": self.nesterov, "ns_steps": self.ns_steps, "adjust": self.adjust,
                 "ns_coeffs": list(self.ns_coeffs)}
@@ -272,6 +244,5 @@ class Muon(FusedAdamW):
         mine = self.hyper()
         other = {k: mu.get(k) for k in mine}
         if other != mine:
-            import warnings
             warnings.warn(f"muon: the checkpoint was written with {other}, this run uses {mine}: the momentum continues under the new values")
         super().load_state_dict(sd)

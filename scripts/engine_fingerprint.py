@@ -9,6 +9,12 @@ caption length 77, tiny / mask 0, micro / mask 0.5 / caption length 20, each onc
 arenas (two microbatches: the first one measures the arena, the second runs in it); and one Trainer.train_step of a single microbatch
 on a one-rank sharded bf16 exchange, so that the weight gradients take the bf16 store path (DiTEngine.wgrad_bf16).
 
+`--cases step` (profiles/step_fingerprint_*.json) fingerprints the training step instead: three Trainer.train_steps of two microbatches
+each on tiny / mask 0.75 / batch 4 under FusedAdamW (EMA, post-hoc EMA, step guard, clipping), the same on the one-rank sharded bf16
+exchange followed by consolidate(), Muon, LoRAAdamW projected and factored, and FusedAdamW with the learned loss weighting.  There the
+recorder also stands in for hip._lib, so the optimisers' own launches are traced; the hashes are the loss of every step, the masters,
+the bf16 shadow, both moments, the EMA, every post-hoc profile and the adapter's / loss weighting's weights.
+
 Per case the file holds
   trace   the ordered list of every call made through `eng.L` (a recording proxy stands in for it): symbol, return code, the integer
           and float arguments, for byref structs their non-pointer fields in order, trailing zeros dropped (pointer fields as p = set / 0 = null), for
@@ -65,8 +71,17 @@ def _struct(s):
     return rec
 
 
+def _array(a):
+    """A host table the optimisers pass (range tables, EMA pointers and betas, Muon / LoRA items): its elements in order."""
+    if issubclass(a._type_, ctypes.Structure):
+        return [_struct(e) for e in a]
+    if a._type_ is ctypes.c_void_p:
+        return "".join("p" if e else "0" for e in a)
+    return [_scalar(e) for e in a]
+
+
 class Recorder:
-    """Stands in for DiTEngine.L: records every call, then makes it."""
+    """Stands in for DiTEngine.L (and, in the step cases, for hip._lib): records every call, then makes it."""
 
     def __init__(self, lib, log):
         self._lib, self._log = lib, log
@@ -75,7 +90,8 @@ class Recorder:
         fn = getattr(self._lib, name)
 
         def call(*args):
-            entry = [name, None] + [_struct(a._obj) if isinstance(a, _BYREF) else _scalar(a) for a in args]
+            entry = [name, None] + [_struct(a._obj) if isinstance(a, _BYREF) else _array(a) if isinstance(a, ctypes.Array) else _scalar(a)
+                                    for a in args]
             rc = fn(*args)
             entry[1] = rc
             self._log.append(json.dumps(entry, separators=(",", ":")))
@@ -150,7 +166,79 @@ def _trainer_case():
         dist.destroy_process_group()
 
 
-def run(out_path, digest_path=None):
+STEP_CASES = ("adamw", "adamw_sharded", "muon", "lora_projected", "lora_factored", "adamw_loss_weighting")
+
+
+def _step_case(kind):
+    """Three Trainer.train_steps of two microbatches each (tiny, batch 4) under one optimiser; the recorder also stands in for
+    hip._lib, so the optimiser's own launches are in the trace.  Hashes: the loss of every step and the state the steps leave."""
+    import torch
+    import torch.distributed as dist
+    from oracle import microdit_ref as orc
+    from micro_diffusion_amd import hip
+    from micro_diffusion_amd.trainer import FusedAdamW, LRSchedule, Trainer
+    sharded = kind == "adamw_sharded"
+    if sharded:
+        with socket.socket() as s:
+            s.bind(("127.0.0.1", 0))
+            port = s.getsockname()[1]
+        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+        torch.cuda.set_device(0)
+        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    real = hip.lib()
+    try:
+        cfg = orc.tiny_config()
+        sd = orc.dezero_state_dict(orc.synth_state_dict(cfg, 81))
+        batch, rnd, epsn, mnoise = orc.synth_batch(cfg, 4, 82)
+        m = _model(cfg, sd, 0.75)
+        # one fixed draw per microbatch of two samples (the same in every step)
+        m._noise_fn = lambda b: (rnd.cuda()[:2], epsn.cuda()[:2], mnoise.cuda()[:2])
+        adamw = dict(lr=2.4e-4, ema_smoothing=0.999, ema_start=1, skip_nonfinite=True, posthoc_sigma_rels=(0.05, 0.1))
+        adapter = lw = None
+        if kind == "muon":
+            from micro_diffusion_amd.muon import Muon
+            opt = Muon(m.dit, **adamw)
+        elif kind.startswith("lora"):
+            from micro_diffusion_amd import lora
+            adapter = lora.LoRA(m.dit, rank=8, alpha=4, seed=5, backward=kind[5:])
+            opt = lora.LoRAAdamW(adapter, lr=1e-3, skip_nonfinite=True)
+        else:
+            opt = FusedAdamW(m.dit, **adamw)
+        kw = dict(exchange="bf16", single_rank_exchange=True, dp_mode="sharded") if sharded else {}
+        if kind == "adamw_loss_weighting":
+            from micro_diffusion_amd.loss_weighting import LossWeighting
+            lw = kw["loss_weighting"] = LossWeighting(channels=64, seed=3)
+        tr = Trainer(m, opt, LRSchedule("constant", alpha=1.0), clip_norm=0.25, microbatch_size=2, **kw)
+        log = []
+        rec = hip._lib = m.dit.engine.L = Recorder(real, log)
+        gb = {k: t.cuda() for k, t in batch.items()}
+        sha = {}
+        for i in range(3):
+            sha[f"loss{i}"] = _sha(tr.train_step(gb))
+        if sharded:
+            tr.consolidate()
+            tr.sync.wait_gather()
+        torch.cuda.synchronize()
+        assert rec is hip._lib
+        f = m.dit.flat_buffers()
+        sha.update(p=_sha(f["p"]), s=_sha(f["s"]), m=_sha(opt.m), v=_sha(opt.v))
+        if getattr(opt, "ema", None) is not None:
+            sha["ema"] = _sha(opt.ema)
+        for k, e in enumerate(getattr(opt, "posthoc", None) or ()):
+            sha[f"posthoc{k}"] = _sha(e)
+        if adapter is not None:
+            sha["adapter_w"] = _sha(adapter.w)
+        if lw is not None:
+            sha["lw_w"] = _sha(lw.w)
+        sha["skipped"] = str(opt.skipped_steps())
+        return log, sha
+    finally:
+        hip._lib = real
+        if sharded:
+            dist.destroy_process_group()
+
+
+def run(out_path, digest_path=None, which="engine"):
     from oracle import microdit_ref as orc
     from micro_diffusion_amd import hip
     specs = [("tiny_mask75", orc.tiny_config, 61, 0.75, -0.6, 1.2, 77), ("tiny_mask0", orc.tiny_config, 62, 0.0, -0.6, 1.2, 77),
@@ -167,10 +255,14 @@ def run(out_path, digest_path=None):
         cases[name] = {"trace": trace, "sha256": sha}
         print(f"{name}: {len(trace)} calls", flush=True)
 
-    for name, *spec in specs:
-        for arena in (False, True):
-            keep(name + ("+arena" if arena else ""), *_microbatch_case(*spec, arena))
-    keep("trainer_one_microbatch", *_trainer_case())
+    if which == "step":
+        for kind in STEP_CASES:
+            keep("step_" + kind, *_step_case(kind))
+    else:
+        for name, *spec in specs:
+            for arena in (False, True):
+                keep(name + ("+arena" if arena else ""), *_microbatch_case(*spec, arena))
+        keep("trainer_one_microbatch", *_trainer_case())
     doc = {"library_source_hash": hip._source_hash(), "calls": calls, "cases": cases}
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:
@@ -246,5 +338,7 @@ if __name__ == "__main__":
     ap.add_argument("--out", default="engine_fingerprint.json", help="the full fingerprint: every call with its arguments")
     ap.add_argument("--digest-out", default=None, help="also write the small form (see digest())")
     ap.add_argument("--compare", nargs=2, metavar=("A.json", "B.json"), help="full files or digests; prints the first difference")
+    ap.add_argument("--cases", choices=("engine", "step"), default="engine",
+                    help="engine: the microbatch cases above; step: three optimiser steps under every optimiser (profiles/step_fingerprint_*.json)")
     args = ap.parse_args()
-    sys.exit(compare(*args.compare) if args.compare else run(args.out, args.digest_out))
+    sys.exit(compare(*args.compare) if args.compare else run(args.out, args.digest_out, args.cases))

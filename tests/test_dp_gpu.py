@@ -260,6 +260,68 @@ def test_one_microbatch_step_stores_bf16_gradients(hip):
     assert abs(a["loss2"] - b["loss2"]) <= 2e-3 * abs(a["loss2"])
 
 
+def _failed_step_main(port, out_path):
+    """One rank over RCCL, sharded bf16 exchange, deterministic mode.  Trainer A: a one-microbatch step whose train_microbatch raises
+    (a plain Python exception in front of every launch), then a two-microbatch step; trainer B: only that two-microbatch step."""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0",
+                      MD_DETERMINISTIC="1")            # before the package is imported: the engine reads it when it is built
+    torch.cuda.set_device(0)
+    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    try:
+        from micro_diffusion_amd.trainer import Trainer
+        res = {}
+        for which in ("A", "B"):
+            model, opt, tr, part = _build((0, BATCH), "bf16", BATCH)
+            tr = Trainer(model, opt, tr.schedule, clip_norm=0.25, microbatch_size=BATCH, exchange="bf16", single_rank_exchange=True,
+                         dp_mode="sharded")
+            assert model.dit.engine.deterministic is True and tr.sharded and tr.sync.store_bf16
+            if which == "A":
+                def boom(*a, **k):
+                    raise RuntimeError("train_microbatch failed before its first launch")
+                model.train_microbatch = boom          # an instance attribute in front of the method
+                raised = False
+                try:
+                    tr.train_step(part)
+                except RuntimeError as e:
+                    raised = "before its first launch" in str(e)
+                eng = model.dit.engine
+                res["disarmed"] = {"raised": raised, "wgrad_bf16": eng.wgrad_bf16 is None, "route_stats": eng.route_stats is None,
+                                   "active": tr.sync.active is False}
+                del model.train_microbatch
+            tr.microbatch_size = BATCH // 2
+            loss = tr.train_step(part)
+            tr.sync.wait_gather()
+            torch.cuda.synchronize()
+            f = model.dit.flat_buffers()
+            res[which] = {"p": f["p"].detach().cpu(), "m": opt.m.detach().cpu(), "v": opt.v.detach().cpu(), "loss": loss.detach().cpu(),
+                          "stored": tr.sync.last_stored}
+            del model, opt, tr
+            torch.cuda.empty_cache()
+        torch.save(res, out_path)
+    finally:
+        dist.destroy_process_group()
+
+
+def test_failed_one_microbatch_step_leaves_nothing_armed(hip):
+    """A train_step that raises inside its only microbatch must leave DiTEngine.wgrad_bf16, DiTEngine.route_stats and GradSync.active
+    disarmed.  Otherwise the next multi-microbatch step stores the weight gradients of every microbatch but the last as bf16 into
+    the exchange buffer, where the last microbatch's staging cast overwrites them: they never reach the fp32 accumulators.  The step
+    after the failure must therefore be bit-identical to the same step on a fresh trainer."""
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "r.pt")
+        ctx = mp.get_context("spawn")
+        proc = ctx.Process(target=_failed_step_main, args=(_free_port(), out))
+        proc.start()
+        proc.join(600)
+        assert proc.exitcode == 0, f"process failed: {proc.exitcode}"
+        r = torch.load(out)
+    a, b = r["A"], r["B"]
+    differ = [k for k in ("loss", "p", "m", "v") if not torch.equal(a[k], b[k])]
+    assert r["disarmed"] == {"raised": True, "wgrad_bf16": True, "route_stats": True, "active": True}, (r["disarmed"], differ)
+    assert not differ, f"{differ} after the failed step differ from a fresh trainer's: gradients of microbatch 0 were lost"
+    assert a["stored"] == 0 and b["stored"] == 0, "a two-microbatch step stores no weight gradient as bf16"
+
+
 def _comm_direct_main(port, out_path):
     """libmicrodit_comm.so by itself on a one-rank communicator: every collective is the identity, what is checked is the stream
     contract -- a collective runs behind the kernels already enqueued on the caller's stream, the caller's later kernels run
