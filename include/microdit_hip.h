@@ -877,6 +877,23 @@ int md_muon_apply(float* p, void* shadow, float* ema, const md_muon_item* items,
                   float weight_decay, int32_t ema_mode, float ema_smoothing, const int32_t* guard, const void* ws, hipStream_t stream);
 int md_muon_axpby(const void* x, const float* y, void* out, float a, float b, int64_t n, hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------- cross-attention probe */
+/* (symbol added, MD_ABI_VERSION stays 6.)  Observes the cross-attention of a DiT block (utils.py:122-132), whose fused
+ * form md_attn_fwd, like the reference's F.scaled_dot_product_attention, never materialises its probabilities.
+ *
+ * out[row, j] += (1/H) * sum_h softmax_j(scale * q_h(b,q) . k_h(b,j)),  j < Skv;  row = out_rows ? out_rows[b*Sq+q] : b*Sq+q
+ * Reads a->q, a->k, B, H, Sq, Skv, ldq, ldk, sq, sk, hsq, hsk, scale, hd (both packed and head-major addressing, as md_attn_fwd);
+ * ignores every other field.  out f32, row pitch ldo >= Skv floats, ldo % 4 == 0, 16-byte aligned.
+ *
+ * hd in {32, 64}, 1 <= Skv <= 128 (the 77 caption tokens; self-attention maps are out of scope), any Sq, B, H >= 1; q and k 16-byte
+ * aligned with ldq, ldk, sq, sk, hsq, hsk multiples of 8 elements.  Anything else, a NULL q / k / out or a bad ldo: MD_BAD_ARG, nothing
+ * launched.  The softmax takes its own row maximum and sum in fp32 (lse is not read): s = acc * scale, p = exp2((s - max) * log2 e),
+ * P = p * rcp(sum).  Heads are added in ascending order in fp32, the sum is multiplied once by 1.0f / H and added to out; every output
+ * element has one writer and there are no atomics: same binary and same arguments give the same bits.  Columns [Skv, ldo) of a row and
+ * rows the launch does not name are not written; nothing is read past row Sq - 1 of q or row Skv - 1 of k of any sample.  out_rows holds
+ * global row indices (md_get_mask's keep_rows, what md_gather_rows consumes). */
+int md_attn_probs(const md_attn_args* a, float* out, int64_t ldo, const int32_t* out_rows, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -288,6 +288,10 @@ class DiTEngine:
         # marginals to its row right behind md_moe_route (one md_moe_route_stats call).  None: no launch, no buffer.  Its tables and
         # workspace are its own allocations: arena sizes, addresses and the tape are those of an unarmed pass.
         self.route_stats = None
+        # Cross-attention maps (opt-in): an attn_maps.AttentionMaps; right behind every cross-attention it recomputes the
+        # head-averaged probabilities from the q / k attention just read (one md_attn_probs launch into its own fp32 buffer, no host
+        # wait).  None: no launch, no buffer; arena sizes, addresses and the tape are those of an unarmed pass either way.
+        self.attn_probe = None
         # Masked-expert pruning: the masking right behind the last patch-mixer block keeps Tk of T tokens, so when that block
         # is MoE its expert MLPs (forward, both data gradients, both weight gradients) run only on the routed rows whose token survives --
         # about (1 - mask_ratio) of them.  Routing stays dense and the tape's probs / rowidx / gval / slot are those of the dense pass.
@@ -825,11 +829,13 @@ class DiTEngine:
         self._qkln_fwd(kv.data_ptr(), Mc, 2 * hx, 0, hx, rk.data_ptr())
         return rk, None
 
-    def _block_fwd(self, bp: BlockPlan, x, ycond, B, S, Lc, gc, mod_all=None, kv=None, keep=None):
+    def _block_fwd(self, bp: BlockPlan, x, ycond, B, S, Lc, gc, mod_all=None, kv=None, keep=None, out_rows=None):
         """kv: this block's entry of Conditioning.kv -- the caption-side projection and its K-LayerNorm are then skipped (ycond is not
         read; inference only: the tape holds no K rstd for a backward).
         keep: (ids_restore [B, S] int32, Tk) when only the tokens with ids_restore < Tk of this block's output are ever read (the
-        last patch-mixer block under masking): a MoE block then runs its experts on the routed rows of those tokens alone."""
+        last patch-mixer block under masking): a MoE block then runs its experts on the routed rows of those tokens alone.
+        out_rows: tp.keep_rows when this block's S rows are the kept tokens of a masked pass (backbone blocks), else None: the row of the
+        full token grid each of its rows stands for, which only attn_probe reads."""
         cfg = self.cfg
         d, h, hx, f = bp.dim, bp.attn_hidden, bp.xattn_hidden, bp.ffn_hidden
         M, Mc, D = B * S, B * Lc, cfg.dim
@@ -886,6 +892,8 @@ class DiTEngine:
             ax = self.attn_args(t.q2.data_ptr(), t.kv.data_ptr(), t.kv.data_ptr() + 2 * hx, t.o2, t.lse2, B, bp.xheads, S, Lc,
                                 hx, 2 * hx, 2 * hx, hx)
         self._attn_fwd(ax)
+        if self.attn_probe is not None:
+            self.attn_probe.record(n, ax, B, S, Lc, out_rows)
         x2 = self.empty(M, d)
         self.lin_fwd(t.o2, n + ".cross_attn.proj", x2, M, d, hx, mode=hip.EPI_RESIDUAL, res=x1)
         t.x2 = x2
@@ -1510,7 +1518,8 @@ class DiTEngine:
             if i == lo:
                 x_lo = x
             seg(bp.name)
-            x, bt = self._block_fwd(bp, x, y2, B, Tk, Lc, gc, mod_all, kv=cond.kv[bp.name] if cond is not None else None)
+            x, bt = self._block_fwd(bp, x, y2, B, Tk, Lc, gc, mod_all, kv=cond.kv[bp.name] if cond is not None else None,
+                                    out_rows=tp.keep_rows)
             if self._record:
                 tp.blocks.append(bt)
             if self._disperse_on and i == self.disperse[0] and B > 1:       # B = 1: L = 0 and the gradient is 0 -- nothing to launch

@@ -323,6 +323,9 @@ _sig("md_muon_momentum", P, P, P, P, P, I32, F32, I32, F32, P, F32, I32, P, P, P
 _sig("md_muon_newton_schulz", P, I32, I32, F32, F32, F32, P, P, P)
 _sig("md_muon_apply", P, P, P, P, P, I32, F32, F32, I32, F32, P, P, P)
 _sig("md_muon_axpby", P, P, P, F32, F32, I64, P)
+# cross-attention probe (attn_maps.py): head-averaged probabilities of a short key set added into fp32 rows
+_sig("md_attn_probs", POINTER(AttnArgs), P, I64, P, P)
+ATTN_PROBS_MAX_KEYS = 128       # Skv of md_attn_probs
 MUON_NORM_PARTS = 16            # MD_MUON_NORM_PARTS
 STEP_DELTA_MAX_BLOCKS = 2048    # MD_STEP_DELTA_MAX_BLOCKS
 STEP_PROBE_CHUNKS = 1024        # MD_STEP_PROBE_CHUNKS

@@ -265,7 +265,7 @@ class LatentDiffusion(nn.Module):
                          guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
                          guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
                          apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, step_cache=None,
-                         **kwargs):
+                         attn_maps=None, **kwargs):
         """EDM sampler, fp64 state (model.py:231-297): x is unit noise, y the caption embeddings, **kwargs extra forward arguments.
         The docstring of sampling.py defines every argument; sampling.tensor_op_loop (fused=False) is the definition of the loop and
         sampling.FusedRun the same loop in fused HIP kernels.  Every random draw of a run reads self.randn_like when it is made."""
@@ -273,7 +273,8 @@ class LatentDiffusion(nn.Module):
                                init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, resample=resample,
                                guidance_mode=guidance_mode, guidance_rescale=guidance_rescale, apg_eta=apg_eta,
                                apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, measurement=measurement,
-                               measurement_scale=measurement_scale, guidance_loss=guidance_loss, step_cache=step_cache)
+                               measurement_scale=measurement_scale, guidance_loss=guidance_loss, step_cache=step_cache,
+                               attn_maps=attn_maps)
         return sampling.sample(self, x, y, steps, cfg, fused, cond_cache, req, kwargs)
 
     @torch.no_grad()
@@ -282,7 +283,8 @@ class LatentDiffusion(nn.Module):
                  cond_cache: Optional[bool] = None, sampler: str = "heun", guidance_interval=None, guide=None,
                  guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
                  guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
-                 apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, step_cache=None, **kwargs):
+                 apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, step_cache=None,
+                 attn_maps=None, **kwargs):
         """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache, sampler,
         guidance_interval, guide and guide_captions: as in edm_sampler_loop (with a guide, guidance_scale is the autoguidance weight).
         init_latents, strength, inpaint_mask and resample: image-to-image and inpainting as in edm_sampler_loop; the seeded draw below is
@@ -292,12 +294,15 @@ class LatentDiffusion(nn.Module):
         edm_sampler_loop; they tame the over-saturation of plain guidance at this default guidance_scale.
         measurement, measurement_scale and guidance_loss: measurement-guided sampling as in edm_sampler_loop (the measurement lives in the
         sampler's latent space, like init_latents).
-        step_cache: a step_cache.StepCache, as in edm_sampler_loop."""
+        step_cache: a step_cache.StepCache, as in edm_sampler_loop.
+        attn_maps: an attn_maps.AttentionMaps that records the cross-attention maps of the run, as in edm_sampler_loop (DESIGN.md 4.21);
+        mapping words to caption positions is the caller's (the tokenizer is third-party)."""
         req = sampling.Request(sampler=sampler, guidance_interval=guidance_interval, guide=guide, guide_captions=guide_captions,
                                init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, resample=resample,
                                guidance_mode=guidance_mode, guidance_rescale=guidance_rescale, apg_eta=apg_eta,
                                apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, measurement=measurement,
-                               measurement_scale=measurement_scale, guidance_loss=guidance_loss, step_cache=step_cache)
+                               measurement_scale=measurement_scale, guidance_loss=guidance_loss, step_cache=step_cache,
+                               attn_maps=attn_maps)
         req.check(self, None, guidance_scale)       # refuse before tokenising; edm_sampler_loop checks again with the state's shape
         assert prompt or tokenized_prompts is not None, "Must provide either prompt or tokenized prompts"
         device = next(self.dit.parameters()).device

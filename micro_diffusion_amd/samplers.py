@@ -288,6 +288,22 @@ def check_step_cache(step_cache=None, guide=None, measurement=None, guidance_los
     return True
 
 
+def check_attn_maps(attn_maps=None, config=None) -> bool:
+    """Refuse, before anything is tokenised, launched or allocated, an attention-map request the sampler cannot run; True
+    when the run records.  ValueError for an object that is not an attn_maps.AttentionMaps (anything without its resolve / start_run /
+    begin_evaluation / record) and, with the model's DiTConfig given, for a block selection that matches none of its blocks.  Nothing
+    else is refused: the recorder only reads, so it composes with every other option."""
+    if attn_maps is None:
+        return False
+    for name in ("resolve", "start_run", "begin_evaluation", "skip_evaluation", "record"):
+        if not callable(getattr(attn_maps, name, None)):
+            raise ValueError(f"attn_maps must be an attn_maps.AttentionMaps, got {type(attn_maps).__name__}")
+    if config is not None:
+        from .attn_maps import block_names, select_blocks
+        select_blocks(block_names(config), attn_maps.blocks)
+    return True
+
+
 def evaluation_sigmas(sampler: str, t_steps: Sequence[float]) -> List[float]:
     """The noise level of every network evaluation of a run without churn, in order."""
     out = []

@@ -55,6 +55,12 @@ last are always full, and so is the first at another network batch (the edge of 
 and composes with the solvers, churn, guidance_interval, the guidance modes, cond_cache and init_latents / inpaint_mask /
 resample; not defined with `guide`, `measurement` or `guidance_loss` (ValueError).  step_cache.stats describes the run.  None:
 the launches and bits of a run without the argument.
+`attn_maps`: an attn_maps.AttentionMaps.  It is armed on the main network's engine for the run (and disarmed when the
+run ends, an error included); both loops tell it the noise level and the batch B before every evaluation of the main network, and
+behind every selected block's cross-attention one md_attn_probs launch adds the head-averaged probabilities of the first B samples (the
+conditional half of a doubled batch) to its buffer.  A `guide` network is not recorded.  It only reads: it composes with every argument
+above, both loops included, and the latents are the bits of the run without it.  None: the launches and bits of a run without the
+argument.
 """
 from __future__ import annotations
 
@@ -91,6 +97,22 @@ def frozen_network(dit):
             p.requires_grad_(r)
 
 
+@contextmanager
+def recording(dit, attn_maps, x):
+    """Context of a run with attn_maps=: the recorder is armed on the main network's engine inside -- resolved against
+    the model, the token grid of the state x, sums and counts cleared -- and the engine is disarmed afterwards, whatever ended the run.
+    None: nothing."""
+    if attn_maps is None:
+        yield
+        return
+    engine, p = dit.engine, dit.patch_size
+    attn_maps.arm(engine, (x.shape[-2] // p, x.shape[-1] // p))
+    try:
+        yield
+    finally:
+        attn_maps.disarm(engine)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The request: the options of one run, checked once
 # ---------------------------------------------------------------------------------------------------------------------
@@ -114,6 +136,7 @@ class Request:
     measurement_scale: float = 1.0
     guidance_loss: Any = None
     step_cache: Any = None
+    attn_maps: Any = None
 
     def check(self, model, shape, cfg, extra=()):
         """Refuse, before anything is tokenised, launched, allocated or drawn, a request that is not defined (the samplers.check_*
@@ -139,6 +162,8 @@ class Request:
             gmode = (self.guidance_mode, float(self.guidance_rescale), float(self.apg_eta), None if r is None else float(r),
                      float(self.apg_momentum))
         samplers.check_edit(self.sampler, self.init_latents is not None, self.strength, self.inpaint_mask is not None, self.resample)
+        if self.attn_maps is not None:
+            samplers.check_attn_maps(self.attn_maps, model.dit.config)
         return caching, guided_by, interval, gmode
 
 
@@ -215,11 +240,14 @@ def sampler_plan(ec, steps: Optional[int], sampler: str, strength: float = 1.0, 
 # ---------------------------------------------------------------------------------------------------------------------
 # The tensor-op loop: the definition
 # ---------------------------------------------------------------------------------------------------------------------
-def autoguided_forward(model, guide, y_guide, w: float):
+def autoguided_forward(model, guide, y_guide, w: float, attn_maps=None):
     """The forward function of an autoguided evaluation for model_forward_wrapper: both networks on the same input at batch B, the
-    guide with its own captions, combined in fp32 as the update kernels do (F = F_guide + w * (F_main - F_guide))."""
+    guide with its own captions, combined in fp32 as the update kernels do (F = F_guide + w * (F_main - F_guide)).  attn_maps: the
+    run's recorder, told that the guide's forward is not the main network's (the guide may share the engine)."""
     def fwd(x, t, y, **kwargs):
         fm = model.dit.forward_without_cfg(x, t, y, **kwargs)["sample"].to(torch.float32)
+        if attn_maps is not None:
+            attn_maps.skip_evaluation()
         fg = guide.forward_without_cfg(x, t, y_guide, **kwargs)["sample"].to(torch.float32)
         return {"sample": fg + w * (fm - fg)}
     return fwd
@@ -228,13 +256,14 @@ def autoguided_forward(model, guide, y_guide, w: float):
 class TensorOpNetwork:
     """The network evaluations of the tensor-op loop: denoise(xs, sigma) -> the denoised prediction in fp64, in three forms."""
 
-    def __init__(self, model, y, cfg: float, interval, guide, guide_null: bool, gmode, kwargs):
+    def __init__(self, model, y, cfg: float, interval, guide, guide_null: bool, gmode, kwargs, attn_maps=None):
         self.model, self.y, self.cfg, self.interval, self.guide, self.gmode, self.kwargs = model, y, cfg, interval, guide, gmode, kwargs
+        self.attn_maps = attn_maps
         dit = model.dit
         if cfg <= 1.0:
             self.guided_forward = dit.forward
         elif guide is not None:
-            self.guided_forward = autoguided_forward(model, guide, torch.zeros_like(y) if guide_null else y, cfg)
+            self.guided_forward = autoguided_forward(model, guide, torch.zeros_like(y) if guide_null else y, cfg, attn_maps)
         else:
             self.guided_forward = partial(dit.forward, cfg=cfg)
         if gmode is not None:
@@ -247,7 +276,13 @@ class TensorOpNetwork:
     def forward_at(self, sigma):
         return self.guided_forward if self.inside(sigma) else self.model.dit.forward
 
+    def announce(self, xs, sigma):
+        """Tell the attention-map recorder (if any) the noise level and the batch of the main network's next evaluation."""
+        if self.attn_maps is not None:
+            self.attn_maps.begin_evaluation(sigma, xs.shape[0])
+
     def denoise(self, xs, sigma):
+        self.announce(xs, sigma)
         return self.model.model_forward_wrapper(xs.to(torch.float32), sigma.to(torch.float32), self.y, self.forward_at(sigma), mask_ratio=0,
                                                 **self.kwargs)["sample"].to(torch.float64)
 
@@ -258,6 +293,7 @@ class TensorOpNetwork:
         Outside the interval the unguided evaluation runs and M stays."""
         if not self.inside(sigma):
             return self.denoise(xs, sigma)
+        self.announce(xs, sigma)
         mode, phi, eta, r, beta = self.gmode
         dit, guide, y, kwargs, sd = self.model.dit, self.guide, self.y, self.kwargs, self.model.edm_config.sigma_data
         xs, sigma = xs.to(torch.float32), sigma.to(torch.float32).reshape(-1, 1, 1, 1)
@@ -269,6 +305,8 @@ class TensorOpNetwork:
             F_c, F_u = torch.split(F.to(torch.float32), len(F) // 2, dim=0)
         else:
             F_c = dit.forward_without_cfg(net_in, c_noise, y, mask_ratio=0, **kwargs)["sample"].to(torch.float32)
+            if self.attn_maps is not None:
+                self.attn_maps.skip_evaluation()
             F_u = guide.forward_without_cfg(net_in, c_noise, self.y_u, mask_ratio=0, **kwargs)["sample"].to(torch.float32)
         D_c = (c_skip * xs + c_out * F_c).to(torch.float64)
         M = c_out.to(torch.float64) * (F_c.to(torch.float64) - F_u.to(torch.float64))
@@ -282,6 +320,7 @@ class TensorOpNetwork:
         """(D, correction) of a measurement-guided step's first evaluation: model_forward_wrapper under
         torch.enable_grad() on the fp32 xs, torch.autograd.grad of L.sum() gives g = dL/dxs through the (frozen) network, and the
         correction zeta / max(sqrt(L_b), GUIDE_TINY) * g, to subtract from the solver's result, is formed in fp64."""
+        self.announce(xs, sigma)
         with torch.enable_grad():
             x32 = xs.to(torch.float32).detach().requires_grad_(True)
             D = self.model.model_forward_wrapper(x32, sigma.to(torch.float32), self.y, self.forward_at(sigma), mask_ratio=0)["sample"]
@@ -369,8 +408,9 @@ class FusedRun:
     The constructor allocates the run's buffers (and writes the image-to-image start); run() steps."""
 
     def __init__(self, model, x, y, plan: Plan, cfg: float, cond_cache: bool = False, interval=None, guide=None, guide_null: bool = False,
-                 edit=None, gmode=None, guidance=None, step_cache=None):
+                 edit=None, gmode=None, guidance=None, step_cache=None, attn_maps=None):
         self.model, self.dit, self.guide, self.plan, self.step_cache = model, model.dit, guide, plan, step_cache
+        self.attn_maps = attn_maps
         self.L, self.st, self.sd = hip.lib(), torch.cuda.current_stream().cuda_stream, model.edm_config.sigma_data
         self.x, self.y, self.cfg, self.interval, self.cond_cache = x, y, cfg, interval, cond_cache
         self.guided = any(samplers.is_guided(s, cfg, interval) for s in plan.sigmas)        # no guided evaluation at all: the cfg = 1 run
@@ -436,6 +476,8 @@ class FusedRun:
         with cond_cache, else the fp32 image; leading-row views when the evaluation runs at batch B of a doubled run --, the c_noise
         tensor, the evaluation's network batch)."""
         B, L, x = self.B, self.L, self.x
+        if self.attn_maps is not None:              # every evaluation of the main network passes here first
+            self.attn_maps.begin_evaluation(sigma, B)
         c_noise = float(np.log(np.float32(sigma)) / 4)
         Be = 2 * B if dup else B
         if self.cond_cache:
@@ -459,9 +501,13 @@ class FusedRun:
         run_guide = self.auto and g_eval
         if self.cond_cache:
             F = self.dit._engine.forward(None, t, None, cond=self.cond.narrow(Be), patches=inp, **sc_args).out_tok
+            if run_guide and self.attn_maps is not None:
+                self.attn_maps.skip_evaluation()
             Fg = self.guide._engine.forward(None, t, None, cond=self.cond_g, patches=inp).out_tok if run_guide else None
             return F, dup, Fg
         F = self.dit.forward_without_cfg(inp, t, self.y2 if Be == self.Bn else self.y, 0, **sc_args)["sample"].contiguous()
+        if run_guide and self.attn_maps is not None:
+            self.attn_maps.skip_evaluation()
         Fg = self.guide.forward_without_cfg(inp, t, self.y_g, 0)["sample"].to(torch.float32).contiguous() if run_guide else None
         return F, dup, Fg
 
@@ -610,11 +656,12 @@ def sample(model, x, y, steps, cfg, fused, cond_cache, req: Request, kwargs):
         assert can_fuse, "the fused sampler needs CUDA tensors and no extra forward arguments"
     plan = sampler_plan(model.edm_config, steps, req.sampler, req.strength if edit is not None else 1.0, req.resample,
                         device=None if fused else x.device)
-    with frozen_network(model.dit) if guided_by else nullcontext():
+    am = req.attn_maps
+    with frozen_network(model.dit) if guided_by else nullcontext(), recording(model.dit, am, x):
         if fused:
             guidance = (req.measurement, req.guidance_loss, zeta) if guided_by else None
-            return FusedRun(model, x, y, plan, cfg, cond_cache, interval, guide, guide_null, edit, gmode, guidance, req.step_cache).run()
-        net = TensorOpNetwork(model, y, cfg, interval, guide, guide_null, gmode, kwargs)
+            return FusedRun(model, x, y, plan, cfg, cond_cache, interval, guide, guide_null, edit, gmode, guidance, req.step_cache, am).run()
+        net = TensorOpNetwork(model, y, cfg, interval, guide, guide_null, gmode, kwargs, am)
         first = None
         if guided_by:
             loss_fn = req.guidance_loss if req.measurement is None else req.measurement.loss_fn(x)
