@@ -248,8 +248,9 @@ int md_colsum_det(const void* x, int32_t x_is_f32, int64_t ld, float* out, int64
                   hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------- attention */
-/* softmax(scale * Q K^T) V per (batch, head), non-causal, no mask.  Row r of head h of batch b of X lives at
- * X + b*sX + r*ldX + h*hsX (bf16; hsX = hd unless set), so packed qkv / kv projection buffers are addressed in place.
+/* softmax(scale * Q K^T) V per (batch, head), non-causal, no mask (md_attn_fwd_kbias below: a per-key bias).  Row r of head h of
+ * batch b of X lives at X + b*sX + r*ldX + h*hsX (bf16; hsX = hd unless set), so packed qkv / kv projection buffers are addressed in
+ * place.
  * lse / delta: f32 [B, H, Sq].  Replaces F.scaled_dot_product_attention (utils.py:127-132,188-193) + backward. */
 typedef struct md_attn_args {
     const void *q, *k, *v;
@@ -278,6 +279,16 @@ typedef struct md_attn_args {
 
 int md_attn_fwd(const md_attn_args* a, hipStream_t stream);
 int md_attn_bwd(const md_attn_args* a, hipStream_t stream);
+/* (symbol added, MD_ABI_VERSION stays 6.)  o = softmax_j(scale * q . k_j + kbias[b * ldb + j]) V per (sample, head): one
+ * fp32 bias per (sample, key), shared by all heads and all queries of the sample; lse includes the bias; -inf removes a key.
+ * Everything md_attn_fwd accepts in `a` (packed and head-major layouts) with 1 <= Skv <= 256: the kernel follows the phased forward
+ * that md_attn_fwd runs for these key counts -- same grid, workgroups, stores and arithmetic, the score in the log2 domain being
+ * acc * (scale * log2 e) + kbias * log2 e, the bias added in fp32.  A zero bias gives the bits of md_attn_fwd; -inf on the trailing
+ * keys [n, Skv) gives the bits of md_attn_fwd with Skv = n.  kbias non-NULL and 16-byte aligned, ldb >= Skv, ldb % 4 == 0; anything
+ * else returns MD_BAD_ARG and launches nothing.  Only rows [0, B) and columns [0, Skv) of kbias are read.  The caller's contract: no
+ * + inf or NaN in the bias, at least one finite bias per sample, K and V finite at removed keys (0 * NaN would poison the row).
+ * There is no backward for this form and no bias form of the streaming forward (Skv > 256). */
+int md_attn_fwd_kbias(const md_attn_args* a, const float* kbias, int64_t ldb, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------- elementwise */
 /* a = silu(h12[:, :f]) * h12[:, f:]  (FeedForward, dit.py:88-89) and its backward (dh12 from da). */
@@ -893,6 +904,12 @@ int md_muon_axpby(const void* x, const float* y, void* out, float a, float b, in
  * rows the launch does not name are not written; nothing is read past row Sq - 1 of q or row Skv - 1 of k of any sample.  out_rows holds
  * global row indices (md_get_mask's keep_rows, what md_gather_rows consumes). */
 int md_attn_probs(const md_attn_args* a, float* out, int64_t ldo, const int32_t* out_rows, hipStream_t stream);
+/* (symbol added.)  md_attn_probs of the attention md_attn_fwd_kbias ran: s = acc * scale + kbias[b * ldb + j] (natural
+ * units, the sum rounded on its own in fp32), everything else and every limit as above; a key with bias -inf adds exactly + 0 to its
+ * column.  kbias as for md_attn_fwd_kbias (non-NULL, 16-byte aligned, ldb >= Skv, ldb % 4 == 0, rows [0, B) x columns [0, Skv) read,
+ * no + inf / NaN, a finite bias in every row); else MD_BAD_ARG, nothing launched.  md_attn_probs itself keeps its bits. */
+int md_attn_probs_kbias(const md_attn_args* a, const float* kbias, int64_t ldb, float* out, int64_t ldo, const int32_t* out_rows,
+                        hipStream_t stream);
 
 #ifdef __cplusplus
 }

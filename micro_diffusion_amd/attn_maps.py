@@ -168,10 +168,12 @@ class AttentionMaps:
         self._active = False
 
     # ------------------------------------------------------------------------------------------ the engine's side
-    def record(self, name: str, ax, B: int, S: int, Lc: int, out_rows=None) -> None:
+    def record(self, name: str, ax, B: int, S: int, Lc: int, out_rows=None, kbias=None) -> None:
         """Behind the cross-attention of block `name`: add its head-averaged probabilities to the block's rows.  ax: the hip.AttnArgs
         attention ran with (both q / k layouts); B, S, Lc: samples, query rows per sample, caption positions; out_rows: int32 [B * S]
-        rows of the full grid (a masked pass's keep_rows) or None when S is the full grid.  One launch on the current stream."""
+        rows of the full grid (a masked pass's keep_rows) or None when S is the full grid; kbias: the engine's caption_bias (fp32
+        [>= B, ldb]) when attention ran with one -- the probabilities are then the biased ones, a removed position
+        records exactly 0.  One launch on the current stream."""
         r = self.row.get(name)
         if r is None or not self._active:
             return
@@ -195,8 +197,12 @@ class AttentionMaps:
         if nb != B:
             a = hip.AttnArgs.from_buffer_copy(ax)
             a.B = nb
-        hip.check(hip.lib().md_attn_probs(byref(a), self.buf[r].data_ptr(), ldo, None if out_rows is None else out_rows.data_ptr(),
-                                          hip.stream_ptr()), "md_attn_probs")
+        rows = None if out_rows is None else out_rows.data_ptr()
+        if kbias is None:
+            hip.check(hip.lib().md_attn_probs(byref(a), self.buf[r].data_ptr(), ldo, rows, hip.stream_ptr()), "md_attn_probs")
+        else:
+            hip.check(hip.lib().md_attn_probs_kbias(byref(a), kbias.data_ptr(), kbias.shape[1], self.buf[r].data_ptr(), ldo, rows,
+                                                    hip.stream_ptr()), "md_attn_probs_kbias")
         self._counts[r] += 1
 
     # ------------------------------------------------------------------------------------------ read-out (plain torch)

@@ -1,6 +1,7 @@
 // Fused multi-head attention (forward + backward) for the four MicroDiT shapes: patch-mixer self-attention
 // (S = T), backbone self-attention over the un-masked tokens (S = Tk), cross-attention to the 77 caption tokens,
-// and the caption block's 77 x 77 self-attention.  Non-causal, no mask, head_dim 64 (XL/2) or 32 (Tiny).
+// and the caption block's 77 x 77 self-attention.  Non-causal, no mask (md_attn_fwd_kbias: a per-key bias), head_dim 64 (XL/2)
+// or 32 (Tiny).
 //
 // One wave owns 32 query rows (forward, dQ) or 32 key rows (dK/dV); K/V (resp. Q/dO) tiles of 32 rows are shared
 // by the workgroup's waves through LDS.  All products run on v_mfma_f32_32x32x16_bf16:
@@ -284,15 +285,23 @@ __device__ __forceinline__ void store_lines(unsigned char* tile, int pitch, bf16
 // (Measured and dropped: capping this kernel at 128 VGPRs -- 117 without a spill at head_dim 64, 4 waves / SIMD instead of 3 --
 // made the 2-wave instantiation 15 % SLOWER in the step, 142.7 -> 164.9 us; the allocation the compiler picks on its own keeps
 // more of a phase's loads in flight.  profiles/r2_attention_two_phase_bwd.txt.)
-template <int HD, int MAXIT>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(md_attn_args p) {
+// The body of attn_fwd_kernel (BIAS = false: kbias, ldb and sBias are not read and the code is the kernel's own) and of
+// attn_fwd_kbias_kernel (BIAS = true): the score of key j of sample b gets kbias[b * ldb + j] added, in the log2 domain
+// like the score itself.  The sample's Skv <= KB_MAX biases are fetched ONCE per workgroup, times log2 e, into sBias (keys past Skv: 0,
+// they are masked by `rem` as before); a lane reads its 16 keys of a tile as four 16-byte LDS reads (tile_slot: four runs of four).
+constexpr int KB_MAX = 256;     // keys of the phased kernel: md_attn_fwd sends longer key sets to the streaming kernel
+template <int HD, int MAXIT, bool BIAS>
+__device__ __forceinline__ void attn_fwd_body(const md_attn_args& p, unsigned char* smem, const float* kbias, int64_t ldb, float* sBias) {
     constexpr int PK = (HD + 8) * 2;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STG * PK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x, nw = nthreads >> 6;
     const int hh = lane >> 5;
     const float c1 = p.scale * LOG2E;
     int64_t b = blockIdx.z, h = blockIdx.y;
     if (gridDim.x == 1) bh_of(blockIdx.y + (int64_t)gridDim.y * blockIdx.z, gridDim.y, gridDim.z, b, h);
+    if (BIAS) {     // visible to every wave after the first barrier of the key loop (Skv >= 1)
+        const int nb = (int)((p.Skv + 31) / 32) * 32;
+        for (int j = tid; j < nb; j += nthreads) sBias[j] = j < p.Skv ? kbias[b * ldb + j] * LOG2E : 0.f;
+    }
     const int64_t q = ((int64_t)blockIdx.x * nw + wave) * 32 + (lane & 31);
     const bool qvalid = q < p.Sq;
     const bf16* Q = reinterpret_cast<const bf16*>(p.q) + b * p.sq + h * p.hsq;
@@ -334,10 +343,25 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(md_attn_args p) {
         // compare + select for the key mask (the first version: a 64-bit index compare per element and exp through __expf)
         const int rem = (int)(p.Skv - key0);
         float tmax = -1e30f;
+        if (BIAS) {
+            // a removed key (-inf) leaves tmax alone and gives exp2(-inf) = 0, as the ragged-tail mask does; a tile of removed keys
+            // gives m_new = m, alpha = 1, psum = 0 and P.V = 0 (K and V there are finite): the state of a shorter key set, bit for bit
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            sacc[r] = tile_slot(r, hh) < rem ? sacc[r] * c1 : -1e30f;
-            tmax = fmaxf(tmax, sacc[r]);
+            for (int j = 0; j < 4; ++j) {
+                const f32x4 b4 = *reinterpret_cast<const f32x4*>(sBias + key0 + 8 * j + 4 * hh);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int r = 4 * j + e;
+                    sacc[r] = tile_slot(r, hh) < rem ? sacc[r] * c1 + b4[e] : -1e30f;
+                    tmax = fmaxf(tmax, sacc[r]);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                sacc[r] = tile_slot(r, hh) < rem ? sacc[r] * c1 : -1e30f;
+                tmax = fmaxf(tmax, sacc[r]);
+            }
         }
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
         const float m_new = fmaxf(m, tmax);
@@ -381,6 +405,20 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(md_attn_args p) {
         store_rows<HD>(O, oacc, 1.f / l, lane, sf(SF_FWD_WIDE) && !PLAIN && o16);
     }
     if (qvalid && lane < 32 && p.lse) reinterpret_cast<float*>(p.lse)[(b * p.H + h) * p.Sq + q] = (m + __log2f(l)) * 0.6931471805599453f;   // natural log
+}
+
+template <int HD, int MAXIT>
+__global__ __launch_bounds__(256) void attn_fwd_kernel(md_attn_args p) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STG * (HD + 8) * 2];
+    attn_fwd_body<HD, MAXIT, false>(p, smem, nullptr, 0, nullptr);
+}
+
+// softmax_j(scale q . k_j + kbias[b, j]) V: one fp32 bias per (sample, key), shared by the heads and the queries (md_attn_fwd_kbias)
+template <int HD, int MAXIT>
+__global__ __launch_bounds__(256) void attn_fwd_kbias_kernel(md_attn_args p, const float* __restrict__ kbias, int64_t ldb) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STG * (HD + 8) * 2];
+    __shared__ __attribute__((aligned(16))) float sBias[KB_MAX];
+    attn_fwd_body<HD, MAXIT, true>(p, smem, kbias, ldb, sBias);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1385,6 +1423,29 @@ extern "C" int md_attn_fwd(const md_attn_args* a_in, hipStream_t stream) {
         if (chunks <= 1) hipLaunchKernelGGL((attn_fwd_kernel<HD_, 1>), grid, dim3(64 * nw), 0, stream, *a);        \
         else if (chunks == 2) hipLaunchKernelGGL((attn_fwd_kernel<HD_, 2>), grid, dim3(64 * nw), 0, stream, *a);   \
         else hipLaunchKernelGGL((attn_fwd_kernel<HD_, 4>), grid, dim3(64 * nw), 0, stream, *a);                    \
+    } while (0)
+    if (a->hd == 64) FWD(64);
+    else FWD(32);
+#undef FWD
+    MD_LAUNCH_CHECK();
+    return 0;
+}
+
+// md_attn_fwd with a per-sample, per-key additive bias on the logits: the phased kernel's grid, workgroup sizes and
+// instantiation rule, so a zero bias reproduces md_attn_fwd's bits.  Key sets beyond the phased kernel's (Skv > 256) are refused.
+extern "C" int md_attn_fwd_kbias(const md_attn_args* a_in, const float* kbias, int64_t ldb, hipStream_t stream) {
+    if (!attn_ok(a_in) || !kbias || reinterpret_cast<uintptr_t>(kbias) % 16 != 0) return MD_BAD_ARG;
+    if (a_in->Skv > KB_MAX || ldb < a_in->Skv || ldb % 4 != 0) return MD_BAD_ARG;
+    const md_attn_args args = with_head_strides(a_in);
+    const md_attn_args* a = &args;
+    const int nw = waves_for(a->Sq);
+    dim3 grid((unsigned)((a->Sq + 32 * nw - 1) / (32 * nw)), (unsigned)a->H, (unsigned)a->B);
+#define FWD(HD_)                                                                                                                  \
+    do {                                                                                                                           \
+        const int chunks = (32 * (HD_ / 8) + 64 * nw - 1) / (64 * nw);                                                             \
+        if (chunks <= 1) hipLaunchKernelGGL((attn_fwd_kbias_kernel<HD_, 1>), grid, dim3(64 * nw), 0, stream, *a, kbias, ldb);      \
+        else if (chunks == 2) hipLaunchKernelGGL((attn_fwd_kbias_kernel<HD_, 2>), grid, dim3(64 * nw), 0, stream, *a, kbias, ldb); \
+        else hipLaunchKernelGGL((attn_fwd_kbias_kernel<HD_, 4>), grid, dim3(64 * nw), 0, stream, *a, kbias, ldb);                  \
     } while (0)
     if (a->hd == 64) FWD(64);
     else FWD(32);

@@ -2,7 +2,9 @@
 // k the fused attention ran on (md_attn_fwd never materialises them; the reference's F.scaled_dot_product_attention, utils.py:122-132,
 // does not either).
 //
-//   md_attn_probs   out[row, j] += (1 / H) * sum_h softmax_j(scale * q_h(b, q) . k_h(b, j)),  j < Skv <= 128
+//   md_attn_probs         out[row, j] += (1 / H) * sum_h softmax_j(scale * q_h(b, q) . k_h(b, j)),  j < Skv <= 128
+//   md_attn_probs_kbias   the same with kbias[b, j] added to the logit of key j (what md_attn_fwd_kbias ran on); -inf
+//                         removes a key, whose column then gets exactly + 0
 //
 // One workgroup of four waves takes 64 query rows of one sample and walks the heads in ascending order.  K of one head, padded with zero
 // rows to a multiple of 16 keys, lives in LDS (two buffers of 128 rows x (hd + 8) bf16: 36,864 bytes at hd = 64, 20,480 at hd = 32; the 8
@@ -18,6 +20,9 @@
 // order, then the two cross-lane adds (both symmetric: the four lanes of a query hold the same bits);  P = p * rcp(sum);  the head sum
 // in ascending head order in registers;  out += headsum * (1.0f / H) as the only writer of the element.  No atomics: same binary and
 // same arguments give the same bits.
+// The bias form is the same kernel with a.kbias set (one kernel per head_dim, a wave-uniform branch per score block): s = acc * scale + bias,
+// the sum rounded on its own.  The sample's biases are fetched once per workgroup into LDS that is already there and idle -- the first four
+// of the 16 padding bytes of key row j of buffer 0, which no K store and no fragment read touches -- so LDS and registers stay as they were.
 #include "md_common.h"
 #include "../../include/microdit_hip.h"
 #include <math.h>
@@ -35,9 +40,10 @@ constexpr int AP_MAX_KB = AP_MAX_KEYS / 16;
 
 struct ap_args {
     const bf16 *q, *k;
+    const float* kbias;                  // [B, ldb] or nullptr
     float* out;
     const int32_t* out_rows;
-    int64_t H, Sq, Skv, ldq, ldk, sq, sk, hsq, hsk, ldo, tiles;
+    int64_t H, Sq, Skv, ldq, ldk, sq, sk, hsq, hsk, ldo, tiles, ldb;
     float scale, inv_h;
 };
 
@@ -64,6 +70,11 @@ __global__ __launch_bounds__(AP_THREADS) void attn_probs_kernel(const ap_args a)
         *reinterpret_cast<uint4*>(&sK[0][off]) = make_uint4(0, 0, 0, 0);
         *reinterpret_cast<uint4*>(&sK[1][off]) = make_uint4(0, 0, 0, 0);
     }
+
+    const bool biased = a.kbias != nullptr;
+    if (biased)     // key j's bias -> the padding of row j of buffer 0 (rows [Skv, 16 nkb): 0, those keys are masked below)
+        for (int j = tid; j < nkb * 16; j += AP_THREADS)
+            *reinterpret_cast<float*>(&sK[0][j * LDK + HD]) = j < Skv ? a.kbias[b * a.ldb + j] : 0.f;
 
     const bf16* qp = a.q + b * a.sq + (qok ? qrow : 0) * a.ldq + 8 * quad;
     const bf16* kp = a.k + b * a.sk;
@@ -119,14 +130,16 @@ __global__ __launch_bounds__(AP_THREADS) void attn_probs_kernel(const ap_args a)
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float v = (16 * kb + 4 * quad + r < Skv) ? acc[r] * a.scale : -INFINITY;
+                    float v = acc[r] * a.scale;
+                    if (biased) v = v + *reinterpret_cast<const float*>(&sK[0][(16 * kb + 4 * quad + r) * LDK + HD]);
+                    v = (16 * kb + 4 * quad + r < Skv) ? v : -INFINITY;
                     s[kb][r] = v;
                     m = fmaxf(m, v);
                 }
             }
         }
         m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));      // key 0 is real: the maximum is finite
+        m = fmaxf(m, __shfl_xor(m, 32, 64));      // a real key with a finite bias exists (the caller's contract): the maximum is finite
         float sum = 0.f;
 #pragma unroll
         for (int kb = 0; kb < AP_MAX_KB; ++kb) {
@@ -187,9 +200,7 @@ __global__ __launch_bounds__(AP_THREADS) void attn_probs_kernel(const ap_args a)
 
 inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
-}  // namespace
-
-extern "C" int md_attn_probs(const md_attn_args* a, float* out, int64_t ldo, const int32_t* out_rows, hipStream_t stream) {
+int launch_probs(const md_attn_args* a, const float* kbias, int64_t ldb, float* out, int64_t ldo, const int32_t* out_rows, hipStream_t stream) {
     if (!a || !a->q || !a->k || !out) return MD_BAD_ARG;
     if (a->B < 1 || a->H < 1 || a->Sq < 1 || a->Skv < 1 || a->Skv > AP_MAX_KEYS || (a->hd != 32 && a->hd != 64)) return MD_BAD_ARG;
     if (ldo < a->Skv || ldo % 4 != 0 || !aligned16(out)) return MD_BAD_ARG;
@@ -197,6 +208,8 @@ extern "C" int md_attn_probs(const md_attn_args* a, float* out, int64_t ldo, con
     ap_args p;
     p.q = reinterpret_cast<const bf16*>(a->q);
     p.k = reinterpret_cast<const bf16*>(a->k);
+    p.kbias = kbias;
+    p.ldb = ldb;
     p.out = out;
     p.out_rows = out_rows;
     p.H = a->H, p.Sq = a->Sq, p.Skv = a->Skv, p.ldq = a->ldq, p.ldk = a->ldk, p.sq = a->sq, p.sk = a->sk;
@@ -212,4 +225,16 @@ extern "C" int md_attn_probs(const md_attn_args* a, float* out, int64_t ldo, con
     else hipLaunchKernelGGL((attn_probs_kernel<32>), grid, dim3(AP_THREADS), 0, stream, p);
     MD_LAUNCH_CHECK();
     return 0;
+}
+
+}  // namespace
+
+extern "C" int md_attn_probs(const md_attn_args* a, float* out, int64_t ldo, const int32_t* out_rows, hipStream_t stream) {
+    return launch_probs(a, nullptr, 0, out, ldo, out_rows, stream);
+}
+
+extern "C" int md_attn_probs_kbias(const md_attn_args* a, const float* kbias, int64_t ldb, float* out, int64_t ldo, const int32_t* out_rows,
+                                   hipStream_t stream) {
+    if (!kbias || !aligned16(kbias) || !a || ldb < a->Skv || ldb % 4 != 0) return MD_BAD_ARG;
+    return launch_probs(a, kbias, ldb, out, ldo, out_rows, stream);
 }

@@ -333,18 +333,19 @@ class DiT(nn.Module):
             sample, mask = self._engine.sample_image(tape), tape.mask
         return {"sample": sample, "mask": mask}
 
-    def forward_with_cfg(self, x, t, y, cfg: float = 1.0, mask_ratio: float = 0, **kwargs):
-        """Classifier-free guidance by batch doubling with zeroed captions (reference dit.py:542-550)."""
+    def forward_with_cfg(self, x, t, y, cfg: float = 1.0, mask_ratio: float = 0, negative=None, **kwargs):
+        """Classifier-free guidance by batch doubling with zeroed captions (reference dit.py:542-550).  negative: caption embeddings of
+        y's shape that take the place of the zeroed captions (a negative prompt)."""
         x2 = torch.cat([x, x], 0)
-        y2 = torch.cat([y, torch.zeros_like(y)], 0)
+        y2 = torch.cat([y, torch.zeros_like(y) if negative is None else negative], 0)
         t2 = torch.cat([t, t], 0) if len(t) != 1 else t
         eps = self.forward_without_cfg(x2, t2, y2, mask_ratio, **kwargs)["sample"]
         cond, uncond = torch.split(eps, len(eps) // 2, dim=0)
         return {"sample": uncond + cfg * (cond - uncond)}
 
-    def forward(self, x, t, y, cfg: float = 1.0, **kwargs):
+    def forward(self, x, t, y, cfg: float = 1.0, negative=None, **kwargs):
         if cfg != 1.0:
-            return self.forward_with_cfg(x, t, y, cfg, **kwargs)
+            return self.forward_with_cfg(x, t, y, cfg, negative=negative, **kwargs)
         return self.forward_without_cfg(x, t, y, **kwargs)
 
     def unpatchify(self, x: torch.Tensor) -> torch.Tensor:

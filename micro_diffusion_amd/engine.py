@@ -292,6 +292,14 @@ class DiTEngine:
         # head-averaged probabilities from the q / k attention just read (one md_attn_probs launch into its own fp32 buffer, no host
         # wait).  None: no launch, no buffer; arena sizes, addresses and the tape are those of an unarmed pass either way.
         self.attn_probe = None
+        # Caption bias (opt-in): None, or an fp32 device tensor [Bmax, ldb] (ldb >= Lc, ldb % 4 == 0, 16-byte aligned rows)
+        # added to the cross-attention logits of every mixer and backbone block: softmax_j(scale q . k_j + caption_bias[b, j]), one value per
+        # (sample, caption position), shared by heads and queries; -inf removes a position.  An evaluation at batch B <= Bmax reads the
+        # first B rows (sample-major, the convention of Conditioning.narrow).  The launches become md_attn_fwd_kbias (and, with an
+        # attn_probe, md_attn_probs_kbias); self-attention, the cached K / V of cond= and the pooled caption vector (md_mean_tokens: the
+        # plain mean over all positions) do not see it.  Inference only: the attention backward does not know the bias, so a forward
+        # that records a tape for a backward raises while it is set.  None: the launches and bits of a pass without it.
+        self.caption_bias = None
         # Masked-expert pruning: the masking right behind the last patch-mixer block keeps Tk of T tokens, so when that block
         # is MoE its expert MLPs (forward, both data gradients, both weight gradients) run only on the routed rows whose token survives --
         # about (1 - mask_ratio) of them.  Routing stays dense and the tape's probs / rowidx / gval / slot are those of the dense pass.
@@ -462,8 +470,26 @@ class DiTEngine:
         self._launch("md_qkln_bwd_hm", dy.data_ptr(), rows * width, y.data_ptr(), rows * width, dptr, ldd, doff, width, rows, width, nseg, S,
                      self.cfg.head_dim, rstd_ptr, prof="qk_layernorm", nbytes=6.0 * rows * width * nseg)
 
-    def _attn_fwd(self, a):
-        self._launch("md_attn_fwd", byref(a), prof="attention", nbytes=2.0 * a.hd * (2 * a.Sq + 2 * a.Skv) * a.B * a.H)
+    def _attn_fwd(self, a, kbias=None):
+        """kbias: the armed caption_bias for a cross-attention (its first a.B rows are read), else None."""
+        nbytes = 2.0 * a.hd * (2 * a.Sq + 2 * a.Skv) * a.B * a.H
+        if kbias is None:
+            self._launch("md_attn_fwd", byref(a), prof="attention", nbytes=nbytes)
+        else:
+            self._launch("md_attn_fwd_kbias", byref(a), kbias.data_ptr(), kbias.shape[1], prof="attention", nbytes=nbytes + 4.0 * a.Skv * a.B)
+
+    def _check_caption_bias(self, B, Lc, taping):
+        """The armed caption_bias against an evaluation at batch B with Lc caption positions, before anything is launched."""
+        kb = self.caption_bias
+        if taping:
+            raise RuntimeError("caption_bias is inference-only: the attention backward does not know the bias, so record_tape, arena and "
+                               "input_tape cannot be combined with it (DESIGN.md 4.22)")
+        if not (torch.is_tensor(kb) and kb.is_cuda and kb.dtype == F32 and kb.dim() == 2 and kb.is_contiguous()
+                and kb.shape[1] % 4 == 0 and kb.data_ptr() % 16 == 0):
+            raise ValueError("caption_bias must be a contiguous fp32 device tensor [Bmax, ldb] with ldb % 4 == 0, 16-byte aligned")
+        if B > kb.shape[0] or kb.shape[1] < Lc:
+            raise ValueError(f"caption_bias holds {kb.shape[0]} rows of {kb.shape[1]} positions; this evaluation has batch {B} and "
+                             f"{Lc} caption positions")
 
     def _gemm(self, **kw):
         a = hip.GemmArgs()
@@ -891,9 +917,9 @@ class DiTEngine:
                 t.rk2, t.k2n = self._k_norm_fwd(t.kv, Mc, hx, Lc)
             ax = self.attn_args(t.q2.data_ptr(), t.kv.data_ptr(), t.kv.data_ptr() + 2 * hx, t.o2, t.lse2, B, bp.xheads, S, Lc,
                                 hx, 2 * hx, 2 * hx, hx)
-        self._attn_fwd(ax)
+        self._attn_fwd(ax, self.caption_bias)
         if self.attn_probe is not None:
-            self.attn_probe.record(n, ax, B, S, Lc, out_rows)
+            self.attn_probe.record(n, ax, B, S, Lc, out_rows, self.caption_bias)
         x2 = self.empty(M, d)
         self.lin_fwd(t.o2, n + ".cross_attn.proj", x2, M, d, hx, mode=hip.EPI_RESIDUAL, res=x1)
         t.x2 = x2
@@ -1289,6 +1315,8 @@ class DiTEngine:
         else:
             assert y.is_contiguous() and y.dtype in (torch.float16, F32)
             Lc, Dc, ydt = y.shape[-2], y.shape[-1], str(y.dtype)
+        if self.caption_bias is not None:
+            self._check_caption_bias(B, Lc, record_tape or arena or input_tape)
         self._poison_ws()
         grad_pass = self.use_arena and arena and record_tape
         self._record = record_tape or input_tape or self.keep_last_tape

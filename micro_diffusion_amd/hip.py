@@ -195,6 +195,7 @@ _sig("md_qkln_bwd", P, I64, I64, P, I64, I64, I64, I64, I32, I64, I64, P, P)
 _sig("md_qkln_fwd_hm", P, I64, I64, I64, I64, I32, I64, P, I64, I64, I32, P, F32, P)
 _sig("md_qkln_bwd_hm", P, I64, P, I64, P, I64, I64, I64, I64, I64, I32, I64, I32, P, P)
 _sig("md_attn_fwd", POINTER(AttnArgs), P)
+_sig("md_attn_fwd_kbias", POINTER(AttnArgs), P, I64, P)      # args, kbias fp32 [B, ldb], ldb
 _sig("md_attn_bwd", POINTER(AttnArgs), P)
 _sig("md_swiglu_fwd", P, I64, P, I64, I64, I64, P)
 _sig("md_swiglu_bwd", P, I64, P, I64, P, I64, I64, I64, P)
@@ -325,6 +326,8 @@ _sig("md_muon_apply", P, P, P, P, P, I32, F32, F32, I32, F32, P, P, P)
 _sig("md_muon_axpby", P, P, P, F32, F32, I64, P)
 # cross-attention probe (attn_maps.py): head-averaged probabilities of a short key set added into fp32 rows
 _sig("md_attn_probs", POINTER(AttnArgs), P, I64, P, P)
+_sig("md_attn_probs_kbias", POINTER(AttnArgs), P, I64, P, I64, P, P)     # args, kbias, ldb, out, ldo, out_rows
+ATTN_KBIAS_MAX_KEYS = 256       # Skv of md_attn_fwd_kbias
 ATTN_PROBS_MAX_KEYS = 128       # Skv of md_attn_probs
 MUON_NORM_PARTS = 16            # MD_MUON_NORM_PARTS
 STEP_DELTA_MAX_BLOCKS = 2048    # MD_STEP_DELTA_MAX_BLOCKS

@@ -265,7 +265,7 @@ class LatentDiffusion(nn.Module):
                          guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
                          guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
                          apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, step_cache=None,
-                         attn_maps=None, **kwargs):
+                         attn_maps=None, negative=None, caption_weights=None, negative_weights=None, **kwargs):
         """EDM sampler, fp64 state (model.py:231-297): x is unit noise, y the caption embeddings, **kwargs extra forward arguments.
         The docstring of sampling.py defines every argument; sampling.tensor_op_loop (fused=False) is the definition of the loop and
         sampling.FusedRun the same loop in fused HIP kernels.  Every random draw of a run reads self.randn_like when it is made."""
@@ -274,7 +274,7 @@ class LatentDiffusion(nn.Module):
                                guidance_mode=guidance_mode, guidance_rescale=guidance_rescale, apg_eta=apg_eta,
                                apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, measurement=measurement,
                                measurement_scale=measurement_scale, guidance_loss=guidance_loss, step_cache=step_cache,
-                               attn_maps=attn_maps)
+                               attn_maps=attn_maps, negative=negative, caption_weights=caption_weights, negative_weights=negative_weights)
         return sampling.sample(self, x, y, steps, cfg, fused, cond_cache, req, kwargs)
 
     @torch.no_grad()
@@ -284,7 +284,8 @@ class LatentDiffusion(nn.Module):
                  guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
                  guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
                  apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, step_cache=None,
-                 attn_maps=None, **kwargs):
+                 attn_maps=None, negative_prompt: Optional[list] = None, negative_tokenized_prompts=None, negative_attention_mask=None,
+                 caption_weights=None, negative_weights=None, mask_padding: bool = False, **kwargs):
         """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache, sampler,
         guidance_interval, guide and guide_captions: as in edm_sampler_loop (with a guide, guidance_scale is the autoguidance weight).
         init_latents, strength, inpaint_mask and resample: image-to-image and inpainting as in edm_sampler_loop; the seeded draw below is
@@ -296,14 +297,28 @@ class LatentDiffusion(nn.Module):
         sampler's latent space, like init_latents).
         step_cache: a step_cache.StepCache, as in edm_sampler_loop.
         attn_maps: an attn_maps.AttentionMaps that records the cross-attention maps of the run, as in edm_sampler_loop (DESIGN.md 4.21);
-        mapping words to caption positions is the caller's (the tokenizer is third-party)."""
+        mapping words to caption positions is the caller's (the tokenizer is third-party).
+        Prompt control: negative_prompt (or negative_tokenized_prompts with negative_attention_mask) goes through the
+        same tokenizer and text encoder and becomes edm_sampler_loop's `negative`, the second operand of classifier-free guidance in place
+        of the zeroed captions (one prompt is broadcast over the batch).  caption_weights / negative_weights: per-position weights of the
+        two captions in every cross-attention, as in edm_sampler_loop.  mask_padding=True multiplies them (ones when None) by the
+        tokenizer's attention_mask -- and the negative half's by the negative prompt's --, which removes the padding positions from the
+        cross-attention; it raises when a mask is not available.  The network was trained without a caption mask: this is a tool, not
+        a quality claim.  The weights act on the cross-attention only; the text encoder and the pooled caption stay as they are."""
         req = sampling.Request(sampler=sampler, guidance_interval=guidance_interval, guide=guide, guide_captions=guide_captions,
                                init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, resample=resample,
                                guidance_mode=guidance_mode, guidance_rescale=guidance_rescale, apg_eta=apg_eta,
                                apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, measurement=measurement,
                                measurement_scale=measurement_scale, guidance_loss=guidance_loss, step_cache=step_cache,
-                               attn_maps=attn_maps)
-        req.check(self, None, guidance_scale)       # refuse before tokenising; edm_sampler_loop checks again with the state's shape
+                               attn_maps=attn_maps, caption_weights=caption_weights, negative_weights=negative_weights)
+        has_negative = bool(negative_prompt) or negative_tokenized_prompts is not None
+        # refuse before tokenising; edm_sampler_loop checks again with the shapes of the state and the captions
+        req.check(self, None, guidance_scale, has_negative=has_negative, will_weight=bool(mask_padding))
+        if mask_padding:
+            if (tokenized_prompts is not None and attention_mask is None) or \
+                    (negative_tokenized_prompts is not None and negative_attention_mask is None):
+                raise ValueError("mask_padding=True needs the tokenizer's attention_mask (attention_mask= / negative_attention_mask= "
+                                 "with tokenized prompts)")
         assert prompt or tokenized_prompts is not None, "Must provide either prompt or tokenized prompts"
         device = next(self.dit.parameters()).device
         gen = torch.Generator(device=device)
@@ -315,12 +330,31 @@ class LatentDiffusion(nn.Module):
             attention_mask = out.get("attention_mask")
         emb = self.text_encoder.encode(tokenized_prompts.to(device),
                                        attention_mask=attention_mask.to(device) if attention_mask is not None else None)[0]
+        if has_negative:
+            if negative_tokenized_prompts is None:
+                out = self.tokenizer.tokenize(negative_prompt)
+                negative_tokenized_prompts = out["input_ids"]
+                negative_attention_mask = out.get("attention_mask")
+            nmask = negative_attention_mask.to(device) if negative_attention_mask is not None else None
+            req.negative = self.text_encoder.encode(negative_tokenized_prompts.to(device), attention_mask=nmask)[0]
+        if mask_padding:
+            req.caption_weights = _masked_weights(req.caption_weights, attention_mask, "attention_mask", device)
+            if has_negative:
+                req.negative_weights = _masked_weights(req.negative_weights, negative_attention_mask, "negative_attention_mask", device)
         latents = torch.randn((len(emb), self.dit.in_channels, self.latent_res, self.latent_res), device=device, generator=gen)
         latents = self.edm_sampler_loop(latents, emb, num_inference_steps, cfg=guidance_scale, cond_cache=cond_cache, **vars(req))
         if return_only_latents:
             return latents
         image = self.vae.decode((latents / self.latent_scale).to(DATA_TYPES[self.dtype])).sample
         return (image / 2 + 0.5).clamp(0, 1).float().detach()
+
+
+def _masked_weights(weights, attention_mask, name: str, device):
+    """generate(mask_padding=True): caption weights (ones when None) times the tokenizer's attention mask [B, Lc]."""
+    if attention_mask is None:
+        raise ValueError(f"mask_padding=True needs the tokenizer's {name}, and the tokenizer returned none")
+    m = attention_mask.to(device=device, dtype=torch.float32).reshape(attention_mask.shape[0], -1)
+    return m if weights is None else weights.to(device=device, dtype=torch.float32) * m
 
 
 def _edm_forward(model: LatentDiffusion, anchor, x, y, rnd, eps, mnoise, mask_ratio, y_rowscale=None, train=None,

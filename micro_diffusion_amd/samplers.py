@@ -304,6 +304,86 @@ def check_attn_maps(attn_maps=None, config=None) -> bool:
     return True
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Prompt control: a negative prompt as the second operand of classifier-free guidance, and per-position caption
+# weights w_j >= 0 that enter every cross-attention as the additive bias ln w_j on the logits: P_j = w_j e^{s_j} / sum_i w_i e^{s_i}
+# (w = 1: today's softmax, w = 0: the position is removed).
+# ---------------------------------------------------------------------------------------------------------------------
+def _check_weights(name: str, w, B: Optional[int], Lc: Optional[int]) -> None:
+    import torch
+    if not torch.is_tensor(w):
+        raise ValueError(f"{name} must be a tensor [B, Lc], [1, Lc] or [Lc], got {type(w).__name__}")
+    if w.dtype != torch.bool and not w.dtype.is_floating_point:
+        raise ValueError(f"{name} must be bool or floating point, got {w.dtype}")
+    if w.dim() not in (1, 2) or w.shape[-1] < 1:
+        raise ValueError(f"{name} has shape {tuple(w.shape)}: expected [B, Lc], [1, Lc] or [Lc]")
+    if Lc is not None and (w.shape[-1] != Lc or (w.dim() == 2 and w.shape[0] not in (1, B))):
+        raise ValueError(f"{name} has shape {tuple(w.shape)}: expected [{B}, {Lc}], [1, {Lc}] or [{Lc}]")
+    v = w.detach().to(torch.float32)
+    if not bool(torch.isfinite(v).all()) or bool((v < 0).any()):
+        raise ValueError(f"{name} must be finite and >= 0 (0 removes a caption position)")
+    if not bool((v > 0).any(dim=-1).all()):
+        raise ValueError(f"{name}: every row needs at least one weight > 0 (a caption with every position removed has no softmax)")
+
+
+def check_prompt_control(has_negative: bool = False, caption_weights=None, negative_weights=None, cfg: float = 1.0, guide=None,
+                         measurement=None, guidance_loss=None, negative=None, y_shape=None, will_weight: bool = False) -> bool:
+    """Refuse, before anything is tokenised, launched or allocated, a prompt-control request that is not defined; True
+    when the run arms a caption bias (any weights).
+    has_negative: the run has a negative prompt; negative: its embeddings once they exist.  will_weight: weights will be made later
+    (generate's mask_padding).  y_shape: the shape of the caption embeddings y once it is known; the shapes are then checked too:
+    negative as y or with a leading 1, weights [B, Lc], [1, Lc] or [Lc].
+    ValueError for a wrong shape, a negative or non-finite weight, a row without a positive weight, a negative prompt with cfg <= 1
+    (there is no second operand to replace), negative_weights without a negative prompt, any of the three with guide= (the guide may
+    share the engine and needs a bias of its own: not done), and weights with measurement= / guidance_loss= (their backward does not
+    know the bias).  A negative prompt alone composes with those two."""
+    has_negative = bool(has_negative) or negative is not None
+    weights = caption_weights is not None or negative_weights is not None or bool(will_weight)
+    if not has_negative and not weights:
+        return False
+    if guide is not None:
+        raise ValueError("negative / caption_weights / negative_weights with guide= (autoguidance) is not done: the guide may share the "
+                         "engine and needs a caption bias of its own (DESIGN.md 4.22)")
+    if has_negative and not float(cfg) > 1.0:
+        raise ValueError(f"a negative prompt replaces the second operand of classifier-free guidance: it needs cfg > 1, got {cfg!r}")
+    if negative_weights is not None and not has_negative:
+        raise ValueError("negative_weights needs negative= (a negative prompt): they weight its positions")
+    if weights and (measurement is not None or guidance_loss is not None):
+        raise ValueError("caption_weights / negative_weights with measurement= / guidance_loss= is not defined: the attention backward "
+                         "does not know the caption bias (DESIGN.md 4.22)")
+    B = Lc = None
+    if y_shape is not None:
+        B, Lc = int(y_shape[0]), int(y_shape[-2])
+        if negative is not None and not (len(negative.shape) == len(y_shape) and tuple(negative.shape[1:]) == tuple(y_shape[1:])
+                                         and negative.shape[0] in (1, B)):
+            raise ValueError(f"negative has shape {tuple(negative.shape)}, the captions {tuple(y_shape)}: expected that shape, or a "
+                             "leading 1 that is broadcast")
+    for name, w in (("caption_weights", caption_weights), ("negative_weights", negative_weights)):
+        if w is not None:
+            _check_weights(name, w, B, Lc)
+    return weights
+
+
+def caption_log_bias(weights, B: int, Lc: int, device=None):
+    """ln w of caption weights ([B, Lc], [1, Lc] or [Lc]; bool or floating point) as fp32 [B, Lc] on `device`: 0 at w = 1, -inf at 0."""
+    import torch
+    w = weights.detach().to(device=device, dtype=torch.float32).reshape(-1, Lc).expand(B, Lc)
+    return torch.log(w)
+
+
+def caption_bias_buffer(caption_weights, negative_weights, B: int, Lc: int, doubled: bool, device=None):
+    """The caption bias of one run: fp32 [2 B, ldb] when the run doubles evaluations (rows [0, B): the captions, [B, 2 B): the second
+    half), else [B, ldb]; ldb = Lc rounded up to 4.  A half without weights and the pad columns [Lc, ldb) hold 0."""
+    import torch
+    ldb = (Lc + 3) // 4 * 4
+    buf = torch.zeros((2 * B if doubled else B), ldb, device=device, dtype=torch.float32)
+    if caption_weights is not None:
+        buf[:B, :Lc] = caption_log_bias(caption_weights, B, Lc, device)
+    if doubled and negative_weights is not None:
+        buf[B:, :Lc] = caption_log_bias(negative_weights, B, Lc, device)
+    return buf
+
+
 def evaluation_sigmas(sampler: str, t_steps: Sequence[float]) -> List[float]:
     """The noise level of every network evaluation of a run without churn, in order."""
     out = []

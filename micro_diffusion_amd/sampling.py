@@ -61,6 +61,20 @@ behind every selected block's cross-attention one md_attn_probs launch adds the 
 conditional half of a doubled batch) to its buffer.  A `guide` network is not recorded.  It only reads: it composes with every argument
 above, both loops included, and the latents are the bits of the run without it.  None: the launches and bits of a run without the
 argument.
+Prompt control (the tensor-op loop, fused=False, is the definition).  `negative`: caption embeddings of the shape of y
+(or with a leading 1 that is broadcast) that replace the zeroed captions as the second half of every batch-doubled evaluation -- in both
+loops, in the guidance modes and in the conditioning cache (encode_condition then sees [y; negative]); needs cfg > 1.
+`caption_weights` ([B, Lc], [1, Lc] or [Lc]; bool or floating point; host or device; finite, >= 0, a value > 0 in every row): weight
+w_j of caption position j in every cross-attention of the main network, P_j = w_j e^{s_j} / sum_i w_i e^{s_i}: the bias ln w_j on the
+logit (md_attn_fwd_kbias); 1 is today's softmax, 0 removes the position (a padding mask: the caption behaves as if it were shorter).
+`negative_weights`: the same for the second half (needs `negative`).  The run's bias buffer (samplers.caption_bias_buffer: fp32
+[2 B, ldb] when evaluations are doubled, else [B, ldb]) is armed as engine.caption_bias for the run, and what the attribute held before
+(None, or a bias armed by hand) is put back when the run ends, an error included; evaluations outside a guidance_interval run at batch B and read its first B rows.  The weights act on the cross-attention only:
+the pooled caption vector stays the plain mean over all positions, and the text encoder is not touched.  They compose with the solvers,
+churn, guidance_interval, the guidance modes, cond_cache, the editing options, step_cache and attn_maps (which then records the
+probabilities the run used: exactly 0 at a removed position); refused (ValueError): any of the three with `guide`, weights with
+`measurement` / `guidance_loss` (the attention backward does not know the bias; `negative` alone composes with them).  None: the
+launches and bits of a run without the arguments.
 """
 from __future__ import annotations
 
@@ -113,6 +127,27 @@ def recording(dit, attn_maps, x):
         attn_maps.disarm(engine)
 
 
+@contextmanager
+def caption_bias(dit, bias):
+    """Context of a run with caption weights: the run's bias buffer is the main network's engine.caption_bias inside,
+    and what the attribute held before (None, or a bias the caller armed by hand) is put back afterwards, whatever ended the run.
+    None: nothing is touched, so a run without weights on an engine armed by hand runs under that bias."""
+    if bias is None:
+        yield
+        return
+    engine = dit.engine
+    before, engine.caption_bias = engine.caption_bias, bias
+    try:
+        yield
+    finally:
+        engine.caption_bias = before
+
+
+def negative_captions(y, negative):
+    """negative as the second half of [y; negative]: y's dtype and device, a leading 1 broadcast over the batch."""
+    return negative.detach().to(device=y.device, dtype=y.dtype).expand_as(y)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The request: the options of one run, checked once
 # ---------------------------------------------------------------------------------------------------------------------
@@ -137,13 +172,18 @@ class Request:
     guidance_loss: Any = None
     step_cache: Any = None
     attn_maps: Any = None
+    negative: Any = None
+    caption_weights: Any = None
+    negative_weights: Any = None
 
-    def check(self, model, shape, cfg, extra=()):
+    def check(self, model, shape, cfg, extra=(), y_shape=None, has_negative=False, will_weight=False):
         """Refuse, before anything is tokenised, launched, allocated or drawn, a request that is not defined (the samplers.check_*
         functions, in this order).  shape: (B, C, H, W) of the state, or None when it is not known yet; extra: the names of the extra
-        forward arguments.  Returns (caching, guided_by, interval, gmode): whether the run uses the step cache, whether it is
-        measurement-guided, the guidance interval's bounds or None, and (mode, phi, eta, r or None, beta) of a run that is guided
-        in a mode other than "cfg" (else None)."""
+        forward arguments; y_shape: the shape of the caption embeddings when known; has_negative / will_weight: a negative prompt will
+        be encoded / caption weights will be made from the tokenizer's mask (generate, before it has tokenised).
+        Returns (caching, guided_by, interval, gmode): whether the run uses the step cache, whether it is measurement-guided, the
+        guidance interval's bounds or None, and (mode, phi, eta, r or None, beta) of a run that is guided in a mode other than "cfg"
+        (else None)."""
         samplers.check_sampler(self.sampler, model.edm_config.S_churn)
         caching = samplers.check_step_cache(self.step_cache, self.guide, self.measurement, self.guidance_loss)
         guided_by = samplers.check_measurement(shape, self.measurement, self.measurement_scale, self.guidance_loss)
@@ -164,6 +204,8 @@ class Request:
         samplers.check_edit(self.sampler, self.init_latents is not None, self.strength, self.inpaint_mask is not None, self.resample)
         if self.attn_maps is not None:
             samplers.check_attn_maps(self.attn_maps, model.dit.config)
+        samplers.check_prompt_control(has_negative, self.caption_weights, self.negative_weights, cfg, self.guide, self.measurement,
+                                      self.guidance_loss, self.negative, y_shape, will_weight)
         return caching, guided_by, interval, gmode
 
 
@@ -256,7 +298,8 @@ def autoguided_forward(model, guide, y_guide, w: float, attn_maps=None):
 class TensorOpNetwork:
     """The network evaluations of the tensor-op loop: denoise(xs, sigma) -> the denoised prediction in fp64, in three forms."""
 
-    def __init__(self, model, y, cfg: float, interval, guide, guide_null: bool, gmode, kwargs, attn_maps=None):
+    def __init__(self, model, y, cfg: float, interval, guide, guide_null: bool, gmode, kwargs, attn_maps=None, negative=None):
+        """negative: the second half of a doubled evaluation in place of the zeroed captions (no guide), already of y's shape."""
         self.model, self.y, self.cfg, self.interval, self.guide, self.gmode, self.kwargs = model, y, cfg, interval, guide, gmode, kwargs
         self.attn_maps = attn_maps
         dit = model.dit
@@ -264,10 +307,12 @@ class TensorOpNetwork:
             self.guided_forward = dit.forward
         elif guide is not None:
             self.guided_forward = autoguided_forward(model, guide, torch.zeros_like(y) if guide_null else y, cfg, attn_maps)
+        elif negative is not None:
+            self.guided_forward = partial(dit.forward, cfg=cfg, negative=negative)
         else:
             self.guided_forward = partial(dit.forward, cfg=cfg)
         if gmode is not None:
-            self.y_u = y if guide is not None and not guide_null else torch.zeros_like(y)
+            self.y_u = y if guide is not None and not guide_null else (torch.zeros_like(y) if negative is None else negative)
             self.M = None                           # the M of the previous guided evaluation of this run
 
     def inside(self, sigma) -> bool:
@@ -401,6 +446,8 @@ class FusedRun:
     md_guide_cotangent_tok -> the bf16 cotangent of both halves of the output, engine.backward(("x",), param_grads=False) -> the
     gradient of the network input, which stops at the image; the tape is dropped, the step's usual update runs (Heun's second
     evaluation without a tape) and md_edm_guide_apply corrects its result in place.  None: none of it.
+    negative (no guide): the second half of the doubled captions y2 in place of zeros, already of y's shape.  The
+    caption bias of a run with weights is not this class's business: sample() arms it on the engine around run().
     step_cache: a step_cache.StepCache (no guide, no guidance): it is reset for the run's evaluation count, and every
     network() call hands the engine its ResidualCache and a decision callback (StepCache.engine_args) -- through engine.forward with
     cond_cache, through dit.forward_without_cfg without.  None: none of it.
@@ -408,7 +455,7 @@ class FusedRun:
     The constructor allocates the run's buffers (and writes the image-to-image start); run() steps."""
 
     def __init__(self, model, x, y, plan: Plan, cfg: float, cond_cache: bool = False, interval=None, guide=None, guide_null: bool = False,
-                 edit=None, gmode=None, guidance=None, step_cache=None, attn_maps=None):
+                 edit=None, gmode=None, guidance=None, step_cache=None, attn_maps=None, negative=None):
         self.model, self.dit, self.guide, self.plan, self.step_cache = model, model.dit, guide, plan, step_cache
         self.attn_maps = attn_maps
         self.L, self.st, self.sd = hip.lib(), torch.cuda.current_stream().cuda_stream, model.edm_config.sigma_data
@@ -435,7 +482,7 @@ class FusedRun:
         self.x_nxt, self.d_cur = torch.empty_like(self.x_cur), torch.empty_like(self.x_cur)
         self.auto = guide is not None and self.guided       # with a guide the second operand comes from it: the batch is never doubled
         doubled = self.guided and not self.auto
-        self.y2 = torch.cat([y, torch.zeros_like(y)], 0) if doubled else y
+        self.y2 = torch.cat([y, torch.zeros_like(y) if negative is None else negative], 0) if doubled else y
         Bn = self.Bn = 2 * B if doubled else B
         if self.auto:
             self.y_g = torch.zeros_like(y) if guide_null else y
@@ -640,7 +687,7 @@ class FusedRun:
 # ---------------------------------------------------------------------------------------------------------------------
 def sample(model, x, y, steps, cfg, fused, cond_cache, req: Request, kwargs):
     """edm_sampler_loop: check the request, convert the edit operands, choose the loop, make the plan where that loop wants it, run."""
-    caching, guided_by, interval, gmode = req.check(model, tuple(x.shape), cfg, kwargs)
+    caching, guided_by, interval, gmode = req.check(model, tuple(x.shape), cfg, kwargs, y_shape=None if y is None else tuple(y.shape))
     edit = None if req.init_latents is None else edit_operands(x, req.init_latents, req.inpaint_mask)
     can_fuse = not kwargs and x.is_cuda
     cond_cache = sampler_cache_enabled(cond_cache)
@@ -657,11 +704,17 @@ def sample(model, x, y, steps, cfg, fused, cond_cache, req: Request, kwargs):
     plan = sampler_plan(model.edm_config, steps, req.sampler, req.strength if edit is not None else 1.0, req.resample,
                         device=None if fused else x.device)
     am = req.attn_maps
-    with frozen_network(model.dit) if guided_by else nullcontext(), recording(model.dit, am, x):
+    negative = None if req.negative is None else negative_captions(y, req.negative)
+    bias = None
+    if req.caption_weights is not None or req.negative_weights is not None:
+        doubled = any(samplers.is_guided(s, cfg, interval) for s in plan.sigmas)       # (no guide: a guided evaluation is a doubled one)
+        bias = samplers.caption_bias_buffer(req.caption_weights, req.negative_weights, x.shape[0], y.shape[-2], doubled, x.device)
+    with frozen_network(model.dit) if guided_by else nullcontext(), recording(model.dit, am, x), caption_bias(model.dit, bias):
         if fused:
             guidance = (req.measurement, req.guidance_loss, zeta) if guided_by else None
-            return FusedRun(model, x, y, plan, cfg, cond_cache, interval, guide, guide_null, edit, gmode, guidance, req.step_cache, am).run()
-        net = TensorOpNetwork(model, y, cfg, interval, guide, guide_null, gmode, kwargs, am)
+            return FusedRun(model, x, y, plan, cfg, cond_cache, interval, guide, guide_null, edit, gmode, guidance, req.step_cache, am,
+                            negative).run()
+        net = TensorOpNetwork(model, y, cfg, interval, guide, guide_null, gmode, kwargs, am, negative)
         first = None
         if guided_by:
             loss_fn = req.guidance_loss if req.measurement is None else req.measurement.loss_fn(x)
