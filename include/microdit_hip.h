@@ -911,6 +911,53 @@ int md_attn_probs(const md_attn_args* a, float* out, int64_t ldo, const int32_t*
 int md_attn_probs_kbias(const md_attn_args* a, const float* kbias, int64_t ldb, float* out, int64_t ldo, const int32_t* out_rows,
                         hipStream_t stream);
 
+/* ------------------------------------------------------------------------------------------- MXFP8 (block-scaled fp8) */
+/* (symbols added, MD_ABI_VERSION stays 6.)  OCP MX with e4m3fn elements ("MXFP8"): a matrix [rows, K] is stored as fp8
+ * elements, K-contiguous, plus one e8m0 scale byte per 32 consecutive elements along K, row-major uint8 [rows, K / 32].  For a block with
+ * largest magnitude amax:  X = clamp(floor(log2 amax) - 8, -127, 127), scale byte = X + 127 (0 with zero elements when amax = 0),
+ * element = e4m3fn_rne(clamp(v * 2^-X, -448, 448)); the scaling is exact, the clamp keeps amax in (448 * 2^X, 512 * 2^X) from
+ * overflowing.  Inputs are finite.  Inference only (the sampler's opt-in mxfp8=): nothing here has a backward.
+ *
+ * md_mx_quant_rows: src bf16, element (r, k) at src[r * ld + k] (src_kcontig = 1: activations, nn.Linear weights [N, K]) or at
+ * src[k * ld + r] (src_kcontig = 0: the MoE expert tensors, whose contraction dimension is the strided one) ->
+ * dst[r * ldd + k] fp8 and scales[r * lds + k / 32]; `batch` matrices sSrc elements / sDst bytes / sScale bytes apart.  K % 32 == 0,
+ * ld % 8 == 0, ldd % 16 == 0, ldd >= K, lds >= K / 32, src and dst 16-byte aligned; else MD_BAD_ARG, nothing launched.  No atomics,
+ * one writer per output byte; bytes [K, ldd) of a dst row, [K / 32, lds) of a scale row and rows the call does not name are not
+ * written.  Bit-exact against the rule above (tests/mx_ref.py). */
+int md_mx_quant_rows(const void* src, int64_t ld, int32_t src_kcontig, void* dst, int64_t ldd, void* scales, int64_t lds, int64_t rows,
+                     int64_t K, int32_t batch, int64_t sSrc, int64_t sDst, int64_t sScale, hipStream_t stream);
+/* md_swiglu_fwd writing a[m, c] = silu(h12[m, c]) * h12[m, f + c] as MXFP8 (a: fp8 [M, f] with pitch lda bytes, scales uint8 [M, f / 32]
+ * with pitch lds): the bits of md_swiglu_fwd followed by md_mx_quant_rows.  f % 32 == 0, ldh % 8 == 0, lda % 16 == 0. */
+int md_swiglu_fwd_mx(const void* h12, int64_t ldh, void* a, int64_t lda, void* scales, int64_t lds, int64_t M, int64_t f,
+                     hipStream_t stream);
+
+/* C[m, n] = epilogue(sum_k A(m, k) * B(n, k)): A [M, K] and B [N, K] MXFP8 (above), fp32 accumulation on
+ * v_mfma_scale_f32_16x16x128_f8f6f4, the hardware applying both block scales.  Epilogues, with the rounding steps of md_gemm_bf16:
+ *   MD_EPI_STORE_BF16  C = bf16(act(acc + bias)), act in {MD_ACT_NONE, MD_ACT_GELU_ERF}; optional C2 = bf16(acc + bias)
+ *   MD_EPI_RESIDUAL    C = bf16(res + gate[row / rows_per_sample, col] * bf16(acc + bias)) (gate optional); optional C2; batch == 1
+ * bias fp32 [N] (optional).  `batch` problems sA / sB / sScaleA / sScaleB bytes and sC / sC2 / sBias elements apart (the experts).
+ * Any M >= 1; N % 16 == 0 and K % 128 == 0, else MD_NOT_ELIGIBLE (-2) and nothing is launched.  lda, ldb (bytes) % 16 == 0, ldc, ldc2,
+ * ldr, ldg,
+ * sC, sC2 % 8 == 0, A, B, C, C2, res and gate 16-byte aligned, ldr and ldg >= N; a malformed problem is MD_BAD_ARG.  Nothing is read or written outside the named rows
+ * and columns; no atomics, one writer per output element. */
+typedef struct md_gemm_mx_args {
+    const void* A;       /* fp8 [M, K], element (m, k) at A[m * lda + k] */
+    const void* B;       /* fp8 [N, K] */
+    const void* scaleA;  /* uint8 [M, K / 32], pitch ldsa */
+    const void* scaleB;  /* uint8 [N, K / 32], pitch ldsb */
+    void* C;             /* bf16 [M, N] */
+    void* C2;            /* bf16 [M, N] or NULL */
+    const void* bias;    /* fp32 [N] or NULL */
+    const void* res;     /* bf16 [M, N] (MD_EPI_RESIDUAL) */
+    const void* gate;    /* bf16 [M / rows_per_sample, N] or NULL */
+    int64_t M, N, K;
+    int64_t lda, ldb, ldsa, ldsb, ldc, ldc2, ldr, ldg;
+    int64_t sA, sB, sScaleA, sScaleB, sC, sC2, sBias;
+    int64_t rows_per_sample;
+    int32_t batch, mode, act, reserved;
+} md_gemm_mx_args;
+int md_gemm_mxfp8(const md_gemm_mx_args* a, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -320,6 +320,9 @@ class DiT(nn.Module):
         if gt:      # one value per sample through differentiable torch ops: a one-element t gets the batch sum from expand's backward
             tin = t.to(torch.float32).reshape(-1).expand(B).contiguous()
         if need_grad:
+            if self._engine.mx is not None:
+                raise RuntimeError("mx (MXFP8 linears) is inference-only: call under torch.no_grad() (or with frozen parameters and inputs "
+                                   "that do not require grad)")
             if cond is not None:
                 raise RuntimeError("cond is inference-only: call under torch.no_grad() (or with frozen parameters and inputs that "
                                    "do not require grad)")

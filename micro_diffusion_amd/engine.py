@@ -300,6 +300,13 @@ class DiTEngine:
         # plain mean over all positions) do not see it.  Inference only: the attention backward does not know the bias, so a forward
         # that records a tape for a backward raises while it is set.  None: the launches and bits of a pass without it.
         self.caption_bias = None
+        # MXFP8 linears (opt-in): None, or an mxfp8.MXWeights -- block-scaled fp8 copies of the targeted block linears.
+        # lin_fwd, the two expert GEMMs and the SwiGLU FFN then quantise their input (md_mx_quant_rows / md_swiglu_fwd_mx, buffers from
+        # empty() like every activation) and launch md_gemm_mxfp8 wherever the weight is in `mx` and the problem is eligible (K % 128 ==
+        # 0, N % 16 == 0); every other launch is the bf16 one, unchanged.  Inference only: a forward that records a tape raises while it
+        # is set, and so does one whose MXWeights were built from another weight version.  None: the launches and bits of a pass without it.
+        self.mx = None
+        self.mx_log = None                 # tests: list that receives (weight name, "mx" | "bf16") per linear of lin_fwd / the expert GEMMs
         # Masked-expert pruning: the masking right behind the last patch-mixer block keeps Tk of T tokens, so when that block
         # is MoE its expert MLPs (forward, both data gradients, both weight gradients) run only on the routed rows whose token survives --
         # about (1 - mask_ratio) of them.  Routing stays dense and the tape's probs / rowidx / gval / slot are those of the dense pass.
@@ -546,14 +553,67 @@ class DiTEngine:
         return True
 
     def lin_fwd(self, x, wname, out, M, N, K, *, ldx=None, ldc=None, mode=hip.EPI_STORE_BF16, act=0, res=None,
-                gate=None, ldg=0, rps=0, C2=None, ldc2=0, xoff=0, ooff=0, bias=True):
-        """out[M,N] = epilogue(x[M,K] @ W[N,K]^T + b).  x / out may be offset views (element offsets)."""
+                gate=None, ldg=0, rps=0, C2=None, ldc2=0, xoff=0, ooff=0, bias=True, xq=None):
+        """out[M,N] = epilogue(x[M,K] @ W[N,K]^T + b).  x / out may be offset views (element offsets).
+        xq: (elements, scales) of x already in MXFP8 (md_swiglu_fwd_mx), for a weight that is in self.mx; x is then not read."""
         b = self.P.get(wname + ".bias") if bias else None
+        if self.mx is not None and mode in (hip.EPI_STORE_BF16, hip.EPI_RESIDUAL):
+            ent = self.mx.entries.get(wname)
+            # (the kernels move 16-byte pieces: an offset view that breaks their alignment keeps the bf16 launch)
+            if ent is not None and ent.batch == 1 and (ent.N, ent.K) == (N, K) and ooff % 8 == 0 and (ldc or N) % 8 == 0 and \
+                    (xq is not None or ((ldx or K) % 8 == 0 and xoff % 8 == 0)):
+                if xq is None:
+                    xq = self._mx_quant(x.data_ptr() + 2 * xoff, ldx or K, M, K)
+                self._mx_gemm(xq, ent, out.data_ptr() + 2 * ooff, M, N, K, ldc=ldc or N, mode=mode, act=act, bias=_p(b), res=_p(res), ldr=N,
+                              gate=gate, ldg=ldg, rps=rps, C2=_p(C2), ldc2=ldc2 or N)
+                if self.mx_log is not None:
+                    self.mx_log.append((wname, "mx"))
+                return
+        assert xq is None, f"{wname}: an MXFP8 input needs the weight in engine.mx"
+        if self.mx_log is not None:
+            self.mx_log.append((wname, "bf16"))
         self._gemm(A=x.data_ptr() + 2 * xoff, B=self.S[wname + ".weight"].data_ptr(),
                    C=out.data_ptr() + (4 if mode in (hip.EPI_STORE_F32, hip.EPI_ACCUM_F32) else 2) * ooff,
                    C2=_p(C2), bias=_p(b), res=_p(res), gate=gate, M=M, N=N, K=K, lda=ldx or K, ldb=K, ldc=ldc or N,
                    ldc2=ldc2 or N, ldr=N, ldg=ldg, rows_per_sample=rps, batch=1, ksplit=1, a_kcontig=1, b_kcontig=1,
                    mode=mode, act=act, alpha=1.0)
+
+    # ------------------------------------------------------------------------------------------ MXFP8 (DESIGN.md 4.23)
+    def _mx_quant(self, src_ptr, ld, M, K, batch=1, sSrc=0, rows_alloc=None):
+        """bf16 rows -> (elements uint8 [batch, rows_alloc, K], scales uint8 [batch, rows_alloc, K / 32]); the first M rows of every
+        batch entry are written."""
+        R = rows_alloc or M
+        q, sc = self.empty(batch, R, K, dtype=torch.uint8), self.empty(batch, R, K // 32, dtype=torch.uint8)
+        self._launch("md_mx_quant_rows", src_ptr, ld, 1, q.data_ptr(), K, sc.data_ptr(), K // 32, M, K, batch, sSrc, R * K, R * (K // 32),
+                     prof="mx_quant", nbytes=3.0 * M * K * batch)
+        return q, sc
+
+    def _mx_gemm(self, xq, ent, out_ptr, M, N, K, *, ldc, mode=hip.EPI_STORE_BF16, act=0, bias=None, res=None, ldr=0, gate=None, ldg=0,
+                 rps=0, C2=None, ldc2=0, batch=1, sC=0):
+        q, sc = xq
+        rows = q.shape[1]
+        a = hip.GemmMxArgs(q.data_ptr(), ent.q.data_ptr(), sc.data_ptr(), ent.s.data_ptr(), out_ptr, C2, bias, res, gate, M, N, K,
+                           K, K, K // 32, K // 32, ldc, ldc2, ldr, ldg, rows * K, N * K, rows * (K // 32), N * (K // 32), sC, 0, 0, rps,
+                           batch, mode, act, 0)
+        self._launch("md_gemm_mxfp8", byref(a))
+
+    def _expert_gemm(self, wname, A, C, M, N, K, Bk, E, *, act=0, C2=None, dact_cached=0):
+        """C[e] = act(A[e] @ W[e]) for the expert tensor W [E, K, N] (contraction strided): MXFP8 when `wname` is in self.mx (the caller
+        then passes no C2: inference), else the bf16 launch."""
+        ent = self.mx.entries.get(wname) if self.mx is not None else None
+        if ent is not None:
+            assert ent.batch == E and (ent.N, ent.K) == (N, K) and C2 is None, wname
+            xq = self._mx_quant(A.data_ptr(), K, M, K, batch=E, sSrc=Bk * K, rows_alloc=Bk)
+            self._mx_gemm(xq, ent, C.data_ptr(), M, N, K, ldc=N, act=act, batch=E, sC=Bk * N)
+            if self.mx_log is not None:
+                self.mx_log.append((wname, "mx"))
+            return
+        if self.mx_log is not None:
+            self.mx_log.append((wname, "bf16"))
+        c2 = C2 is not None
+        self._gemm(A=A.data_ptr(), B=self.S[wname].data_ptr(), C=C.data_ptr(), C2=_p(C2), M=M, N=N, K=K, lda=K, ldb=N, ldc=N,
+                   ldc2=N if c2 else 0, sA=Bk * K, sB=K * N, sC=Bk * N, sC2=Bk * N if c2 else 0, batch=E, ksplit=1, a_kcontig=1, b_kcontig=0,
+                   mode=hip.EPI_STORE_BF16, act=act, alpha=1.0, dact_cached=dact_cached)
 
     def lin_dgrad(self, dy, wname, dx, M, N, K, *, lddy=None, mode=hip.EPI_STORE_BF16, act=0, aux=None, res=None,
                   dyoff=0):
@@ -580,6 +640,17 @@ class DiTEngine:
         else:
             self.lin_fwd(xin, pre + ".w1", t.h12, rows, f, d, ldc=2 * f)
             self.lin_fwd(xin, pre + ".w2", t.h12, rows, f, d, ldc=2 * f, ooff=f)
+        ent = self.mx.entries.get(pre + ".w3") if self.mx is not None else None
+        if ent is not None and ent.batch == 1 and (ent.N, ent.K) == (d, f):
+            # a = silu(h1) * h2 leaves the SwiGLU kernel as MXFP8, the form the w3 GEMM reads: the bf16 a is never written
+            t.a = None
+            aq, asc = self.empty(1, rows, f, dtype=torch.uint8), self.empty(1, rows, f // 32, dtype=torch.uint8)
+            self._launch("md_swiglu_fwd_mx", t.h12.data_ptr(), 2 * f, aq.data_ptr(), f, asc.data_ptr(), f // 32, rows, f, prof="swiglu",
+                         nbytes=5.0 * rows * f)
+            if out is None:
+                out = self.empty(rows, d)
+            self.lin_fwd(None, pre + ".w3", out, rows, d, f, mode=hip.EPI_RESIDUAL, res=res, gate=gate, ldg=ldg, rps=rps, C2=C2, xq=(aq, asc))
+            return out
         t.a = self.empty(rows, f)
         self._launch("md_swiglu_fwd", t.h12.data_ptr(), 2 * f, t.a.data_ptr(), f, rows, f, prof="swiglu", nbytes=6.0 * rows * f)
         if out is None:
@@ -960,17 +1031,16 @@ class DiTEngine:
                 self._launch("md_gather_rows", t.xm3.data_ptr(), d, t.rowidx.data_ptr(), t.xin.data_ptr(), d, E * Bk, d)
             else:
                 self._launch("md_moe_gather_compact", t.xm3.data_ptr(), d, t.rowidx_c.data_ptr(), t.xin.data_ptr(), E, rows, Bk, d)
-            t.hpre = self.empty(E, Bk, f)         # the pre-activation -- or, with moe_cache_dact, gelu'(pre-activation): nothing but
-            t.hact = self.empty(E, Bk, f)         # the backward's activation derivative ever reads it (md_gemm_args.dact_cached)
+            # the pre-activation -- or, with moe_cache_dact, gelu'(pre-activation): nothing but the backward's activation derivative ever
+            # reads it (md_gemm_args.dact_cached), so an MXFP8 fc1 (inference only) neither allocates nor writes it
+            mx_fc1 = self.mx is not None and (n + ".mlp.w1") in self.mx.entries
+            t.hpre = None if mx_fc1 else self.empty(E, Bk, f)
+            t.hact = self.empty(E, Bk, f)
             t.hpre_is_dact = 1 if self.moe_cache_dact else 0
-            w1, w2 = self.S[n + ".mlp.w1"], self.S[n + ".mlp.w2"]       # [E, d, f], [E, f, d]
-            self._gemm(A=t.xin.data_ptr(), B=w1.data_ptr(), C=t.hact.data_ptr(), C2=t.hpre.data_ptr(), M=rows, N=f, K=d, lda=d,
-                       ldb=f, ldc=f, ldc2=f, sA=Bk * d, sB=d * f, sC=Bk * f, sC2=Bk * f, batch=E, ksplit=1, a_kcontig=1,
-                       b_kcontig=0, mode=hip.EPI_STORE_BF16, act=hip.ACT_GELU_ERF, alpha=1.0, dact_cached=t.hpre_is_dact)
+            # w1 [E, d, f], w2 [E, f, d]: the contraction dimension is the strided one
+            self._expert_gemm(n + ".mlp.w1", t.xin, t.hact, rows, f, d, Bk, E, act=hip.ACT_GELU_ERF, C2=t.hpre, dact_cached=t.hpre_is_dact)
             t.h2 = self.empty(E, Bk, d)
-            self._gemm(A=t.hact.data_ptr(), B=w2.data_ptr(), C=t.h2.data_ptr(), M=rows, N=d, K=f, lda=f, ldb=d, ldc=d,
-                       sA=Bk * f, sB=f * d, sC=Bk * d, batch=E, ksplit=1, a_kcontig=1, b_kcontig=0, mode=hip.EPI_STORE_BF16,
-                       act=0, alpha=1.0)
+            self._expert_gemm(n + ".mlp.w2", t.hact, t.h2, rows, d, f, Bk, E)
             if t.cap is None:
                 self._launch("md_moe_combine", t.h2.data_ptr(), t.gval.data_ptr(), t.slot.data_ptr(), x2.data_ptr(), gate_mlp, ldm, t.br3.data_ptr(),
                              x3.data_ptr(), B, S, E, k, d)
@@ -1317,6 +1387,11 @@ class DiTEngine:
             Lc, Dc, ydt = y.shape[-2], y.shape[-1], str(y.dtype)
         if self.caption_bias is not None:
             self._check_caption_bias(B, Lc, record_tape or arena or input_tape)
+        if self.mx is not None:
+            if record_tape or arena or input_tape:
+                raise RuntimeError("mx (MXFP8 linears) is inference-only: nothing of it has a backward, so record_tape, arena and "
+                                   "input_tape cannot be combined with it (DESIGN.md 4.23)")
+            self.mx.check_fresh(self.weights_version)
         self._poison_ws()
         grad_pass = self.use_arena and arena and record_tape
         self._record = record_tape or input_tape or self.keep_last_tape

@@ -327,6 +327,25 @@ _sig("md_muon_axpby", P, P, P, F32, F32, I64, P)
 # cross-attention probe (attn_maps.py): head-averaged probabilities of a short key set added into fp32 rows
 _sig("md_attn_probs", POINTER(AttnArgs), P, I64, P, P)
 _sig("md_attn_probs_kbias", POINTER(AttnArgs), P, I64, P, I64, P, P)     # args, kbias, ldb, out, ldo, out_rows
+# MXFP8 (mxfp8.py): the quantisers, the MX-writing SwiGLU and the block-scaled fp8 GEMM
+_sig("md_mx_quant_rows", P, I64, I32, P, I64, P, I64, I64, I64, I32, I64, I64, I64, P)
+_sig("md_swiglu_fwd_mx", P, I64, P, I64, P, I64, I64, I64, P)
+
+
+class GemmMxArgs(Structure):
+    """md_gemm_mx_args."""
+    _fields_ = [("A", c_void_p), ("B", c_void_p), ("scaleA", c_void_p), ("scaleB", c_void_p), ("C", c_void_p), ("C2", c_void_p),
+                ("bias", c_void_p), ("res", c_void_p), ("gate", c_void_p),
+                ("M", c_int64), ("N", c_int64), ("K", c_int64),
+                ("lda", c_int64), ("ldb", c_int64), ("ldsa", c_int64), ("ldsb", c_int64), ("ldc", c_int64), ("ldc2", c_int64),
+                ("ldr", c_int64), ("ldg", c_int64),
+                ("sA", c_int64), ("sB", c_int64), ("sScaleA", c_int64), ("sScaleB", c_int64), ("sC", c_int64), ("sC2", c_int64),
+                ("sBias", c_int64), ("rows_per_sample", c_int64),
+                ("batch", c_int32), ("mode", c_int32), ("act", c_int32), ("reserved", c_int32)]
+
+
+_sig("md_gemm_mxfp8", POINTER(GemmMxArgs), P)
+MX_BLOCK = 32                   # elements per e8m0 scale
 ATTN_KBIAS_MAX_KEYS = 256       # Skv of md_attn_fwd_kbias
 ATTN_PROBS_MAX_KEYS = 128       # Skv of md_attn_probs
 MUON_NORM_PARTS = 16            # MD_MUON_NORM_PARTS
@@ -422,3 +441,25 @@ def gemm(A, B, C, M, N, K, *, lda, ldb, ldc, a_kcontig=True, b_kcontig=True, mod
     if expect is None:
         return rc
     check(rc, "md_gemm_bf16")
+
+
+def mx_quant_rows(src, dst, scales, rows, K, *, ld, ldd, lds, src_kcontig=True, batch=1, sSrc=0, sDst=0, sScale=0, stream=None, expect=0):
+    """md_mx_quant_rows: bf16 [rows, K] (K-contiguous, or K-strided with src_kcontig=False) -> fp8 elements + e8m0 scales.  src / dst /
+    scales: ints (device addresses) or torch tensors.  expect=None returns the code instead of raising."""
+    rc = lib().md_mx_quant_rows(_ptr(src), ld, int(src_kcontig), _ptr(dst), ldd, _ptr(scales), lds, rows, K, batch, sSrc, sDst, sScale,
+                                stream if stream is not None else stream_ptr())
+    if expect is None:
+        return rc
+    check(rc, "md_mx_quant_rows")
+
+
+def gemm_mxfp8(A, scaleA, B, scaleB, C, M, N, K, *, lda, ldb, ldsa, ldsb, ldc, mode=EPI_STORE_BF16, act=ACT_NONE, bias=None, res=None,
+               ldr=0, gate=None, ldg=0, rows_per_sample=0, C2=None, ldc2=0, batch=1, sA=0, sB=0, sScaleA=0, sScaleB=0, sC=0, sC2=0, sBias=0,
+               stream=None, expect=0):
+    """Raw-pointer md_gemm_mxfp8 launch (operands: ints or torch tensors).  expect=None returns the code (NOT_ELIGIBLE: nothing ran)."""
+    a = GemmMxArgs(_ptr(A), _ptr(B), _ptr(scaleA), _ptr(scaleB), _ptr(C), _ptr(C2), _ptr(bias), _ptr(res), _ptr(gate), M, N, K,
+                   lda, ldb, ldsa, ldsb, ldc, ldc2, ldr, ldg, sA, sB, sScaleA, sScaleB, sC, sC2, sBias, rows_per_sample, batch, mode, act, 0)
+    rc = lib().md_gemm_mxfp8(byref(a), stream if stream is not None else stream_ptr())
+    if expect is None:
+        return rc
+    check(rc, "md_gemm_mxfp8")

@@ -265,16 +265,19 @@ class LatentDiffusion(nn.Module):
                          guide_captions: str = "same", init_latents=None, strength: float = 1.0, inpaint_mask=None, resample: int = 1,
                          guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
                          apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, step_cache=None,
-                         attn_maps=None, negative=None, caption_weights=None, negative_weights=None, **kwargs):
+                         attn_maps=None, negative=None, caption_weights=None, negative_weights=None, mxfp8=None, **kwargs):
         """EDM sampler, fp64 state (model.py:231-297): x is unit noise, y the caption embeddings, **kwargs extra forward arguments.
         The docstring of sampling.py defines every argument; sampling.tensor_op_loop (fused=False) is the definition of the loop and
-        sampling.FusedRun the same loop in fused HIP kernels.  Every random draw of a run reads self.randn_like when it is made."""
+        sampling.FusedRun the same loop in fused HIP kernels.  Every random draw of a run reads self.randn_like when it is made.
+        mxfp8=True selects mxfp8's DEFAULT target set, which is currently empty (every class measured slower than bf16):
+        it quantises nothing and runs the plain bf16 launches.  Pass MXWeights(self.dit, targets=mxfp8.ALL_TARGETS) to run MXFP8."""
         req = sampling.Request(sampler=sampler, guidance_interval=guidance_interval, guide=guide, guide_captions=guide_captions,
                                init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, resample=resample,
                                guidance_mode=guidance_mode, guidance_rescale=guidance_rescale, apg_eta=apg_eta,
                                apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, measurement=measurement,
                                measurement_scale=measurement_scale, guidance_loss=guidance_loss, step_cache=step_cache,
-                               attn_maps=attn_maps, negative=negative, caption_weights=caption_weights, negative_weights=negative_weights)
+                               attn_maps=attn_maps, negative=negative, caption_weights=caption_weights, negative_weights=negative_weights,
+                               mxfp8=mxfp8)
         return sampling.sample(self, x, y, steps, cfg, fused, cond_cache, req, kwargs)
 
     @torch.no_grad()
@@ -285,7 +288,7 @@ class LatentDiffusion(nn.Module):
                  guidance_mode: str = "cfg", guidance_rescale: float = 0.0, apg_eta: float = 0.0, apg_norm_threshold=None,
                  apg_momentum: float = 0.0, measurement=None, measurement_scale: float = 1.0, guidance_loss=None, step_cache=None,
                  attn_maps=None, negative_prompt: Optional[list] = None, negative_tokenized_prompts=None, negative_attention_mask=None,
-                 caption_weights=None, negative_weights=None, mask_padding: bool = False, **kwargs):
+                 caption_weights=None, negative_weights=None, mask_padding: bool = False, mxfp8=None, **kwargs):
         """tokenise -> text encoder -> EDM sampler on the HIP DiT -> VAE decode (model.py:299-353).  cond_cache, sampler,
         guidance_interval, guide and guide_captions: as in edm_sampler_loop (with a guide, guidance_scale is the autoguidance weight).
         init_latents, strength, inpaint_mask and resample: image-to-image and inpainting as in edm_sampler_loop; the seeded draw below is
@@ -304,13 +307,16 @@ class LatentDiffusion(nn.Module):
         two captions in every cross-attention, as in edm_sampler_loop.  mask_padding=True multiplies them (ones when None) by the
         tokenizer's attention_mask -- and the negative half's by the negative prompt's --, which removes the padding positions from the
         cross-attention; it raises when a mask is not available.  The network was trained without a caption mask: this is a tool, not
-        a quality claim.  The weights act on the cross-attention only; the text encoder and the pooled caption stay as they are."""
+        a quality claim.  The weights act on the cross-attention only; the text encoder and the pooled caption stay as they are.
+        mxfp8: None, True or an mxfp8.MXWeights -- the block linears of the main network in block-scaled fp8, as in edm_sampler_loop
+        (DESIGN.md 4.23).  True selects the default target set, which is currently empty: it quantises nothing and runs the plain
+        bf16 launches; MXWeights(self.dit, targets=mxfp8.ALL_TARGETS) runs MXFP8."""
         req = sampling.Request(sampler=sampler, guidance_interval=guidance_interval, guide=guide, guide_captions=guide_captions,
                                init_latents=init_latents, strength=strength, inpaint_mask=inpaint_mask, resample=resample,
                                guidance_mode=guidance_mode, guidance_rescale=guidance_rescale, apg_eta=apg_eta,
                                apg_norm_threshold=apg_norm_threshold, apg_momentum=apg_momentum, measurement=measurement,
                                measurement_scale=measurement_scale, guidance_loss=guidance_loss, step_cache=step_cache,
-                               attn_maps=attn_maps, caption_weights=caption_weights, negative_weights=negative_weights)
+                               attn_maps=attn_maps, caption_weights=caption_weights, negative_weights=negative_weights, mxfp8=mxfp8)
         has_negative = bool(negative_prompt) or negative_tokenized_prompts is not None
         # refuse before tokenising; edm_sampler_loop checks again with the shapes of the state and the captions
         req.check(self, None, guidance_scale, has_negative=has_negative, will_weight=bool(mask_padding))

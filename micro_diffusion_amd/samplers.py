@@ -304,6 +304,25 @@ def check_attn_maps(attn_maps=None, config=None) -> bool:
     return True
 
 
+def check_mxfp8(mxfp8=None, measurement=None, guidance_loss=None) -> bool:
+    """Refuse, before anything is quantised, launched or allocated, an MXFP8 request the sampler cannot run; True when
+    the run quantises.  mxfp8: None, True (the sampler quantises the main network's default targets for this run) or an
+    mxfp8.MXWeights.  ValueError for anything else (False included: leave the argument out instead) and for measurement= /
+    guidance_loss=, whose backward through the network has no MXFP8 form.  Everything else composes: every solver, churn, the guidance
+    interval and modes, cond_cache, step_cache, the editing options, attn_maps and prompt control; with guide= only the main network
+    is quantised."""
+    if mxfp8 is None:
+        return False
+    if mxfp8 is not True:
+        if mxfp8 is False or not (isinstance(getattr(mxfp8, "entries", None), dict) and callable(getattr(mxfp8, "check_fresh", None))
+                                  and callable(getattr(mxfp8, "requantize", None))):
+            raise ValueError(f"mxfp8 must be None, True or an mxfp8.MXWeights, got {mxfp8!r}")
+    if measurement is not None or guidance_loss is not None:
+        raise ValueError("mxfp8 with measurement= / guidance_loss= is not defined: the guided step needs a backward through the network, "
+                         "and the MXFP8 linears are forward-only (DESIGN.md 4.23)")
+    return True
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Prompt control (DESIGN.md 4.22): a negative prompt as the second operand of classifier-free guidance, and per-position caption
 # weights w_j >= 0 that enter every cross-attention as the additive bias ln w_j on the logits: P_j = w_j e^{s_j} / sum_i w_i e^{s_i}

@@ -75,6 +75,17 @@ churn, guidance_interval, the guidance modes, cond_cache, the editing options, s
 probabilities the run used: exactly 0 at a removed position); refused (ValueError): any of the three with `guide`, weights with
 `measurement` / `guidance_loss` (the attention backward does not know the bias; `negative` alone composes with them).  None: the
 launches and bits of a run without the arguments.
+
+`mxfp8`: None, True, or an mxfp8.MXWeights.  The targeted block linears of the main network run in block-scaled fp8
+(MXFP8: their input is quantised, md_gemm_mxfp8 multiplies) for the run: the MXWeights -- True makes them from the default targets
+for this run -- are armed as engine.mx and what the attribute held before is put back when the run ends, an error included.  In both
+loops; composes with every solver, churn, guidance_interval, the guidance modes, cond_cache (the caption side stays bf16, so the cache
+is bit-identical on or off), step_cache, the editing options, attn_maps and prompt control; with `guide` only the main network is
+quantised.  Refused (ValueError) with `measurement` / `guidance_loss`, which need a backward; MXWeights quantised at another weight
+version raise.  None: the launches and bits of a run without the argument.
+NOTE: the default target set is currently EMPTY -- every class of linear measured slower in MXFP8 than in bf16 (mxfp8.DEFAULT_EXCLUDED,
+DESIGN.md 4.23) -- so `mxfp8=True` quantises nothing and the run issues the plain bf16 launches; to run MXFP8 pass
+`MXWeights(model.dit, targets=mxfp8.ALL_TARGETS)` or a pattern of your own.
 """
 from __future__ import annotations
 
@@ -143,6 +154,28 @@ def caption_bias(dit, bias):
         engine.caption_bias = before
 
 
+@contextmanager
+def mx_armed(dit, mxfp8):
+    """Context of a run with mxfp8=: the MXWeights -- made here from the main network's default targets when the
+    argument is True -- are the main network's engine.mx inside, and what the attribute held before afterwards, whatever ended the
+    run.  MXWeights quantised at another weight version raise before anything is armed.  None: nothing is touched."""
+    if mxfp8 is None:
+        yield
+        return
+    dit._ensure_flat()
+    dit.refresh_shadow()
+    if mxfp8 is True:
+        from .mxfp8 import MXWeights
+        mxfp8 = MXWeights(dit)
+    engine = dit.engine
+    mxfp8.check_fresh(engine.weights_version)
+    before, engine.mx = engine.mx, mxfp8
+    try:
+        yield
+    finally:
+        engine.mx = before
+
+
 def negative_captions(y, negative):
     """negative as the second half of [y; negative]: y's dtype and device, a leading 1 broadcast over the batch."""
     return negative.detach().to(device=y.device, dtype=y.dtype).expand_as(y)
@@ -175,6 +208,7 @@ class Request:
     negative: Any = None
     caption_weights: Any = None
     negative_weights: Any = None
+    mxfp8: Any = None
 
     def check(self, model, shape, cfg, extra=(), y_shape=None, has_negative=False, will_weight=False):
         """Refuse, before anything is tokenised, launched, allocated or drawn, a request that is not defined (the samplers.check_*
@@ -186,6 +220,7 @@ class Request:
         (else None)."""
         samplers.check_sampler(self.sampler, model.edm_config.S_churn)
         caching = samplers.check_step_cache(self.step_cache, self.guide, self.measurement, self.guidance_loss)
+        samplers.check_mxfp8(self.mxfp8, self.measurement, self.guidance_loss)
         guided_by = samplers.check_measurement(shape, self.measurement, self.measurement_scale, self.guidance_loss)
         if guided_by:
             for bad, what in ((self.guide is not None, "a guide network (autoguidance)"),
@@ -709,7 +744,8 @@ def sample(model, x, y, steps, cfg, fused, cond_cache, req: Request, kwargs):
     if req.caption_weights is not None or req.negative_weights is not None:
         doubled = any(samplers.is_guided(s, cfg, interval) for s in plan.sigmas)       # (no guide: a guided evaluation is a doubled one)
         bias = samplers.caption_bias_buffer(req.caption_weights, req.negative_weights, x.shape[0], y.shape[-2], doubled, x.device)
-    with frozen_network(model.dit) if guided_by else nullcontext(), recording(model.dit, am, x), caption_bias(model.dit, bias):
+    with frozen_network(model.dit) if guided_by else nullcontext(), recording(model.dit, am, x), caption_bias(model.dit, bias), \
+            mx_armed(model.dit, req.mxfp8):
         if fused:
             guidance = (req.measurement, req.guidance_loss, zeta) if guided_by else None
             return FusedRun(model, x, y, plan, cfg, cond_cache, interval, guide, guide_null, edit, gmode, guidance, req.step_cache, am,
