@@ -454,8 +454,8 @@ int md_edm_solver_update_tok(const double* x_in, const void* tok_bf16, double* h
  *     kernels run, with the same fp32 combine (one fma), fp32 preconditioning and fp64 state.
  *   - The token forms take the 16-byte vector path only when C*p*p is a multiple of 8 and BOTH token pointers are 16-byte aligned;
  *     otherwise the whole launch goes element by element.  A misaligned pointer is never read with a vector load.
- *   - A null pointer (the guide's included), a non-positive size, H % p or W % p non-zero, or t_in <= 0 returns MD_BAD_ARG and launches
- *     nothing.
+ *   - A null pointer (the guide's included), a non-positive size, H % p or W % p non-zero, or a t_in that is not positive (NaN
+ *     included) returns MD_BAD_ARG and launches nothing.
  *   - Aliasing as above: x_next may alias x_in / x_hat; the two network outputs are only read and may alias each other. */
 int md_edm_heun_update_guide(const double* x_hat, const double* x_in, const float* F, const float* F_guide, double* d_cur, double* x_next,
                              int64_t n, float cfg, double t_in, double t_hat, double t_next, float sigma_data, int32_t second,

@@ -9,6 +9,7 @@
 //                       mean (model.py:177,199-210) and its gradient w.r.t. the kept-token network output.
 #include "md_common.h"
 #include "sampler_math.h"
+#include "sampler_tok.h"
 #include "../../include/microdit_hip.h"
 #include <cmath>
 
@@ -145,6 +146,8 @@ __global__ __launch_bounds__(64) void edm_loss_finish_kernel(const float* loss_p
     }
 }
 
+// Grid of a 256-thread grid-stride launch over `work` items (tests/test_kernel_geometry_cpu.py reads the cap here; guide.hip keeps the
+// same helper).
 inline int egrid(int64_t work) {
     int64_t g = (work + 255) / 256;
     if (g > 8192) g = 8192;
@@ -153,14 +156,19 @@ inline int egrid(int64_t work) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Sampler (model.py:231-297): the arithmetic around each network evaluation of the Heun loop as two fused kernels, with the
+// Sampler (model.py:231-297): the arithmetic around each network evaluation of the sampling loop as two fused kernels, with the
 // reference's precisions: fp64 sampler state, fp32 preconditioning (model.py:144-179) and fp32 classifier-free-guidance
 // combine (dit.py:542-550).
 //   sampler_input : net_in = float(c_in(sigma) * float(x)), written once, or twice when the batch is doubled for guidance
-//   heun_update   : F = Fu + cfg * (Fc - Fu);  D = c_skip * float(x_in) + c_out * F;  d = (x_in - D) / sigma;
-//                   first half-step : d_cur = d, x_next = x_hat + (t_next - t_hat) * d
-//                   second half-step: x_next = x_hat + (t_next - t_hat) * (0.5 d_cur + 0.5 d)
-//   sampler_patchify / heun_update_tok: the same two, writing bf16 patch rows / reading the bf16 token output directly
+//   update        : x_next = Step(x_in, D), D = Source(x_in, network output): one kernel template per layout (update_kernel: fp32 images,
+//                   one element per item; update_tok_kernel: bf16 token rows, one 8-element segment per item) behind all twelve
+//                   md_edm_{heun,solver}_update[_guide|_coef][_tok] entry points.
+//       Source cfg_source : F = Fu + cfg * (Fc - Fu) (Fu NULL: F = Fc);  D = c_skip * float(x_in) + c_out * F
+//              coef_source: D = alpha_b * (c_skip * float(x_in) + c_out * Fc) + gamma_b * M                     (guidance modes)
+//       Step   heun_step  : d = (x_in - D) / sigma;  first half-step : d_cur = d, x_next = x_hat + (t_next - t_hat) * d
+//                                                    second half-step: x_next = x_hat + (t_next - t_hat) * (0.5 d_cur + 0.5 d)
+//              solver_step: x_next = a * x_in + b * (c1 * D - c2 * hist);  hist = D                      (Euler, DPM-Solver++(2M))
+//   sampler_patchify: sampler_input writing bf16 patch rows
 // ---------------------------------------------------------------------------------------------------------------------
 // The per-element arithmetic, shared by the image-space and the token-space kernels below (and by guide.hip): sampler_math.h.
 // The combine of the guidance modes, in the space of the denoised value: D = alpha_b * D_c + gamma_b * M with D_c the
@@ -178,21 +186,12 @@ __device__ __forceinline__ double heun_from_denoised(double xi, double xh, doubl
     if (!second) return fma(t_next - t_hat, d, xh);
     return fma(t_next - t_hat, fma(0.5, d, 0.5 * d_prev), xh);
 }
-__device__ __forceinline__ double heun_element(double xi, double xh, float f, float c_skip, float c_out, double t_in, double t_hat,
-                                               double t_next, int second, double d_prev, double& d) {
-    return heun_from_denoised(xi, xh, sampler_denoised(xi, f, c_skip, c_out), t_in, t_hat, t_next, second, d_prev, d);
-}
 
 // One step of a linear multistep solver on the denoised value (Euler, DPM-Solver++(2M)): x_next = a * x_in + b * (c1 * den - c2 * hist);
 // den goes back to the caller, which stores it as the next step's hist.  hist is 0.0 when c2 == 0 (the callers do not load it then),
 // so c1 * den - c2 * hist is c1 * den exactly and a stale or non-finite history buffer never reaches x_next.
 __device__ __forceinline__ double solver_from_denoised(double xi, double den, double a, double b, double c1, double c2, double hist) {
     return fma(a, xi, b * fma(c1, den, -(c2 * hist)));
-}
-__device__ __forceinline__ double solver_element(double xi, float f, float c_skip, float c_out, double a, double b, double c1, double c2,
-                                                 double hist, double& den) {
-    den = sampler_denoised(xi, f, c_skip, c_out);
-    return solver_from_denoised(xi, den, a, b, c1, c2, hist);
 }
 
 __global__ __launch_bounds__(256) void sampler_input_kernel(const double* x, float* out, int64_t n, float sigma, float sigma_data, int dup) {
@@ -204,65 +203,9 @@ __global__ __launch_bounds__(256) void sampler_input_kernel(const double* x, flo
     }
 }
 
-// The second operand of the guidance combine is a pointer of its own (Fu / tok_u; NULL: no combine): the unconditional half of a
-// doubled batch (F + n, the has_uncond entry points) or the output of a second, weaker network (the _guide entry points).  One set
-// of kernels serves both, so the two give the same bits by construction.
-__global__ __launch_bounds__(256) void heun_update_kernel(const double* x_hat, const double* x_in, const float* F, const float* Fu,
-                                                          double* d_cur, double* x_next, int64_t n, float cfg, double t_in, double t_hat,
-                                                          double t_next, float sigma_data, int second) {
-    float c_skip, c_out;
-    heun_coef(t_in, sigma_data, c_skip, c_out);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double xi = x_in[i];
-        float f = F[i];
-        if (Fu) f = cfg_combine(f, Fu[i], cfg);
-        double d;
-        x_next[i] = heun_element(xi, x_hat[i], f, c_skip, c_out, t_in, t_hat, t_next, second, second ? d_cur[i] : 0.0, d);
-        if (!second) d_cur[i] = d;
-    }
-}
-
-__global__ __launch_bounds__(256) void solver_update_kernel(const double* x_in, const float* F, const float* Fu, double* hist, double* x_next,
-                                                            int64_t n, float cfg, double t_in, float sigma_data, double a, double b,
-                                                            double c1, double c2) {
-    float c_skip, c_out;
-    heun_coef(t_in, sigma_data, c_skip, c_out);
-    const bool use_hist = c2 != 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double xi = x_in[i];
-        float f = F[i];
-        if (Fu) f = cfg_combine(f, Fu[i], cfg);
-        double den;
-        x_next[i] = solver_element(xi, f, c_skip, c_out, a, b, c1, c2, use_hist ? hist[i] : 0.0, den);
-        hist[i] = den;
-    }
-}
-
 // x_hat = x + coef * noise: the stochastic churn of model.py:258, coef = sqrt(t_hat^2 - t_cur^2) * S_noise from the host.
 __global__ __launch_bounds__(256) void churn_kernel(const double* x, const double* noise, double* x_hat, int64_t n, double coef) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x_hat[i] = fma(coef, noise[i], x[i]);
-}
-
-// Token-space forms of the two kernels above: the network reads bf16 patch rows and writes bf16 token rows, so the fp32 images
-// md_edm_sampler_input -> md_patchify and md_unpatchify -> md_edm_heun_update pass through memory are skipped; the fp64 sampler state
-// is the only image-shaped tensor.  A work item is one 8-element (16-byte) segment of one token row; items are ordered
-// (b, ti, segment, tj) with tj fastest, so the lanes of a wave walk along w: the fp64 rows are read / written along w and every
-// lane moves its bf16 segment as one 16-byte piece (VEC; rows that are no multiple of 8 wide, or a misaligned base, go element
-// by element).
-struct tok_item {
-    int64_t b, row;     // sample, token row b * T + ti * gw + tj
-    int ti, tj, e0;     // grid position, first element of the segment
-};
-__device__ __forceinline__ tok_item tok_item_of(int64_t i, int gh, int gw, int nseg) {
-    tok_item t;
-    t.tj = (int)(i % gw);
-    const int64_t r = i / gw;
-    t.e0 = (int)(r % nseg) * 8;
-    const int64_t bt = r / nseg;
-    t.ti = (int)(bt % gh);
-    t.b = bt / gh;
-    t.row = (t.b * gh + t.ti) * gw + t.tj;
-    return t;
 }
 
 // patches[row, c*p*p + ph*p + pw] = bf16(c_in * float(x[b, c, ti*p+ph, tj*p+pw]));  rows [B*T, 2*B*T) repeat them when dup
@@ -295,152 +238,189 @@ __global__ __launch_bounds__(256) void sampler_patchify_kernel(const double* x, 
     }
 }
 
-// F[b, c, ti*p+ph, tj*p+pw] = tok[row, (ph*p + pw)*C + c] (the second operand: the same row of tok_u), then heun_element on that pixel
-template <bool VEC>
-__global__ __launch_bounds__(256) void heun_update_tok_kernel(const double* x_hat, const double* x_in, const bf16* tok, const bf16* tok_u,
-                                                              double* d_cur, double* x_next, int64_t B, int C, int H, int W, int p,
-                                                              float cfg, double t_in, double t_hat, double t_next, float sigma_data,
-                                                              int second) {
+// The update kernels: x_next = Step(x_in, D) with D = Source(x_in, network output).  Source and Step are small structs passed by value;
+// all arithmetic goes through sampler_math.h and the functions above, so every form of a step gives the same bits by construction.
+// FT is the type of the network output: float (image layout) or bf16 (token rows; a token row holds the elements of its patch in
+// (ph, pw, c) order, tok_pixel).  In the token layout a Source keeps what it loads for one item in its `segment`.
+__device__ __forceinline__ float f32_of(float v) { return v; }
+__device__ __forceinline__ float f32_of(bf16 v) { return bf2f(v); }
+
+// The guidance combine of two network outputs.  The second operand is a pointer of its own (NULL: no combine): the unconditional half
+// of a doubled batch (fc + n, the has_uncond entry points) or the output of a second, weaker network (the _guide entry points).
+template <typename FT>
+struct cfg_source {
+    const FT *fc, *fu;
+    float cfg;
+    struct segment {
+        const FT *pc, *pu;
+        U128 vc, vu;
+    };
+    bool aligned() const { return aligned16(fc) && aligned16(fu); }
+    __device__ __forceinline__ double flat(int64_t i, double xi, float c_skip, float c_out) const {
+        float f = f32_of(fc[i]);
+        if (fu) f = cfg_combine(f, f32_of(fu[i]), cfg);
+        return sampler_denoised(xi, f, c_skip, c_out);
+    }
+    template <bool VEC>
+    __device__ __forceinline__ void load_segment(segment& s, const tok_item& t, int pv) const {
+        const int64_t off = t.row * pv + t.e0;
+        s.pc = fc + off;
+        s.pu = fu ? fu + off : s.pc;
+        if (VEC) {
+            s.vc.h = ld_bf16x8(s.pc);
+            if (fu) s.vu.h = ld_bf16x8(s.pu);
+        }
+    }
+    __device__ __forceinline__ void load_pixel(segment&, int, int64_t) const {}
+    template <bool VEC>
+    __device__ __forceinline__ double denoised(const segment& s, int j, double xi, float c_skip, float c_out) const {
+        float f = bf2f(VEC ? s.vc.e[j] : s.pc[j]);
+        if (fu) f = cfg_combine(f, bf2f(VEC ? s.vu.e[j] : s.pu[j]), cfg);
+        return sampler_denoised(xi, f, c_skip, c_out);
+    }
+};
+
+// The coefficient form of the guidance modes: M and the per-sample (alpha_b, gamma_b) of md_guidance_prepare, both in the layout of the
+// state whatever the layout of fc.  per: elements of one sample (the image layout finds its sample with it).
+template <typename FT>
+struct coef_source {
+    const FT* fc;
+    const float *M, *coef;
+    int64_t per;
+    struct segment {
+        const FT* pc;
+        U128 vc;
+        float alpha, gamma, m[8];
+    };
+    bool aligned() const { return aligned16(fc); }
+    __device__ __forceinline__ double flat(int64_t i, double xi, float c_skip, float c_out) const {
+        const int64_t b = i / per;
+        return sampler_guided(xi, f32_of(fc[i]), M[i], c_skip, c_out, coef[b * 2], coef[b * 2 + 1]);
+    }
+    template <bool VEC>
+    __device__ __forceinline__ void load_segment(segment& s, const tok_item& t, int pv) const {
+        s.pc = fc + t.row * pv + t.e0;
+        s.alpha = coef[t.b * 2], s.gamma = coef[t.b * 2 + 1];
+        if (VEC) s.vc.h = ld_bf16x8(s.pc);
+    }
+    __device__ __forceinline__ void load_pixel(segment& s, int j, int64_t pix) const { s.m[j] = M[pix]; }
+    template <bool VEC>
+    __device__ __forceinline__ double denoised(const segment& s, int j, double xi, float c_skip, float c_out) const {
+        return sampler_guided(xi, bf2f(VEC ? s.vc.e[j] : s.pc[j]), s.m[j], c_skip, c_out, s.alpha, s.gamma);
+    }
+};
+
+// A Step loads its per-pixel state (load) and stores x_next and its own output (apply).  d_cur is read only by the second half-step
+// and hist only when c2 != 0, so a stale or non-finite buffer never reaches x_next.
+struct heun_step {
+    const double* x_hat;
+    double* d_cur;
+    double t_hat, t_next;
+    int second;
+    struct state {
+        double xh, dp;
+    };
+    __device__ __forceinline__ state load(int64_t i) const { return {x_hat[i], second ? d_cur[i] : 0.0}; }
+    __device__ __forceinline__ void apply(int64_t i, double xi, double D, const state& s, double t_in, double* x_next) const {
+        double d;
+        x_next[i] = heun_from_denoised(xi, s.xh, D, t_in, t_hat, t_next, second, s.dp, d);
+        if (!second) d_cur[i] = d;
+    }
+};
+
+struct solver_step {
+    double* hist;
+    double a, b, c1, c2;
+    struct state {
+        double hp;
+    };
+    __device__ __forceinline__ state load(int64_t i) const { return {c2 != 0.0 ? hist[i] : 0.0}; }
+    __device__ __forceinline__ void apply(int64_t i, double xi, double D, const state& s, double, double* x_next) const {
+        x_next[i] = solver_from_denoised(xi, D, a, b, c1, c2, s.hp);
+        hist[i] = D;
+    }
+};
+
+// Per item, every load comes before the first store, so x_next may alias x_in or x_hat.
+template <typename Source, typename Step>
+__global__ __launch_bounds__(256) void update_kernel(Source src, Step step, const double* x_in, double* x_next, int64_t n, double t_in,
+                                                     float sigma_data) {
     float c_skip, c_out;
     heun_coef(t_in, sigma_data, c_skip, c_out);
-    const int gh = H / p, gw = W / p, pv = C * p * p, nseg = (pv + 7) / 8;
-    const int64_t rows = B * gh * gw, total = rows * nseg;
-    const bool has_uncond = tok_u != nullptr;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double xi = x_in[i];
+        const double D = src.flat(i, xi, c_skip, c_out);
+        const typename Step::state s = step.load(i);
+        step.apply(i, xi, D, s, t_in, x_next);
+    }
+}
+
+// (The geometry is formed here from the five sizes, in scalar registers: handed over as a tok_geometry argument, the solver
+// instantiations took 2-3 more VGPRs, one occupancy step.)
+template <bool VEC, typename Source, typename Step>
+__global__ __launch_bounds__(256) void update_tok_kernel(Source src, Step step, const double* x_in, double* x_next, int64_t B, int C, int H,
+                                                         int W, int p, double t_in, float sigma_data) {
+    const tok_geometry g = tok_geometry_of(B, C, H, W, p);
+    float c_skip, c_out;
+    heun_coef(t_in, sigma_data, c_skip, c_out);
+    const int64_t total = g.items();
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const tok_item t = tok_item_of(i, gh, gw, nseg);
-        const int64_t off = t.row * pv + t.e0;
-        const bf16* fc = tok + off;
-        const bf16* fu = has_uncond ? tok_u + off : fc;
-        U128 vc, vu;
-        if (VEC) {
-            vc.h = ld_bf16x8(fc);
-            if (has_uncond) vu.h = ld_bf16x8(fu);
-        }
+        const tok_item t = tok_item_of(i, g.gh, g.gw, g.nseg);
+        typename Source::segment seg;
+        src.template load_segment<VEC>(seg, t, g.pv);
         int64_t pix[8];
-        double xi[8], xh[8], dp[8];
+        double xi[8];
+        typename Step::state s[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {          // every load of the item before its first store (x_next may alias x_in / x_hat)
+        for (int j = 0; j < 8; ++j) {          // every load of the item before its first store
             const int e = t.e0 + j;
-            if (!VEC && e >= pv) break;
-            const int c = e % C, pw = (e / C) % p, ph = e / (C * p);
-            pix[j] = ((t.b * C + c) * H + t.ti * p + ph) * W + t.tj * p + pw;
+            if (!VEC && e >= g.pv) break;
+            pix[j] = tok_pixel(t, e, g.C, g.H, g.W, g.p);
             xi[j] = x_in[pix[j]];
-            xh[j] = x_hat[pix[j]];
-            dp[j] = second ? d_cur[pix[j]] : 0.0;
+            s[j] = step.load(pix[j]);
+            src.load_pixel(seg, j, pix[j]);
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            if (!VEC && t.e0 + j >= pv) break;
-            float f = bf2f(VEC ? vc.e[j] : fc[j]);
-            if (has_uncond) f = cfg_combine(f, bf2f(VEC ? vu.e[j] : fu[j]), cfg);
-            double d;
-            x_next[pix[j]] = heun_element(xi[j], xh[j], f, c_skip, c_out, t_in, t_hat, t_next, second, dp[j], d);
-            if (!second) d_cur[pix[j]] = d;
+            if (!VEC && t.e0 + j >= g.pv) break;
+            step.apply(pix[j], xi[j], src.template denoised<VEC>(seg, j, xi[j], c_skip, c_out), s[j], t_in, x_next);
         }
     }
 }
 
-// The token-space form of solver_update_kernel: F as in heun_update_tok_kernel, then solver_element on that pixel
-template <bool VEC>
-__global__ __launch_bounds__(256) void solver_update_tok_kernel(const double* x_in, const bf16* tok, const bf16* tok_u, double* hist, double* x_next,
-                                                                int64_t B, int C, int H, int W, int p, float cfg, double t_in,
-                                                                float sigma_data, double a, double b, double c1, double c2) {
-    float c_skip, c_out;
-    heun_coef(t_in, sigma_data, c_skip, c_out);
-    const bool use_hist = c2 != 0.0;
-    const int gh = H / p, gw = W / p, pv = C * p * p, nseg = (pv + 7) / 8;
-    const int64_t rows = B * gh * gw, total = rows * nseg;
-    const bool has_uncond = tok_u != nullptr;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const tok_item t = tok_item_of(i, gh, gw, nseg);
-        const int64_t off = t.row * pv + t.e0;
-        const bf16* fc = tok + off;
-        const bf16* fu = has_uncond ? tok_u + off : fc;
-        U128 vc, vu;
-        if (VEC) {
-            vc.h = ld_bf16x8(fc);
-            if (has_uncond) vu.h = ld_bf16x8(fu);
-        }
-        int64_t pix[8];
-        double xi[8], hp[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {          // every load of the item before its first store (x_next may alias x_in)
-            const int e = t.e0 + j;
-            if (!VEC && e >= pv) break;
-            const int c = e % C, pw = (e / C) % p, ph = e / (C * p);
-            pix[j] = ((t.b * C + c) * H + t.ti * p + ph) * W + t.tj * p + pw;
-            xi[j] = x_in[pix[j]];
-            hp[j] = use_hist ? hist[pix[j]] : 0.0;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (!VEC && t.e0 + j >= pv) break;
-            float f = bf2f(VEC ? vc.e[j] : fc[j]);
-            if (has_uncond) f = cfg_combine(f, bf2f(VEC ? vu.e[j] : fu[j]), cfg);
-            double den;
-            x_next[pix[j]] = solver_element(xi[j], f, c_skip, c_out, a, b, c1, c2, hp[j], den);
-            hist[pix[j]] = den;
-        }
-    }
-}
-
-inline bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
-
-// The launches behind the sampler update entry points (arguments checked by the callers).  Fu / tok_u: the second operand of the
-// guidance combine, NULL for none.  The token forms take the 16-byte path only when the row width is a multiple of 8 and BOTH token
-// pointers are 16-byte aligned: one misaligned pointer sends the whole launch element by element, so it is never read as a vector.
-inline int64_t uncond_offset(int64_t B, int C, int H, int W, int p) { return B * (H / p) * (W / p) * C * p * p; }
-
-inline int launch_heun_update(const double* x_hat, const double* x_in, const float* F, const float* Fu, double* d_cur, double* x_next,
-                              int64_t n, float cfg, double t_in, double t_hat, double t_next, float sigma_data, int second, hipStream_t st) {
-    hipLaunchKernelGGL(heun_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_hat, x_in, F, Fu, d_cur, x_next, n, cfg, t_in, t_hat, t_next,
-                       sigma_data, second);
+// One launcher per layout (arguments checked by the callers).  The token form takes the 16-byte path only when the row width is a
+// multiple of 8 and EVERY token pointer of the source is 16-byte aligned: one misaligned pointer sends the whole launch element by
+// element, so it is never read as a vector.
+template <typename Source, typename Step>
+int launch_update(Source src, Step step, const double* x_in, double* x_next, int64_t n, double t_in, float sigma_data, hipStream_t st) {
+    hipLaunchKernelGGL((update_kernel<Source, Step>), dim3(egrid(n)), dim3(256), 0, st, src, step, x_in, x_next, n, t_in, sigma_data);
     MD_LAUNCH_CHECK();
     return 0;
 }
 
-inline int launch_solver_update(const double* x_in, const float* F, const float* Fu, double* hist, double* x_next, int64_t n, float cfg,
-                                double t_in, float sigma_data, double a, double b, double c1, double c2, hipStream_t st) {
-    hipLaunchKernelGGL(solver_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_in, F, Fu, hist, x_next, n, cfg, t_in, sigma_data, a, b, c1,
-                       c2);
-    MD_LAUNCH_CHECK();
-    return 0;
-}
-
-inline int launch_heun_update_tok(const double* x_hat, const double* x_in, const bf16* tok, const bf16* tok_u, double* d_cur, double* x_next,
-                                  int64_t B, int C, int H, int W, int p, float cfg, double t_in, double t_hat, double t_next,
-                                  float sigma_data, int second, hipStream_t st) {
-    const int pv = C * p * p;
-    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
-    if (pv % 8 == 0 && aligned16(tok) && aligned16(tok_u))
-        hipLaunchKernelGGL(heun_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, tok, tok_u, d_cur, x_next, B, C,
-                           H, W, p, cfg, t_in, t_hat, t_next, sigma_data, second);
+template <typename Source, typename Step>
+int launch_update_tok(Source src, Step step, const double* x_in, double* x_next, const tok_geometry& g, double t_in, float sigma_data,
+                      hipStream_t st) {
+    if (g.pv % 8 == 0 && src.aligned())
+        hipLaunchKernelGGL((update_tok_kernel<true, Source, Step>), dim3(egrid(g.items())), dim3(256), 0, st, src, step, x_in, x_next, g.B,
+                           g.C, g.H, g.W, g.p, t_in, sigma_data);
     else
-        hipLaunchKernelGGL(heun_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, tok, tok_u, d_cur, x_next, B, C,
-                           H, W, p, cfg, t_in, t_hat, t_next, sigma_data, second);
+        hipLaunchKernelGGL((update_tok_kernel<false, Source, Step>), dim3(egrid(g.items())), dim3(256), 0, st, src, step, x_in, x_next, g.B,
+                           g.C, g.H, g.W, g.p, t_in, sigma_data);
     MD_LAUNCH_CHECK();
     return 0;
 }
 
-inline int launch_solver_update_tok(const double* x_in, const bf16* tok, const bf16* tok_u, double* hist, double* x_next, int64_t B, int C,
-                                    int H, int W, int p, float cfg, double t_in, float sigma_data, double a, double b, double c1, double c2,
-                                    hipStream_t st) {
-    const int pv = C * p * p;
-    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
-    if (pv % 8 == 0 && aligned16(tok) && aligned16(tok_u))
-        hipLaunchKernelGGL(solver_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_in, tok, tok_u, hist, x_next, B, C, H, W,
-                           p, cfg, t_in, sigma_data, a, b, c1, c2);
-    else
-        hipLaunchKernelGGL(solver_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_in, tok, tok_u, hist, x_next, B, C, H, W,
-                           p, cfg, t_in, sigma_data, a, b, c1, c2);
-    MD_LAUNCH_CHECK();
-    return 0;
+// The second operand of the has_uncond entry points: the unconditional half of the doubled batch, or none.
+template <typename FT>
+cfg_source<FT> cfg_pair(const void* F, int64_t n, float cfg, int has_uncond) {
+    return {(const FT*)F, has_uncond ? (const FT*)F + n : nullptr, cfg};
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Guidance modes: CFG rescale and adaptive projected guidance need per-sample reductions over the denoised prediction,
 // so a guided evaluation is two launches: guidance_prepare_kernel (M, the five moments, alpha_b and gamma_b) and one of the _coef update
-// kernels, which are the update kernels above with D = alpha_b * D_c + gamma_b * M in place of the cfg combine.
+// entry points, which are the update kernels above with coef_source (D = alpha_b * D_c + gamma_b * M) in place of the cfg combine.
 // ---------------------------------------------------------------------------------------------------------------------
 struct guidance_args {
     int mode, first, has_r;             // MD_GUIDANCE_*; first: M holds nothing yet (not read); has_r: the norm threshold r is set
@@ -522,115 +502,6 @@ __global__ __launch_bounds__(256) void guidance_prepare_kernel(const double* x_i
     }
     coef[b * 2] = (float)alpha;
     coef[b * 2 + 1] = (float)gamma;
-}
-
-__global__ __launch_bounds__(256) void heun_coef_update_kernel(const double* x_hat, const double* x_in, const float* Fc, const float* M,
-                                                               const float* coef, double* d_cur, double* x_next, int64_t n, int64_t per,
-                                                               double t_in, double t_hat, double t_next, float sigma_data, int second) {
-    float c_skip, c_out;
-    heun_coef(t_in, sigma_data, c_skip, c_out);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int64_t b = i / per;
-        const double xi = x_in[i];
-        const double D = sampler_guided(xi, Fc[i], M[i], c_skip, c_out, coef[b * 2], coef[b * 2 + 1]);
-        double d;
-        x_next[i] = heun_from_denoised(xi, x_hat[i], D, t_in, t_hat, t_next, second, second ? d_cur[i] : 0.0, d);
-        if (!second) d_cur[i] = d;
-    }
-}
-
-__global__ __launch_bounds__(256) void solver_coef_update_kernel(const double* x_in, const float* Fc, const float* M, const float* coef,
-                                                                 double* hist, double* x_next, int64_t n, int64_t per, double t_in,
-                                                                 float sigma_data, double a, double b, double c1, double c2) {
-    float c_skip, c_out;
-    heun_coef(t_in, sigma_data, c_skip, c_out);
-    const bool use_hist = c2 != 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int64_t s = i / per;
-        const double xi = x_in[i];
-        const double den = sampler_guided(xi, Fc[i], M[i], c_skip, c_out, coef[s * 2], coef[s * 2 + 1]);
-        x_next[i] = solver_from_denoised(xi, den, a, b, c1, c2, use_hist ? hist[i] : 0.0);
-        hist[i] = den;
-    }
-}
-
-// The token-space forms: F_c as in heun_update_tok_kernel, M and the coefficients of the item's sample from the image-layout buffers.
-template <bool VEC>
-__global__ __launch_bounds__(256) void heun_coef_update_tok_kernel(const double* x_hat, const double* x_in, const bf16* tok, const float* M,
-                                                                   const float* coef, double* d_cur, double* x_next, int64_t B, int C, int H,
-                                                                   int W, int p, double t_in, double t_hat, double t_next, float sigma_data,
-                                                                   int second) {
-    float c_skip, c_out;
-    heun_coef(t_in, sigma_data, c_skip, c_out);
-    const int gh = H / p, gw = W / p, pv = C * p * p, nseg = (pv + 7) / 8;
-    const int64_t rows = B * gh * gw, total = rows * nseg;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const tok_item t = tok_item_of(i, gh, gw, nseg);
-        const bf16* fc = tok + t.row * pv + t.e0;
-        const float alpha = coef[t.b * 2], gamma = coef[t.b * 2 + 1];
-        U128 vc;
-        if (VEC) vc.h = ld_bf16x8(fc);
-        int64_t pix[8];
-        double xi[8], xh[8], dp[8];
-        float m[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {          // every load of the item before its first store (x_next may alias x_in / x_hat)
-            const int e = t.e0 + j;
-            if (!VEC && e >= pv) break;
-            const int c = e % C, pw = (e / C) % p, ph = e / (C * p);
-            pix[j] = ((t.b * C + c) * H + t.ti * p + ph) * W + t.tj * p + pw;
-            xi[j] = x_in[pix[j]];
-            xh[j] = x_hat[pix[j]];
-            dp[j] = second ? d_cur[pix[j]] : 0.0;
-            m[j] = M[pix[j]];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (!VEC && t.e0 + j >= pv) break;
-            const double D = sampler_guided(xi[j], bf2f(VEC ? vc.e[j] : fc[j]), m[j], c_skip, c_out, alpha, gamma);
-            double d;
-            x_next[pix[j]] = heun_from_denoised(xi[j], xh[j], D, t_in, t_hat, t_next, second, dp[j], d);
-            if (!second) d_cur[pix[j]] = d;
-        }
-    }
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void solver_coef_update_tok_kernel(const double* x_in, const bf16* tok, const float* M, const float* coef,
-                                                                     double* hist, double* x_next, int64_t B, int C, int H, int W, int p,
-                                                                     double t_in, float sigma_data, double a, double b, double c1, double c2) {
-    float c_skip, c_out;
-    heun_coef(t_in, sigma_data, c_skip, c_out);
-    const bool use_hist = c2 != 0.0;
-    const int gh = H / p, gw = W / p, pv = C * p * p, nseg = (pv + 7) / 8;
-    const int64_t rows = B * gh * gw, total = rows * nseg;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const tok_item t = tok_item_of(i, gh, gw, nseg);
-        const bf16* fc = tok + t.row * pv + t.e0;
-        const float alpha = coef[t.b * 2], gamma = coef[t.b * 2 + 1];
-        U128 vc;
-        if (VEC) vc.h = ld_bf16x8(fc);
-        int64_t pix[8];
-        double xi[8], hp[8];
-        float m[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {          // every load of the item before its first store (x_next may alias x_in)
-            const int e = t.e0 + j;
-            if (!VEC && e >= pv) break;
-            const int c = e % C, pw = (e / C) % p, ph = e / (C * p);
-            pix[j] = ((t.b * C + c) * H + t.ti * p + ph) * W + t.tj * p + pw;
-            xi[j] = x_in[pix[j]];
-            hp[j] = use_hist ? hist[pix[j]] : 0.0;
-            m[j] = M[pix[j]];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (!VEC && t.e0 + j >= pv) break;
-            const double den = sampler_guided(xi[j], bf2f(VEC ? vc.e[j] : fc[j]), m[j], c_skip, c_out, alpha, gamma);
-            x_next[pix[j]] = solver_from_denoised(xi[j], den, a, b, c1, c2, hp[j]);
-            hist[pix[j]] = den;
-        }
-    }
 }
 
 // Everything md_guidance_prepare(_tok) refuses about the mode and its parameters; the comparisons are written so that a NaN fails them.
@@ -743,27 +614,12 @@ extern "C" int md_edm_sampler_input(const double* x, float* out, int64_t n, floa
     return 0;
 }
 
-extern "C" int md_edm_heun_update(const double* x_hat, const double* x_in, const float* F, double* d_cur, double* x_next, int64_t n,
-                                  float cfg, int32_t has_uncond, double t_in, double t_hat, double t_next, float sigma_data,
-                                  int32_t second, hipStream_t st) {
-    if (!x_hat || !x_in || !F || !d_cur || !x_next || n <= 0 || t_in <= 0) return MD_BAD_ARG;
-    return launch_heun_update(x_hat, x_in, F, has_uncond ? F + n : nullptr, d_cur, x_next, n, cfg, t_in, t_hat, t_next, sigma_data, second,
-                              st);
-}
-
-extern "C" int md_edm_heun_update_guide(const double* x_hat, const double* x_in, const float* F, const float* F_guide, double* d_cur,
-                                        double* x_next, int64_t n, float cfg, double t_in, double t_hat, double t_next, float sigma_data,
-                                        int32_t second, hipStream_t st) {
-    if (!x_hat || !x_in || !F || !F_guide || !d_cur || !x_next || n <= 0 || t_in <= 0) return MD_BAD_ARG;
-    return launch_heun_update(x_hat, x_in, F, F_guide, d_cur, x_next, n, cfg, t_in, t_hat, t_next, sigma_data, second, st);
-}
-
 extern "C" int md_edm_sampler_patchify(const double* x, void* patches_bf16, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p,
                                        float sigma, float sigma_data, int32_t duplicate, hipStream_t st) {
-    if (!x || !patches_bf16 || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p) return MD_BAD_ARG;
-    const int pv = C * p * p;
-    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
-    if (pv % 8 == 0 && aligned16(patches_bf16))
+    if (!x || !patches_bf16 || !tok_geometry_ok(B, C, H, W, p)) return MD_BAD_ARG;
+    const tok_geometry g = tok_geometry_of(B, C, H, W, p);
+    const int64_t items = g.items();
+    if (g.pv % 8 == 0 && aligned16(patches_bf16))
         hipLaunchKernelGGL(sampler_patchify_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x, (bf16*)patches_bf16, B, C, H, W, p,
                            sigma, sigma_data, duplicate);
     else
@@ -771,61 +627,6 @@ extern "C" int md_edm_sampler_patchify(const double* x, void* patches_bf16, int6
                            sigma, sigma_data, duplicate);
     MD_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int md_edm_heun_update_tok(const double* x_hat, const double* x_in, const void* tok_bf16, double* d_cur, double* x_next,
-                                      int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg, int32_t has_uncond, double t_in,
-                                      double t_hat, double t_next, float sigma_data, int32_t second, hipStream_t st) {
-    if (!x_hat || !x_in || !tok_bf16 || !d_cur || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
-        t_in <= 0)
-        return MD_BAD_ARG;
-    const bf16* tok = (const bf16*)tok_bf16;
-    return launch_heun_update_tok(x_hat, x_in, tok, has_uncond ? tok + uncond_offset(B, C, H, W, p) : nullptr, d_cur, x_next, B, C, H, W, p,
-                                  cfg, t_in, t_hat, t_next, sigma_data, second, st);
-}
-
-extern "C" int md_edm_heun_update_guide_tok(const double* x_hat, const double* x_in, const void* tok_bf16, const void* tok_guide_bf16,
-                                            double* d_cur, double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg,
-                                            double t_in, double t_hat, double t_next, float sigma_data, int32_t second, hipStream_t st) {
-    if (!x_hat || !x_in || !tok_bf16 || !tok_guide_bf16 || !d_cur || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p ||
-        W % p || t_in <= 0)
-        return MD_BAD_ARG;
-    return launch_heun_update_tok(x_hat, x_in, (const bf16*)tok_bf16, (const bf16*)tok_guide_bf16, d_cur, x_next, B, C, H, W, p, cfg, t_in,
-                                  t_hat, t_next, sigma_data, second, st);
-}
-
-extern "C" int md_edm_solver_update(const double* x_in, const float* F, double* hist, double* x_next, int64_t n, float cfg,
-                                    int32_t has_uncond, double t_in, float sigma_data, double a, double b, double c1, double c2,
-                                    hipStream_t st) {
-    if (!x_in || !F || !hist || !x_next || n <= 0 || t_in <= 0) return MD_BAD_ARG;
-    return launch_solver_update(x_in, F, has_uncond ? F + n : nullptr, hist, x_next, n, cfg, t_in, sigma_data, a, b, c1, c2, st);
-}
-
-extern "C" int md_edm_solver_update_guide(const double* x_in, const float* F, const float* F_guide, double* hist, double* x_next, int64_t n,
-                                          float cfg, double t_in, float sigma_data, double a, double b, double c1, double c2,
-                                          hipStream_t st) {
-    if (!x_in || !F || !F_guide || !hist || !x_next || n <= 0 || t_in <= 0) return MD_BAD_ARG;
-    return launch_solver_update(x_in, F, F_guide, hist, x_next, n, cfg, t_in, sigma_data, a, b, c1, c2, st);
-}
-
-extern "C" int md_edm_solver_update_tok(const double* x_in, const void* tok_bf16, double* hist, double* x_next, int64_t B, int32_t C,
-                                        int32_t H, int32_t W, int32_t p, float cfg, int32_t has_uncond, double t_in, float sigma_data,
-                                        double a, double b, double c1, double c2, hipStream_t st) {
-    if (!x_in || !tok_bf16 || !hist || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p || t_in <= 0)
-        return MD_BAD_ARG;
-    const bf16* tok = (const bf16*)tok_bf16;
-    return launch_solver_update_tok(x_in, tok, has_uncond ? tok + uncond_offset(B, C, H, W, p) : nullptr, hist, x_next, B, C, H, W, p, cfg,
-                                    t_in, sigma_data, a, b, c1, c2, st);
-}
-
-extern "C" int md_edm_solver_update_guide_tok(const double* x_in, const void* tok_bf16, const void* tok_guide_bf16, double* hist,
-                                              double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg, double t_in,
-                                              float sigma_data, double a, double b, double c1, double c2, hipStream_t st) {
-    if (!x_in || !tok_bf16 || !tok_guide_bf16 || !hist || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
-        t_in <= 0)
-        return MD_BAD_ARG;
-    return launch_solver_update_tok(x_in, (const bf16*)tok_bf16, (const bf16*)tok_guide_bf16, hist, x_next, B, C, H, W, p, cfg, t_in,
-                                    sigma_data, a, b, c1, c2, st);
 }
 
 extern "C" int md_edm_churn(const double* x, const double* noise, double* x_hat, int64_t n, double coef, hipStream_t st) {
@@ -853,8 +654,8 @@ extern "C" int md_guidance_prepare_tok(const double* x_in, const void* tok_bf16,
                                        double* moments, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, double t_in, float sigma_data,
                                        int32_t mode, double w, double rescale_phi, double apg_eta, int32_t has_norm_threshold,
                                        double apg_norm_threshold, double apg_momentum, int32_t first, hipStream_t st) {
-    if (!x_in || !tok_bf16 || !tok_u_bf16 || !M || !coef || !moments || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
-        !(t_in > 0) || !guidance_args_ok(mode, w, rescale_phi, apg_eta, has_norm_threshold, apg_norm_threshold, apg_momentum))
+    if (!x_in || !tok_bf16 || !tok_u_bf16 || !M || !coef || !moments || !tok_geometry_ok(B, C, H, W, p) || !(t_in > 0) ||
+        !guidance_args_ok(mode, w, rescale_phi, apg_eta, has_norm_threshold, apg_norm_threshold, apg_momentum))
         return MD_BAD_ARG;
     hipLaunchKernelGGL(guidance_prepare_kernel<true>, dim3((unsigned)B), dim3(256), 0, st, x_in, tok_bf16, tok_u_bf16, M, coef, moments,
                        (int64_t)C * H * W, C, H, W, p, t_in, sigma_data,
@@ -863,60 +664,102 @@ extern "C" int md_guidance_prepare_tok(const double* x_in, const void* tok_bf16,
     return 0;
 }
 
+// The twelve update entry points: {heun, solver} x {cfg pair in one buffer, cfg pair in two (_guide), coefficient form (_coef)} x {image,
+// _tok}.  Each checks its arguments and makes one launch_update(_tok) call; a time that is not positive (NaN included) is refused.
+extern "C" int md_edm_heun_update(const double* x_hat, const double* x_in, const float* F, double* d_cur, double* x_next, int64_t n,
+                                  float cfg, int32_t has_uncond, double t_in, double t_hat, double t_next, float sigma_data,
+                                  int32_t second, hipStream_t st) {
+    if (!x_hat || !x_in || !F || !d_cur || !x_next || n <= 0 || !(t_in > 0)) return MD_BAD_ARG;
+    return launch_update(cfg_pair<float>(F, n, cfg, has_uncond), heun_step{x_hat, d_cur, t_hat, t_next, second}, x_in, x_next, n, t_in,
+                         sigma_data, st);
+}
+
+extern "C" int md_edm_heun_update_guide(const double* x_hat, const double* x_in, const float* F, const float* F_guide, double* d_cur,
+                                        double* x_next, int64_t n, float cfg, double t_in, double t_hat, double t_next, float sigma_data,
+                                        int32_t second, hipStream_t st) {
+    if (!x_hat || !x_in || !F || !F_guide || !d_cur || !x_next || n <= 0 || !(t_in > 0)) return MD_BAD_ARG;
+    return launch_update(cfg_source<float>{F, F_guide, cfg}, heun_step{x_hat, d_cur, t_hat, t_next, second}, x_in, x_next, n, t_in, sigma_data,
+                         st);
+}
+
 extern "C" int md_edm_heun_update_coef(const double* x_hat, const double* x_in, const float* F_c, const float* M, const float* coef,
                                        double* d_cur, double* x_next, int64_t B, int64_t per_sample, double t_in, double t_hat, double t_next,
                                        float sigma_data, int32_t second, hipStream_t st) {
     if (!x_hat || !x_in || !F_c || !M || !coef || !d_cur || !x_next || B <= 0 || per_sample <= 0 || !(t_in > 0)) return MD_BAD_ARG;
-    const int64_t n = B * per_sample;
-    hipLaunchKernelGGL(heun_coef_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_hat, x_in, F_c, M, coef, d_cur, x_next, n, per_sample, t_in,
-                       t_hat, t_next, sigma_data, second);
-    MD_LAUNCH_CHECK();
-    return 0;
+    return launch_update(coef_source<float>{F_c, M, coef, per_sample}, heun_step{x_hat, d_cur, t_hat, t_next, second}, x_in, x_next,
+                         B * per_sample, t_in, sigma_data, st);
+}
+
+extern "C" int md_edm_heun_update_tok(const double* x_hat, const double* x_in, const void* tok_bf16, double* d_cur, double* x_next,
+                                      int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg, int32_t has_uncond, double t_in,
+                                      double t_hat, double t_next, float sigma_data, int32_t second, hipStream_t st) {
+    if (!x_hat || !x_in || !tok_bf16 || !d_cur || !x_next || !tok_geometry_ok(B, C, H, W, p) || !(t_in > 0)) return MD_BAD_ARG;
+    const tok_geometry g = tok_geometry_of(B, C, H, W, p);
+    return launch_update_tok(cfg_pair<bf16>(tok_bf16, g.rows() * g.pv, cfg, has_uncond), heun_step{x_hat, d_cur, t_hat, t_next, second}, x_in,
+                             x_next, g, t_in, sigma_data, st);
+}
+
+extern "C" int md_edm_heun_update_guide_tok(const double* x_hat, const double* x_in, const void* tok_bf16, const void* tok_guide_bf16,
+                                            double* d_cur, double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg,
+                                            double t_in, double t_hat, double t_next, float sigma_data, int32_t second, hipStream_t st) {
+    if (!x_hat || !x_in || !tok_bf16 || !tok_guide_bf16 || !d_cur || !x_next || !tok_geometry_ok(B, C, H, W, p) || !(t_in > 0))
+        return MD_BAD_ARG;
+    return launch_update_tok(cfg_source<bf16>{(const bf16*)tok_bf16, (const bf16*)tok_guide_bf16, cfg},
+                             heun_step{x_hat, d_cur, t_hat, t_next, second}, x_in, x_next, tok_geometry_of(B, C, H, W, p), t_in, sigma_data, st);
+}
+
+extern "C" int md_edm_heun_update_coef_tok(const double* x_hat, const double* x_in, const void* tok_bf16, const float* M, const float* coef,
+                                           double* d_cur, double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, double t_in,
+                                           double t_hat, double t_next, float sigma_data, int32_t second, hipStream_t st) {
+    if (!x_hat || !x_in || !tok_bf16 || !M || !coef || !d_cur || !x_next || !tok_geometry_ok(B, C, H, W, p) || !(t_in > 0)) return MD_BAD_ARG;
+    return launch_update_tok(coef_source<bf16>{(const bf16*)tok_bf16, M, coef, (int64_t)C * H * W}, heun_step{x_hat, d_cur, t_hat, t_next, second},
+                             x_in, x_next, tok_geometry_of(B, C, H, W, p), t_in, sigma_data, st);
+}
+
+extern "C" int md_edm_solver_update(const double* x_in, const float* F, double* hist, double* x_next, int64_t n, float cfg,
+                                    int32_t has_uncond, double t_in, float sigma_data, double a, double b, double c1, double c2,
+                                    hipStream_t st) {
+    if (!x_in || !F || !hist || !x_next || n <= 0 || !(t_in > 0)) return MD_BAD_ARG;
+    return launch_update(cfg_pair<float>(F, n, cfg, has_uncond), solver_step{hist, a, b, c1, c2}, x_in, x_next, n, t_in, sigma_data, st);
+}
+
+extern "C" int md_edm_solver_update_guide(const double* x_in, const float* F, const float* F_guide, double* hist, double* x_next, int64_t n,
+                                          float cfg, double t_in, float sigma_data, double a, double b, double c1, double c2,
+                                          hipStream_t st) {
+    if (!x_in || !F || !F_guide || !hist || !x_next || n <= 0 || !(t_in > 0)) return MD_BAD_ARG;
+    return launch_update(cfg_source<float>{F, F_guide, cfg}, solver_step{hist, a, b, c1, c2}, x_in, x_next, n, t_in, sigma_data, st);
 }
 
 extern "C" int md_edm_solver_update_coef(const double* x_in, const float* F_c, const float* M, const float* coef, double* hist, double* x_next,
                                          int64_t B, int64_t per_sample, double t_in, float sigma_data, double a, double b, double c1, double c2,
                                          hipStream_t st) {
     if (!x_in || !F_c || !M || !coef || !hist || !x_next || B <= 0 || per_sample <= 0 || !(t_in > 0)) return MD_BAD_ARG;
-    const int64_t n = B * per_sample;
-    hipLaunchKernelGGL(solver_coef_update_kernel, dim3(egrid(n)), dim3(256), 0, st, x_in, F_c, M, coef, hist, x_next, n, per_sample, t_in,
-                       sigma_data, a, b, c1, c2);
-    MD_LAUNCH_CHECK();
-    return 0;
+    return launch_update(coef_source<float>{F_c, M, coef, per_sample}, solver_step{hist, a, b, c1, c2}, x_in, x_next, B * per_sample, t_in,
+                         sigma_data, st);
 }
 
-extern "C" int md_edm_heun_update_coef_tok(const double* x_hat, const double* x_in, const void* tok_bf16, const float* M, const float* coef,
-                                           double* d_cur, double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, double t_in,
-                                           double t_hat, double t_next, float sigma_data, int32_t second, hipStream_t st) {
-    if (!x_hat || !x_in || !tok_bf16 || !M || !coef || !d_cur || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
-        !(t_in > 0))
-        return MD_BAD_ARG;
-    const int pv = C * p * p;
-    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
-    if (pv % 8 == 0 && aligned16(tok_bf16))
-        hipLaunchKernelGGL(heun_coef_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, (const bf16*)tok_bf16, M, coef,
-                           d_cur, x_next, B, C, H, W, p, t_in, t_hat, t_next, sigma_data, second);
-    else
-        hipLaunchKernelGGL(heun_coef_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_hat, x_in, (const bf16*)tok_bf16, M, coef,
-                           d_cur, x_next, B, C, H, W, p, t_in, t_hat, t_next, sigma_data, second);
-    MD_LAUNCH_CHECK();
-    return 0;
+extern "C" int md_edm_solver_update_tok(const double* x_in, const void* tok_bf16, double* hist, double* x_next, int64_t B, int32_t C,
+                                        int32_t H, int32_t W, int32_t p, float cfg, int32_t has_uncond, double t_in, float sigma_data,
+                                        double a, double b, double c1, double c2, hipStream_t st) {
+    if (!x_in || !tok_bf16 || !hist || !x_next || !tok_geometry_ok(B, C, H, W, p) || !(t_in > 0)) return MD_BAD_ARG;
+    const tok_geometry g = tok_geometry_of(B, C, H, W, p);
+    return launch_update_tok(cfg_pair<bf16>(tok_bf16, g.rows() * g.pv, cfg, has_uncond), solver_step{hist, a, b, c1, c2}, x_in, x_next, g, t_in,
+                             sigma_data, st);
+}
+
+extern "C" int md_edm_solver_update_guide_tok(const double* x_in, const void* tok_bf16, const void* tok_guide_bf16, double* hist,
+                                              double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg, double t_in,
+                                              float sigma_data, double a, double b, double c1, double c2, hipStream_t st) {
+    if (!x_in || !tok_bf16 || !tok_guide_bf16 || !hist || !x_next || !tok_geometry_ok(B, C, H, W, p) || !(t_in > 0)) return MD_BAD_ARG;
+    return launch_update_tok(cfg_source<bf16>{(const bf16*)tok_bf16, (const bf16*)tok_guide_bf16, cfg}, solver_step{hist, a, b, c1, c2}, x_in,
+                             x_next, tok_geometry_of(B, C, H, W, p), t_in, sigma_data, st);
 }
 
 extern "C" int md_edm_solver_update_coef_tok(const double* x_in, const void* tok_bf16, const float* M, const float* coef, double* hist,
                                              double* x_next, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, double t_in,
                                              float sigma_data, double a, double b, double c1, double c2, hipStream_t st) {
-    if (!x_in || !tok_bf16 || !M || !coef || !hist || !x_next || B <= 0 || C <= 0 || H <= 0 || W <= 0 || p <= 0 || H % p || W % p ||
-        !(t_in > 0))
-        return MD_BAD_ARG;
-    const int pv = C * p * p;
-    const int64_t items = B * (H / p) * (W / p) * ((pv + 7) / 8);
-    if (pv % 8 == 0 && aligned16(tok_bf16))
-        hipLaunchKernelGGL(solver_coef_update_tok_kernel<true>, dim3(egrid(items)), dim3(256), 0, st, x_in, (const bf16*)tok_bf16, M, coef, hist,
-                           x_next, B, C, H, W, p, t_in, sigma_data, a, b, c1, c2);
-    else
-        hipLaunchKernelGGL(solver_coef_update_tok_kernel<false>, dim3(egrid(items)), dim3(256), 0, st, x_in, (const bf16*)tok_bf16, M, coef, hist,
-                           x_next, B, C, H, W, p, t_in, sigma_data, a, b, c1, c2);
-    MD_LAUNCH_CHECK();
-    return 0;
+    if (!x_in || !tok_bf16 || !M || !coef || !hist || !x_next || !tok_geometry_ok(B, C, H, W, p) || !(t_in > 0)) return MD_BAD_ARG;
+    return launch_update_tok(coef_source<bf16>{(const bf16*)tok_bf16, M, coef, (int64_t)C * H * W}, solver_step{hist, a, b, c1, c2}, x_in, x_next,
+                             tok_geometry_of(B, C, H, W, p), t_in, sigma_data, st);
 }
+

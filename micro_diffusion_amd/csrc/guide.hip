@@ -8,18 +8,19 @@
 // atomics; two calls give the same bits.
 #include "md_common.h"
 #include "sampler_math.h"
+#include "sampler_tok.h"
 #include "../../include/microdit_hip.h"
 #include <cmath>
 
 namespace {
 
+// the grid helper of edm.hip
 inline int egrid(int64_t work) {
     int64_t g = (work + 255) / 256;
     if (g > 8192) g = 8192;
     if (g < 1) g = 1;
     return (int)g;
 }
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // md_edm_denoised: item = 4 consecutive elements (two 16-byte loads of the state, one of each F, one 16-byte store), or one element.
@@ -51,30 +52,7 @@ __global__ __launch_bounds__(256) void denoised_kernel(const double* x_in, const
     }
 }
 
-// Token-space items as in edm.hip: one 8-element (16-byte) segment of one token row, ordered (b, ti, segment, tj) with tj fastest, so
-// the lanes of a wave walk along w of the image-shaped operand.  VEC: the bf16 segment moves as one 16-byte piece; rows that are no
-// multiple of 8 wide, or a misaligned base, go element by element.
-struct tok_item {
-    int64_t b, row;     // sample, token row b * T + ti * gw + tj
-    int ti, tj, e0;     // grid position, first element of the segment
-};
-__device__ __forceinline__ tok_item tok_item_of(int64_t i, int gh, int gw, int nseg) {
-    tok_item t;
-    t.tj = (int)(i % gw);
-    const int64_t r = i / gw;
-    t.e0 = (int)(r % nseg) * 8;
-    const int64_t bt = r / nseg;
-    t.ti = (int)(bt % gh);
-    t.b = bt / gh;
-    t.row = (t.b * gh + t.ti) * gw + t.tj;
-    return t;
-}
-// image offset of element e = (ph * p + pw) * C + c of the token at (b, ti, tj)
-__device__ __forceinline__ int64_t tok_pixel(const tok_item& t, int e, int C, int H, int W, int p) {
-    const int c = e % C, pw = (e / C) % p, ph = e / (C * p);
-    return ((t.b * C + c) * H + t.ti * p + ph) * W + t.tj * p + pw;
-}
-
+// Token-space items: sampler_tok.h.
 // D[b, c, ti*p+ph, tj*p+pw] from tok[row, (ph*p + pw)*C + c] (the second operand: the same row of tok_u): md_unpatchify followed by
 // denoised_kernel, without the fp32 image of F in between
 template <bool VEC>
@@ -286,7 +264,7 @@ extern "C" int md_edm_denoised(const double* x_in, const float* F, float* D, int
 
 extern "C" int md_edm_denoised_tok(const double* x_in, const void* tok_bf16, float* D, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p,
                                    float cfg, int32_t has_uncond, double t_in, float sigma_data, hipStream_t st) {
-    if (!x_in || !tok_bf16 || !D || !image_ok(B, C, H, W) || p <= 0 || H % p || W % p || !level_ok(t_in, sigma_data) || !std::isfinite(cfg))
+    if (!x_in || !tok_bf16 || !D || !tok_geometry_ok(B, C, H, W, p) || !level_ok(t_in, sigma_data) || !std::isfinite(cfg))
         return MD_BAD_ARG;
     const int pv = C * p * p;
     const int64_t rows = B * (H / p) * (W / p), items = rows * ((pv + 7) / 8);
@@ -321,7 +299,7 @@ extern "C" int md_measure_residual(const float* D, const float* meas, const floa
 
 extern "C" int md_guide_cotangent_tok(const float* q, void* dtok_bf16, int64_t B, int32_t C, int32_t H, int32_t W, int32_t p, float cfg,
                                       int32_t has_uncond, double t_in, float sigma_data, hipStream_t st) {
-    if (!q || !dtok_bf16 || !image_ok(B, C, H, W) || p <= 0 || H % p || W % p || !level_ok(t_in, sigma_data) || !std::isfinite(cfg))
+    if (!q || !dtok_bf16 || !tok_geometry_ok(B, C, H, W, p) || !level_ok(t_in, sigma_data) || !std::isfinite(cfg))
         return MD_BAD_ARG;
     const int pv = C * p * p;
     const int64_t rows = B * (H / p) * (W / p), items = rows * ((pv + 7) / 8);
